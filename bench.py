@@ -7,15 +7,26 @@ master parameters).
     python bench.py --gpus N --steps K --warmup W          # N > 1 without a launcher: starts its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                                 # + the evidence blocks below (about a minute more)
+    python bench.py --dump-outputs DIR                     # + what the last timed step computed, as DIR/<name>.npy
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline fields (metric,
+value, unit, ms_per_step, dtype, ...); the blocks below stay null.  With --full the line also carries
   roofline     : the dominant kernel family of the step, timed live with HIP events on the launch stream in
                  a separate instrumented pass (the timed region itself carries no instrumentation);
   cpu_baseline : the CPU oracle (oracle/, stock PyTorch fp32 ops = the reference algorithm) timed on the host
                  cores on a bounded sample of the same workload (rank 0, N=1 only); its `parity` entry is the
                  metric's "IoU parity vs CPU ref": fp32-mode logits / argmax masks / mIoU of the HIP path against
                  that same oracle on the same sample;
-  kernels      : per-kernel-family ms/step and achieved TFLOP/s / GB/s (algorithmic counts).
+  kernels      : per-kernel-family ms/step and achieved TFLOP/s / GB/s (algorithmic counts);
+and levels, launch_census, other_configs, clock, allreduce_overlap (profiles/README.md).
+
+--dump-outputs DIR writes, on rank 0, what the caller of the timed step holds after the last timed step (before anything
+else runs): loss.npy (float64 scalar), logits.npy (the step's forward output, float32), params.npy / grads.npy (the
+trainable parameters after the optimizer step and their gradients, float32, flattened in named_parameters() order) and
+buffers.npy (the floating-point buffers, e.g. BatchNorm running statistics).  An array larger than its share of the 64 MB
+budget is replaced by a fixed seeded sample of its flattened elements (same indices for params and grads).  Inputs and
+initial weights are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -61,10 +72,54 @@ def labels(shape, seed, num_classes):
     return torch.from_numpy(lab.reshape(shape))
 
 
-def run_workload(args, world, rank, dev, want_levels=False):
+def _sample_index(n, cap, seed):
+    """None when n <= cap (keep every element), else a fixed seeded sample of at most `cap` indices, ascending."""
+    import numpy as np
+    if n <= cap:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=cap))
+
+
+def _flat(t, idx):
+    import torch
+    t = t.detach().reshape(-1)
+    if idx is not None:
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """--dump-outputs: the arrays the caller of the timed step holds after the last timed step (module docstring), as
+    float32 / float64 .npy files under out_dir; logits at most 8 Mi elements, the others 2 Mi each (<= 56 MiB in all)."""
+    import numpy as np
+    import torch
+    cap = 1 << 23
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                        for p in params])
+    pidx = _sample_index(flat_p.numel(), cap // 4, seed=2)
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    flat_b = torch.cat(bufs) if bufs else torch.zeros(0, device=flat_p.device)
+    lg = logits.detach()
+    lidx = _sample_index(lg.numel(), cap, seed=1)
+    arrays = {
+        "loss": np.asarray(loss.item(), dtype=np.float64),
+        "logits": lg.float().cpu().numpy() if lidx is None else _flat(lg, lidx),
+        "params": _flat(flat_p, pidx),
+        "grads": _flat(flat_g, pidx),
+        "buffers": _flat(flat_b, _sample_index(flat_b.numel(), cap // 4, seed=3)),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_workload(args, world, rank, dev, want_levels=False, dump_dir=None):
     """Build the model of `args` (model / batch / size / dtype / loss), run args.warmup untimed and args.steps timed
-    training steps bracketed by barrier + synchronize, then args.profile_steps instrumented steps (HIP events on the launch
-    stream around every kernel family; every rank runs them -- they contain the gradient all-reduce -- rank 0 records).
+    training steps bracketed by barrier + synchronize, write the last timed step's outputs to dump_dir (rank 0, if given),
+    then args.profile_steps instrumented steps (HIP events on the launch stream around every kernel family; every rank runs
+    them -- they contain the gradient all-reduce -- rank 0 records).
     Returns the max-over-ranks time of the timed region and the per-family (and, for the U-Net, per-level) event sums."""
     import torch
     import torch.distributed as dist
@@ -97,7 +152,8 @@ def run_workload(args, world, rank, dev, want_levels=False):
         opt.zero_grad(set_to_none=True)
         if gs is not None:
             gs.arm()
-        loss = loss_fn(model(X), Y)
+        logits = model(X)
+        loss = loss_fn(logits, Y)
         if gs is not None:
             gs.backward_begin()
         loss.backward()
@@ -105,7 +161,7 @@ def run_workload(args, world, rank, dev, want_levels=False):
             gs.backward_end()
             gs.sync()
         opt.step()
-        return loss
+        return loss, logits
 
     def barrier():
         if world > 1:
@@ -117,7 +173,7 @@ def run_workload(args, world, rank, dev, want_levels=False):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -125,6 +181,8 @@ def run_workload(args, world, rank, dev, want_levels=False):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = loss.item()
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, logits, model)
 
     prof, level_prof, overlap = {}, {}, None
     if args.profile_steps > 0:
@@ -261,14 +319,23 @@ def main():
     ap.add_argument("--model", choices=["unet", "clipunet"], default="unet",
                     help="clipunet = BASELINE config 4 (use --batch 16 --size 224): frozen ViT-B/16 (local random-weight "
                          "config) + HIP decoder, 4 classes; not the headline metric")
-    ap.add_argument("--profile-steps", type=int, default=3, help="instrumented steps for the roofline block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline timed region, also measure the evidence blocks: "
+                    "instrumented steps (roofline, kernels), CPU baseline + parity, per-level table, launch census, "
+                    "other BASELINE configurations, clock probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--profile-steps", type=int, default=None, help="instrumented steps for the roofline block "
+                    "(default 3 with --full, else 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); 'gloo' only to rehearse "
                     "the multi-rank code path on a box with fewer GPUs than ranks")
     ap.add_argument("--share-device", action="store_true", help="rehearsal only: every rank uses cuda:0 (needs --backend gloo)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the blocks appended after the headline timed region "
-                    "(per-level roofline table, other BASELINE configurations, clock probe)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the blocks appended after the headline timed "
+                    "region (per-level roofline table, launch census, other BASELINE configurations, clock probe)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.profile_steps is None:
+        args.profile_steps = 3 if args.full else 0
 
     # dmabuf IPC: RCCL needs it on this driver.  Set before torch is imported, for every way a rank can be started -- by
     # the self-launch below (inherited) and by the driver's own `python -m torch.distributed.run ... bench.py` alike.
@@ -319,7 +386,8 @@ def main():
             dist.init_process_group(args.backend)
 
     B, S = args.batch, args.size
-    w = run_workload(args, world, rank, dev, want_levels=(args.model == "unet" and not args.no_extras))
+    w = run_workload(args, world, rank, dev, want_levels=(args.full and args.model == "unet" and not args.no_extras),
+                     dump_dir=args.dump_outputs)
     dt, final_loss, prof, level_prof, overlap = w["dt"], w["final_loss"], w["prof"], w["levels"], w["overlap"]
     me = {"rank": rank, "device": local, "name": torch.cuda.get_device_name(local)}
     ranks_info = [me]
@@ -409,7 +477,7 @@ def main():
                  "frac_of_6.29TBps_copy": round(gbps * 1e9 / HBM_COPY, 4)}
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.model == "unet":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.model == "unet":
         cpu = cpu_baseline(S)
 
     # ---- appended evidence (after the headline timed region, which stays un-instrumented): per-level two-roof table, the
@@ -417,7 +485,7 @@ def main():
     levels = level_table(level_prof, n, peak) if level_prof else None
     extras, clock = None, None
     headline = (args.model == "unet" and B == 32 and S == 256 and args.loss == "ce" and args.dtype == "bf16")
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             clock = ops.clock_probe()
         except Exception as e:

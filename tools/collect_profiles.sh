@@ -16,9 +16,9 @@ echo "write done"
 python $R/tools/pmc_post.py traffic $OUT $R
 # the bench attaches a PMC record only when its build_id matches the library: put this run's record where bench.py looks
 cp $OUT/pmc_traffic.json $R/profiles/${TAG}_pmc_traffic.json
-timeout -k 10 500 python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 500 python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r -- python $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 echo "stats done"
 
 cp $OUT/stats/r_kernel_stats.csv $OUT/kernel_stats.csv
