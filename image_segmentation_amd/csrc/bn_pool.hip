@@ -495,9 +495,6 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
       sg[j] = 0.f; sgx[j] = 0.f;
     }
   }
-#ifdef SEGK_POOL_NO_Z
-  from_z = false;                                  // diagnostic build: the kernel without its rare path (A/B of its cost)
-#endif
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)total; i += gridDim.x * 256u) {
     const Idx4 ix = split4(i, (unsigned)CV, (unsigned)Wc, (unsigned)Hc);
     const int cv = ix.cv, xo = ix.x, yo = ix.y, b = ix.b;

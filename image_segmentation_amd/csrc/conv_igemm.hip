@@ -24,7 +24,6 @@
 // Epilogue: optional bias, per-channel sum / sum-of-squares partials for training-mode BatchNorm taken
 // from the fp32 accumulators (deterministic per-tile partials, no atomics), LDS transpose, 16-byte
 // coalesced NHWC stores (optionally split over two destinations, or pixel-shuffled for ConvTranspose).
-#include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
 #include "segk_internal.h"
@@ -428,20 +427,21 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_igemm_kernel(const ConvA
 //
 // Structure here: the 8 waves of a workgroup split into
 //   * 4 CONSUMER waves (one per SIMD, raised priority), each owning a 128-pixel x 64-channel tile of the
-//     256 x 128 workgroup tile: their stream is nothing but MFMAs and ds_read_b128 fragment reads (6 reads
-//     per 8 MFMAs, one sub-step ahead; the first fragments of the next step are read BEFORE the barrier
-//     that ends the current one);
+//     256 x 128 workgroup tile: their stream is nothing but MFMAs and ds_read_b128 fragment reads (one
+//     sub-step ahead; the first fragments of the next step are read BEFORE the barrier that ends the
+//     current one);
 //   * 4 PRODUCER waves (the SIMDs' second waves) that do all staging: weight steps through a ring of three
 //     LDS buffers, stored two steps ahead of their use from registers fetched two steps before that, and
 //     the next chunk's patch (BatchNorm+ReLU prologue and halo zero-fill applied on the way), stored one
 //     step ahead.  Their waits (vmcnt, LDS-store queueing) no longer sit in any MFMA stream.
 // One s_barrier per step joins the two roles.  The weight ring keeps running across work units (the epilogue
-// tile overlays only [P0 | P1 | W2], dead at that point).  LDS: [W0 | W1 | P0 | P1 | W2], 80-byte pitch.
-// M16: the consumers multiply with v_mfma_f32_16x16x32_bf16 instead of 32x32x16 (the same LDS bytes and matrix cycles per
-// FLOP; on random data the chip holds a ~12 % higher clock on the 16x16 shape: tools/ubench/mfma_tiles.hip 1.79 vs
-// 1.60 PFLOP/s at this wave tile).  A 16x16x32 operand is 16 rows x one whole 64-byte chunk, so the LDS image changes:
-// patch pixels at a 96-byte pitch (conflict-free for 16 consecutive pixels at any tap shift), weight rows unpadded with
-// the 16-byte piece index XOR-ed by [0,3,2,1][(row >> 2) & 3] (conflict-free, rows never shift).
+// tile overlays only [P0 | P1 | W2], dead at that point).  LDS: [W0 | W1 | P0 | P1 | W2].
+// The consumers multiply with v_mfma_f32_16x16x32_bf16 (the same LDS bytes and matrix cycles per FLOP as 32x32x16; on random
+// data the chip holds a ~12 % higher clock on the 16x16 shape: tools/ubench/mfma_tiles.hip 1.79 vs 1.60 PFLOP/s at this wave
+// tile; on the whole step 0.5 % faster, and its producers' stores lose 6 % of their LDS cycles to bank conflicts instead of
+// 22 %).  A 16x16x32 operand is 16 rows x one whole 64-byte chunk, so the LDS image is: patch pixels at a 96-byte pitch
+// (conflict-free for 16 consecutive pixels at any tap shift), weight rows unpadded with the 16-byte piece index XOR-ed by
+// [0,3,2,1][(row >> 2) & 3] (conflict-free, rows never shift).
 // Diagnostic build only (-DSEGK_PIPE_STAMPS, tools/stamp_build.sh): per-wave cycle sums of the loop's phases, written
 // over the statistics buffer by lane 0 of every wave; the shipped library contains no stamp.
 #ifdef SEGK_PIPE_STAMPS
@@ -465,23 +465,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_igemm_kernel(const ConvA
 #else
 #define PIPE_STAMP(i) do {} while (0)
 #define PIPE_STAMP_OUT() do {} while (0)
-#endif
-#ifndef PIPE_ILV
-#define PIPE_ILV 1     // 16x16x32 consumers read the next sub-step's fragments between the MFMAs (0: in a group ahead of them, rounds 2-3)
-#endif
-#ifndef PIPE_RAWBAR
-#define PIPE_RAWBAR 0  // 1: the 16x16x32 consumers' step barriers as a raw s_barrier (no lgkmcnt(0) drain): 12.31 vs 12.29-12.30 ms, no gain
-#endif
-__device__ __forceinline__ void step_barrier() {
-#if PIPE_RAWBAR
-  __builtin_amdgcn_s_barrier();
-#else
-  __syncthreads();
-#endif
-}
-#ifndef PIPE_ABL
-#define PIPE_ABL 0     // diagnostic ablations (results are wrong): 1 producers skip LDS stores, 2 skip global loads, 4 consumers re-use fragments,
-                       // 8 DMA form: no output stores, 16 DMA form: no statistics reduction, 32 DMA form: no epilogue at all
 #endif
 
 // DMA (round 4; 16x16x32 consumers, no prologue): the producers move NOTHING through registers.  Weights and patch arrive by
@@ -517,18 +500,18 @@ __device__ __forceinline__ float pipe_row16_sum(float v) {
   return v;
 }
 
-template <int TWL, bool PRO, int BN, bool M16, bool DMA = false>
+template <int TWL, bool PRO, int BN, bool DMA = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) {
   using T = bf16_t;
   using E = ET<T>;
-  static_assert(!DMA || (M16 && !PRO), "the LDS-DMA form serves the 16x16x32 consumers without a prologue");
-  constexpr int PPIX = DMA ? 64 : (M16 ? 96 : PIXB);   // LDS pitch of a patch pixel's chunk
-  constexpr int WPIX = M16 ? 64 : PIXB;            // LDS pitch of a weight row
+  static_assert(!DMA || !PRO, "the LDS-DMA form serves the layers without a prologue");
+  constexpr int PPIX = DMA ? 64 : 96;              // LDS pitch of a patch pixel's chunk
+  constexpr int WPIX = 64;                         // LDS pitch of a weight row
   // workgroup tile 256 px x 128 ch (consumers 2 x 2) or, for 64-channel layers, 512 px x 64 ch (consumers 4 x 1):
   // the same bytes per step and the same 128 x 64 consumer tile either way
   static_assert(BN == 128 || BN == 64, "channel tile is 128 or 64");
   constexpr int BM = 32768 / BN, NTHR = 512, NPT = 256;       // NPT: producer threads
-  constexpr int WN = BN / 64, WM = 4 / WN, MF = 4, NF = 2;    // consumer waves: WM x WN, 128 px x 64 ch each
+  constexpr int WN = BN / 64, WM = 4 / WN;                   // consumer waves: WM x WN, 128 px x 64 ch each
   constexpr int TW = 1 << TWL, TH = BM >> TWL, PW = TW + 2, PH = TH + 2;
   constexpr int RPX = (PW + 7) & ~7;               // DMA image: pixel slots per patch row (whole 8-pixel blocks)
   constexpr int ROWP = DMA ? RPX * 64 : ((PW * PPIX + 255) & ~255);
@@ -537,7 +520,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
   constexpr int NP = PH * PW * 4, NPL = (NP + NPT - 1) / NPT;
   constexpr int NWL = 3 * BN * 4 / NPT;            // 16-byte weight pieces per producer thread and step
   constexpr int POFF = 2 * WB, W2OFF = POFF + 2 * PB, MAINB = W2OFF + WB;
-  constexpr int NSUB = 6;                          // 3 taps x two k-halves of the 64-byte chunk
   static_assert(3 * BN * 4 % NPT == 0, "weight pieces divide evenly");
   auto wring = [](int r) { return r < 2 ? r * WB : W2OFF; };
 
@@ -773,7 +755,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
       const int q = ptid + i * NPT;
       const int t = q / (BN * 4), r = q - t * (BN * 4);
       wsrc[i] = t * a.Ntot * 64 + r * 16;              // byte offset from the step's weight base
-      const int wrow = r >> 2, wpc = M16 ? ((r & 3) ^ ((0x1230 >> (4 * ((wrow >> 2) & 3))) & 3)) : (r & 3);   // [0,3,2,1]
+      const int wrow = r >> 2, wpc = (r & 3) ^ ((0x1230 >> (4 * ((wrow >> 2) & 3))) & 3);   // [0,3,2,1]
       wlds[i] = t * (BN * WPIX) + wrow * WPIX + wpc * 16;
     }
 
@@ -803,7 +785,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
       else { base = (const T*)a.srcB; C = a.CB; coff = (kc - nchA) * E::CH; }
       base += coff + pc * E::VEC;
       pl_aoff = (kc < nchA) ? coff + pc * E::VEC : -1;      // act_out mirrors srcA only
-      if (PIPE_ABL & 2) return;
 #pragma unroll
       for (int i = 0; i < NPL; ++i) preg[i] = *(const u32x4*)(base + (size_t)(unsigned)(plin[i] * C));
       if (PRO) {
@@ -815,7 +796,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
       }
     };
     auto patch_store = [&](int pboff) {
-      if (PIPE_ABL & 1) return;
 #pragma unroll
       for (int i = 0; i < NPL; ++i) {
         u32x4 v = preg[i];
@@ -849,13 +829,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
       if (cu_ok) {
         const char* wb = (const char*)a.w + ((size_t)(cu_step * 3) * a.Ntot + cu_n0) * 64;
 #pragma unroll
-        for (int i = 0; i < NWL; ++i)
-          if (!(PIPE_ABL & 2)) R[i] = *(const u32x4*)(wb + wsrc[i]);
+        for (int i = 0; i < NWL; ++i) R[i] = *(const u32x4*)(wb + wsrc[i]);
         if (++cu_step == nsteps) { cu_step = 0; cu_n0 = nn0; cu_ok = has_next; }
       }
     };
     auto store_w = [&](int ring, const u32x4 (&R)[NWL]) {
-      if (PIPE_ABL & 1) return;
 #pragma unroll
       for (int i = 0; i < NWL; ++i) *(u32x4*)(smem + wring(ring) + wlds[i]) = R[i];
     };
@@ -927,133 +905,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
   }
 
   // ============================================= CONSUMERS =============================================
-  if constexpr (!M16) {
-  const int wm = wave / WN, wn = wave - wm * WN;
-  const int lr = lane & 31, lh = lane >> 5;
-  int laneA[MF], laneB[NF];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf) {
-    const int m = (wm * MF + mf) * 32 + lr;
-    laneA[mf] = POFF + (m >> TWL) * ROWP + (m & (TW - 1)) * PIXB + lh * 16;
-  }
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) laneB[nf] = ((wn * NF + nf) * 32 + lr) * PIXB + lh * 16;
-
-  f32x16 acc[MF][NF];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mf][nf][r] = 0.f;
-  };
-  uint4 fa[2][MF], fb[2][NF];   // fragment double buffer; [0] is primed before a step begins
-  auto rd = [&](int prow, int wb, int i, uint4 (&A)[MF], uint4 (&Bf)[NF]) {
-    const int t = i >> 1, kk = i & 1;
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) A[mf] = *(const uint4*)(smem + prow + laneA[mf] + t * PIXB + kk * 32);
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf) Bf[nf] = *(const uint4*)(smem + wb + laneB[nf] + t * (BN * PIXB) + kk * 32);
-  };
-  // one step (kernel row TG of chunk kc): 6 sub-steps of 8 MFMAs, fragments read one sub-step (256 matrix
-  // cycles) ahead; the last sub-step reads the next step's first fragments
-  auto step = [&](auto TGc, int kc) {
-    constexpr int TG = decltype(TGc)::value;
-    const int prow = (kc & 1) * PB + TG * ROWP;
-    const int prow_next = (TG < 2) ? prow + ROWP : ((kc + 1) & 1) * PB;
-    constexpr int wb = TG < 2 ? TG * WB : W2OFF, wb_next = (TG + 1) % 3 < 2 ? ((TG + 1) % 3) * WB : W2OFF;
-#pragma unroll
-    for (int i = 0; i < NSUB; ++i) {
-      if (i + 1 < NSUB) rd(prow, wb, i + 1, fa[(i + 1) & 1], fb[(i + 1) & 1]);
-      else rd(prow_next, wb_next, 0, fa[0], fb[0]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) Mma<T>::run(fa[i & 1][mf], fb[i & 1][nf], acc[mf][nf]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  auto stage_tile = [&](bool full) {   // bias, BN partial sums from the fp32 accumulators, tile -> LDS
-    if (a.bias) {
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf) {
-        const float bv = a.bias[un0 + (wn * NF + nf) * 32 + lr];
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[mf][nf][r] += bv;
-      }
-    }
-    if (!full) {   // rare: pixels past the image edge must not enter the statistics (they are never stored)
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = (wm * MF + mf) * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
-          const bool in = (uy0 + (m >> TWL) < H) && (ux0 + (m & (TW - 1)) < W);
-#pragma unroll
-          for (int nf = 0; nf < NF; ++nf) acc[mf][nf][r] = in ? acc[mf][nf][r] : 0.f;
-        }
-    }
-    const bool do_stats = (a.stats != nullptr);
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf) {
-      float s1 = 0.f, s2 = 0.f;
-      const int n = (wn * NF + nf) * 32 + lr;
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf) {
-        const int mb = (wm * MF + mf) * 32 + 4 * lh;
-        char* const obase = ot + mb * OP + n * E::ES;
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = acc[mf][nf][r];
-        stage_frag<T>(v, obase, OP, s1, s2);
-      }
-      if (do_stats) {
-        s1 += __shfl_xor(s1, 32);
-        s2 += __shfl_xor(s2, 32);
-        if (lh == 0) {
-          red[(wm * BN + n) * 2 + 0] = s1;
-          red[(wm * BN + n) * 2 + 1] = s2;
-        }
-      }
-    }
-  };
-
-  zero_acc();
-  __syncthreads();                                     // B0
-  rd(0, 0, 0, fa[0], fb[0]);
-  for (;;) {
-    const int un = u + GW;
-    const bool has_next = un < u_end;
-    int nmt = 0, nb = 0, ny0 = 0, nx0 = 0, nn0 = 0;
-    if (has_next) decode(un, nmt, nb, ny0, nx0, nn0);
-    for (int kc = 0; kc < nchunks; ++kc) {
-      step(std::integral_constant<int, 0>{}, kc);
-      __syncthreads();
-      step(std::integral_constant<int, 1>{}, kc);
-      __syncthreads();
-      step(std::integral_constant<int, 2>{}, kc);
-      __syncthreads();
-    }
-    const bool full = (uy0 + TH <= H) && (ux0 + TW <= W);
-    stage_tile(full);
-    __syncthreads();                                   // E1
-    if (full) store_tile(std::true_type{});
-    else store_tile(std::false_type{});
-    if (!has_next) break;
-    zero_acc();
-    __syncthreads();                                   // E2
-    u = un; umt = nmt; ub = nb; uy0 = ny0; ux0 = nx0; un0 = nn0;
-    __syncthreads();                                   // E3: the next unit's chunk 0 is in P0
-    rd(0, 0, 0, fa[0], fb[0]);
-  }
-  } else {
-  // ---- 16x16x32 form: the 128 x 64 wave tile is 8 x 4 blocks of 16 x 16; per tap (k = 32 = one whole chunk) 8 patch
-  // and 4 weight fragments feed 32 MFMAs.  Sub-step = one tap x one half of the pixel blocks (4 A + 4 B -> 16 MFMAs, 256
-  // matrix cycles, as before); fragments are read one sub-step ahead, the weight fragments of a tap once per two.
+  // the 128 x 64 wave tile is 8 x 4 blocks of 16 x 16; per tap (k = 32 = one whole chunk) 8 patch and 4 weight fragments
+  // feed 32 MFMAs.  Sub-step = one tap x one half of the pixel blocks (4 A + 4 B -> 16 MFMAs, 256 matrix cycles); fragments
+  // are read one sub-step ahead, the weight fragments of a tap once per two.
   const int wm = wave / WN, wn = wave - wm * WN;
   const int lc = lane & 15, lq = lane >> 4;
   constexpr int MB = 8, NB = 4;
@@ -1092,20 +946,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
   };
   uint4 fa[2][4], fb[3][NB];    // patch halves ping-pong per sub-step; weight fragments per tap ([0] primed before a step)
   auto rdA = [&](int prow, int t, int hh, uint4 (&A)[4]) {
-    if (PIPE_ABL & 4) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(A[j].x), "+v"(A[j].y), "+v"(A[j].z), "+v"(A[j].w));
-      return;
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) A[j] = *(const uint4*)pa(prow, 4 * hh + j, t);
   };
   auto rdB = [&](int wb, int t, uint4 (&Bf)[NB]) {
-    if (PIPE_ABL & 4) {
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) asm volatile("" : "+v"(Bf[nb].x), "+v"(Bf[nb].y), "+v"(Bf[nb].z), "+v"(Bf[nb].w));
-      return;
-    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) Bf[nb] = *(const uint4*)(smem + wb + laneB[nb] + t * (BN * WPIX));
   };
@@ -1122,51 +966,36 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       const int t = i >> 1, hh = i & 1;
-#if PIPE_ILV
-      // Round 4: the next sub-step's fragments are read BETWEEN this sub-step's MFMAs, one ds_read_b128 behind every
-      // second MFMA (weight fragments of a new tap first: the next sub-step's first MFMAs need all four).  A consumer is
-      // alone on its SIMD's matrix pipe: while it issues a group of 4-8 reads back to back the pipe runs dry (tools/ubench/
-      // pipe_roles.hip: 1968 -> 1652 cycles per 1536-cycle step in the bare loop, 2006 -> 1806 beside staging partners).
-      {
-        const int ni = (i + 1) % 6, nt_ = ni >> 1, nh = ni & 1;
-        const int rp = (i + 1 < 6) ? prow : prow_next;
-        const int rw = (i + 1 < 6) ? wb : wb_next;
-        const bool needB = (nh == 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-            acc[4 * hh + j][nb] = mma16(fa[i & 1][j], fb[t][nb], acc[4 * hh + j][nb]);
-            const int m = j * NB + nb;
-            if ((m & 1) && !(PIPE_ABL & 4)) {
-              const int r = m >> 1;   // 0 .. 7
-              if (needB) {
-                if (r < 4) fb[nt_][r] = *(const uint4*)(smem + rw + laneB[r] + nt_ * (BN * WPIX));
-                else fa[(i + 1) & 1][r - 4] = *(const uint4*)pa(rp, 4 * nh + r - 4, nt_);
-              } else if (r < 4) {
-                fa[(i + 1) & 1][r] = *(const uint4*)pa(rp, 4 * nh + r, nt_);
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        continue;
-      }
-#endif
-      if (i + 1 < 6) {
-        rdA(prow, (i + 1) >> 1, (i + 1) & 1, fa[(i + 1) & 1]);
-        if (((i + 1) & 1) == 0) rdB(wb, (i + 1) >> 1, fb[(i + 1) >> 1]);
-      } else {
-        rdA(prow_next, 0, 0, fa[0]);
-        rdB(wb_next, 0, fb[0]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
+      // the next sub-step's fragments are read BETWEEN this sub-step's MFMAs, one ds_read_b128 behind every second MFMA
+      // (weight fragments of a new tap first: the next sub-step's first MFMAs need all four).  A consumer is alone on its
+      // SIMD's matrix pipe: while it issues a group of 4-8 reads back to back the pipe runs dry (tools/ubench/pipe_roles.hip:
+      // 1968 -> 1652 cycles per 1536-cycle step in the bare loop, 2006 -> 1806 beside staging partners).
+      const int ni = (i + 1) % 6, nt_ = ni >> 1, nh = ni & 1;
+      const int rp = (i + 1 < 6) ? prow : prow_next;
+      const int rw = (i + 1 < 6) ? wb : wb_next;
+      const bool needB = (nh == 0);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
+        for (int nb = 0; nb < NB; ++nb) {
           acc[4 * hh + j][nb] = mma16(fa[i & 1][j], fb[t][nb], acc[4 * hh + j][nb]);
-      __builtin_amdgcn_sched_barrier(0);
+          const int m = j * NB + nb;
+          if (m & 1) {
+            const int r = m >> 1;   // 0 .. 7
+            if (needB) {
+              if (r < 4) fb[nt_][r] = *(const uint4*)(smem + rw + laneB[r] + nt_ * (BN * WPIX));
+              else fa[(i + 1) & 1][r - 4] = *(const uint4*)pa(rp, 4 * nh + r - 4, nt_);
+            } else if (r < 4) {
+              fa[(i + 1) & 1][r] = *(const uint4*)pa(rp, 4 * nh + r, nt_);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
     }
+    // rdA / rdB are captured only to keep this closure's layout, which steers the register assignment of the instances as
+    // measured; drop these two lines with the next change to the step.
+    (void)rdA;
+    (void)rdB;
   };
   auto stage_tile = [&](auto FULLc) {   // bias, BN partial sums from the fp32 accumulators, tile -> LDS
     constexpr bool full = decltype(FULLc)::value;      // compile time: a run-time test here is a branch per value
@@ -1260,11 +1089,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
           s2[k][e] = fmaf(v[e], v[e], s2[k][e]);
         }
         const uint4 o = make_uint4(cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]), cvt_pk_bf16(v[4], v[5]), cvt_pk_bf16(v[6], v[7]));
-        if (in && !(PIPE_ABL & 8)) *(uint4*)(dpx[k] + (size_t)(dty * W + dtx) * pstr[k]) = o;
-        if (PIPE_ABL & 8) asm volatile("" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
+        if (in) *(uint4*)(dpx[k] + (size_t)(dty * W + dtx) * pstr[k]) = o;
       }
     }
-    if (do_stats && !(PIPE_ABL & 16)) {
+    if (do_stats) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
 #pragma unroll
@@ -1276,7 +1104,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
         }
       }
     }
-    if (do_stats && !(PIPE_ABL & 16)) {
+    if (do_stats) {
       // ONE statistics row per unit: the consumer waves of a channel half (same wn, WM pixel parts) meet in LDS -- parts 1 ..
       // WM - 1 publish (data, then a sequence flag), part 0 waits for their flags and adds the WM values per channel in part
       // order (bit-stable) -- 512 contiguous bytes per wave instead of WM rows for segk_bn_finalize to walk (a first form with
@@ -1316,27 +1144,26 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
     const bool has_next = un < u_end;
     int nmt = 0, nb = 0, ny0 = 0, nx0 = 0, nn0 = 0;
     if (has_next) decode(un, nmt, nb, ny0, nx0, nn0);
-    // step barriers: a raw s_barrier.  __syncthreads() adds s_waitcnt lgkmcnt(0), which drains the fragment pre-reads of the next
-    // step that the last sub-step left in flight; every read of the slot this barrier releases has already been consumed by an
-    // MFMA (so it has returned), and the pre-reads target a slot that was published one barrier earlier.
+    // step barriers: __syncthreads() drains the consumers' LDS reads (s_waitcnt lgkmcnt(0)) before the barrier, so the producers
+    // may overwrite the slot it releases by DMA right after it.  A raw s_barrier would be valid only if every read of that slot
+    // had already been consumed by an MFMA.
     for (int kc = 0; kc < nchunks; ++kc) {
       step(std::integral_constant<int, 0>{}, kc);
       PIPE_STAMP(0);
-      step_barrier();
+      __syncthreads();
       PIPE_STAMP(1);
       step(std::integral_constant<int, 1>{}, kc);
       PIPE_STAMP(0);
-      step_barrier();
+      __syncthreads();
       PIPE_STAMP(1);
       step(std::integral_constant<int, 2>{}, kc);
       PIPE_STAMP(0);
-      step_barrier();
+      __syncthreads();
       PIPE_STAMP(1);
     }
     const bool full = (uy0 + TH <= H) && (ux0 + TW <= W);
     if constexpr (DMA) {
-      if (PIPE_ABL & 32) { asm volatile("" ::"v"(acc[0][0][0])); }
-      else if (full) direct_out(std::true_type{});
+      if (full) direct_out(std::true_type{});
       else direct_out(std::false_type{});
       PIPE_STAMP(2);
       if (!has_next) break;
@@ -1364,7 +1191,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(const ConvArgs a) 
     rdB(0, 0, fb[0]);
   }
   PIPE_STAMP_OUT();
-  }
 }
 
 // Weight-stationary variant for the narrow, high-resolution layers (Cin <= 2 chunks, 64 output channels per
@@ -1647,11 +1473,11 @@ int launch_ws(ConvArgs a, hipStream_t st) {
   return 0;
 }
 
-template <int TWL, bool PRO, int BN, bool M16, bool DMA = false>
+template <int TWL, bool PRO, int BN, bool DMA>
 int launch_pipe_m(ConvArgs a, hipStream_t st) {
   constexpr int BM = 32768 / BN, NTHR = 512;
   constexpr int TW = 1 << TWL, TH = BM >> TWL, PW = TW + 2, PH = TH + 2;
-  constexpr int PPIX = DMA ? 64 : (M16 ? 96 : PIXB), WPIX = M16 ? 64 : PIXB;
+  constexpr int PPIX = DMA ? 64 : 96, WPIX = 64;
   constexpr int ROWP = DMA ? ((PW + 7) & ~7) * 64 : ((PW * PPIX + 255) & ~255);
   constexpr size_t ring = 3 * (size_t)(3 * BN * WPIX) + 2 * (size_t)PH * ROWP;
   // + a trash KiB and the statistics exchange (4 waves x 64 channels x 2 floats, 4 flags) / the producers' trash slots
@@ -1665,7 +1491,7 @@ int launch_pipe_m(ConvArgs a, hipStream_t st) {
   int gw = num_cus() / 8;                                  // one 8-wave workgroup per CU
   if (gw > per_xcd) gw = per_xcd;
   a.persistent = 1;
-  auto kern = conv3x3_pipe_kernel<TWL, PRO, BN, M16, DMA>;
+  auto kern = conv3x3_pipe_kernel<TWL, PRO, BN, DMA>;
   static bool attr_set[SEGK_MAX_DEVICES] = {};
   const int dev = segk_device_index();
   if (!attr_set[dev]) {
@@ -1680,27 +1506,18 @@ int launch_pipe_m(ConvArgs a, hipStream_t st) {
 
 template <int TWL, bool PRO, int BN>
 int launch_pipe(ConvArgs a, hipStream_t st) {
-  // 16x16x32 consumers on every layer of this kernel.  Round 2 kept the 32x32x16 form for Cin = 128 (same-box kbench: 128->128@128
-  // 164 vs 160 us); on the whole step the 16x16 form is 0.5 % faster on all three A/B pairs of round 3 (12.19 / 12.23 / 12.18 vs
-  // 12.22 / 12.28 / 12.28 ms), its producers' stores lose 6 % of their LDS cycles to bank conflicts instead of 22 %, and its
-  // build has no spilled registers (the 32x32 instances carry 45-60 outside the K loop).  The 32x32x16 form stays compiled
-  // for the A/B switch.
-  static const char* const force = getenv("SEGK_PIPE_MFMA");  // A/B switch for tools/kbench.py / tools/ab_bench.sh: "16" or "32"
-  const bool m16 = force ? (force[0] == '1') : true;
   if constexpr (!PRO) {
     // LDS-DMA producers (round 4): layers without a BatchNorm prologue and without a bias (the register epilogue carries none)
     // whose chunk count is even (the patch ring's parity across the unit boundary) and whose sources stay below 4 GiB (32-bit
     // byte offsets per DMA lane)
-    static const char* const nodma = getenv("SEGK_PIPE_DMA");  // "0": the register-staged producers of rounds 1-3 (A/B runs)
     const int nchunks = (a.CA + a.CB) / 32;
     const long long px = (long long)a.B * a.H * a.W;
     int cmax = a.CA > a.CB ? a.CA : a.CB;
     cmax = cmax > a.CO1 ? cmax : a.CO1;
     cmax = cmax > a.CO2 ? cmax : a.CO2;
-    if (m16 && !(nodma && nodma[0] == '0') && nchunks % 2 == 0 && px * cmax * 2 < 4294967296LL && a.bias == nullptr)
-      return launch_pipe_m<TWL, PRO, BN, true, true>(a, st);
+    if (nchunks % 2 == 0 && px * cmax * 2 < 4294967296LL && a.bias == nullptr) return launch_pipe_m<TWL, PRO, BN, true>(a, st);
   }
-  return m16 ? launch_pipe_m<TWL, PRO, BN, true>(a, st) : launch_pipe_m<TWL, PRO, BN, false>(a, st);
+  return launch_pipe_m<TWL, PRO, BN, false>(a, st);
 }
 
 template <typename T, int GEO, int TWL, int WM, int WN, int MF, int NF, int PBUF, bool PRO>
@@ -1786,12 +1603,12 @@ int launch_geo(const ConvArgs& a, hipStream_t st) {
     const int mode = a.shuffle ? 1 : (a.unshuf ? 2 : 0);
     const int nchA = a.CA / 32, nchunks = a.unshuf ? 4 * nchA : nchA;
     const long M = (long)a.B * a.H * a.W;
-    if (!a.srcB && !a.out2 && !a.stats && segk_gemm_pipe_ok(M, nchunks, nchA, a.Ntot, a.CO1, mode)) {
+    if (!a.srcB && !a.out2 && !a.stats && segk_gemm_dma_ok(M, nchunks, nchA, a.Ntot, a.CO1, a.CA, mode)) {
       GemmArgs g{};
       g.A = a.srcA; g.w = (const char*)a.w; g.bias = a.bias; g.out = a.out;
       g.M = M; g.N = a.Ntot; g.nchunks = nchunks; g.nchA = nchA; g.lda = a.CA; g.H = a.H; g.W = a.W; g.Cout = a.CO1;
       g.act = a.act;
-      return segk_gemm_pipe_launch(g, mode, st);
+      return segk_gemm_dma_launch(g, mode, st);
     }
   }
   if constexpr (GEO == 1 && sizeof(T) == 2) {

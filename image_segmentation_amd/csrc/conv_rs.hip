@@ -23,7 +23,6 @@
 // One s_barrier per tile.  PRO (second conv of a DoubleConv block): the BatchNorm+ReLU of the previous layer is applied
 // in LDS by the wave that fetched the piece (after its own vmcnt wait), which also writes the transformed activation
 // to `act_out` for the weight-gradient pass.
-#include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
 #include "segk_internal.h"
@@ -110,10 +109,6 @@ __device__ __forceinline__ uint4 pack8_bf16(const float (&v)[8]) {
   o.w = cvt_pk_bf16(v[6], v[7]);
   return o;
 }
-
-#ifndef RS_ABL
-#define RS_ABL 0      // diagnostic builds: bit 0 = no output stores, bit 1 = no DMA, bit 2 = no MFMA loop (timing only)
-#endif
 
 template <int NCH, bool PRO>
 __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
@@ -238,7 +233,6 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
       unsigned po = poff[i];
       asm volatile("" : "+v"(po));                    // keeps hipcc from hoisting 64-bit (base + offset) sums out of the
                                                       // tile loop (five register pairs, spilled around the MFMA loop)
-      if (RS_ABL & 2) continue;
       if (interior) {
         __builtin_amdgcn_global_load_lds((glb_vp)(cb + po), (lds_vp)dst, 16, 0, 0);
       } else {
@@ -392,8 +386,8 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
       lds_rd128<(c0 >> 3) * 512 + c * RS_CHB>(fr[f % RING], abuf[c0 & 7]);
     };
     constexpr int NFRAG = 2 * NSTEP;
-    if (!(RS_ABL & 4)) static_for<0, RING - 1>(rd);
-    if (!(RS_ABL & 4)) static_for<0, NFRAG>([&](auto FC) {
+    static_for<0, RING - 1>(rd);
+    static_for<0, NFRAG>([&](auto FC) {
       constexpr int f = decltype(FC)::value, ct = f >> 1, pg = f & 1;
       lds_wait<(NFRAG - 1 - f < RING - 2) ? NFRAG - 1 - f : RING - 2>();   // fragment f has arrived (LDS returns in order)
       __builtin_amdgcn_sched_barrier(0);
@@ -428,11 +422,7 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { s1[i] += v[i]; s2[i] = fmaf(v[i], v[i], s2[i]); }
       }
-      if (!(RS_ABL & 1)) {
-        if (in) *(uint4*)(tb + (pg * xstep + h * ystep) + soff) = pack8_bf16(v);
-      } else {
-        asm volatile("" ::"v"(v[0] + v[7]));
-      }
+      if (in) *(uint4*)(tb + (pg * xstep + h * ystep) + soff) = pack8_bf16(v);
     }
   };
   const std::integral_constant<int, 0> H0{};
@@ -558,9 +548,7 @@ int segk_conv_rs_rows(int B, int H, int W, int n_p) {
 
 // bf16, 3x3, one or two 64-byte input chunks, 64-channel output tiles, image wider than 16 pixels
 int segk_conv_use_rs(int cin_p, int n_p, int dtype, int W) {
-  static const bool off = getenv("SEGK_NO_RS") != nullptr;    // A/B switch for tools/kbench.py (read once, used by the
-  // tile-count query and the dispatch alike: the statistics buffer is sized for the kernel that runs)
-  return !off && dtype == SEGK_DT_BF16 && (cin_p == 32 || cin_p == 64) && n_p % 64 == 0 && W > 16;
+  return dtype == SEGK_DT_BF16 && (cin_p == 32 || cin_p == 64) && n_p % 64 == 0 && W > 16;
 }
 
 int segk_conv_rs_launch(const ConvArgs& a, hipStream_t st) {

@@ -12,7 +12,6 @@
 // and the channel rows of each PAIR of 16-channel blocks are interleaved (block 2p row 4q+j = channel 32p + 8q + j, block
 // 2p+1 row 4q+j = channel 32p + 8q + 4 + j), so a lane ends with 8 consecutive channels of one output pixel: one 16-byte
 // store per pair, 64 contiguous bytes per pixel from the four lanes of a column.
-#include <stdlib.h>
 #include "common.hpp"
 #include "segk_internal.h"
 
@@ -141,8 +140,7 @@ int launch(const void* x, const void* wp, const float* bias4, void* out, int B, 
 // the streaming kernel serves this ConvTranspose forward (bf16, Cin 128 or 256, whole 16-pixel blocks per image row, the
 // channel count a multiple of 32 whose 16-channel blocks divide evenly over the eight waves)
 int segk_convt_stream_ok(int B, int H, int W, int Cin, int Cout, int dtype) {
-  static const bool off = getenv("SEGK_NO_CONVT_STREAM") != nullptr;     // A/B switch (tools/kbench.py convt)
-  if (off || dtype != SEGK_DT_BF16 || B <= 0 || H <= 0 || W <= 0 || W % 16 != 0 || Cout <= 0 || Cout % 32 != 0) return 0;
+  if (dtype != SEGK_DT_BF16 || B <= 0 || H <= 0 || W <= 0 || W % 16 != 0 || Cout <= 0 || Cout % 32 != 0) return 0;
   if ((long long)B * H * W * 4 >= 2147483647LL) return 0;
   if (Cin != 128 && Cin != 256) return 0;
   const int NBW = Cin == 128 ? 8 : 4, n16 = 4 * Cout / 16;
@@ -162,8 +160,7 @@ int segk_convt_stream_launch(const void* x, const void* wp, const float* bias4, 
 
 // ... and this ConvTranspose data gradient (bf16, Cin 128, Cout 64: the up4 level -- K = 4 Cout = 256, N = Cin = 128)
 int segk_convt_stream_dgrad_ok(int B, int H, int W, int Cin, int Cout, int dtype) {
-  static const bool off = getenv("SEGK_NO_CONVT_STREAM") != nullptr;
-  if (off || dtype != SEGK_DT_BF16 || B <= 0 || H <= 0 || W <= 0 || W % 16 != 0) return 0;
+  if (dtype != SEGK_DT_BF16 || B <= 0 || H <= 0 || W <= 0 || W % 16 != 0) return 0;
   if ((long long)B * H * W * 4 >= 2147483647LL) return 0;
   return (Cin == 128 && Cout == 64) ? 1 : 0;
 }

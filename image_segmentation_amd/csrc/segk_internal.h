@@ -103,5 +103,5 @@ struct GemmArgs {
   int ksplit;           // > 1: split-K, partial outputs [ksplit][M][N] (split_stride elements apart), bias on split 0
   long split_stride;
 };
-int segk_gemm_pipe_ok(long M, int nchunks, int nchA, int N, int cout_shuffle, int mode);   // mode 0 plain, 1 shuffle, 2 un-shuffle
-int segk_gemm_pipe_launch(const GemmArgs& g, int mode, hipStream_t st);
+int segk_gemm_dma_ok(long M, int nchunks, int nchA, int N, int cout_shuffle, int lda, int mode);   // mode 0 plain, 1 shuffle, 2 un-shuffle
+int segk_gemm_dma_launch(const GemmArgs& g, int mode, hipStream_t st);

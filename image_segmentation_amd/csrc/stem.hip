@@ -11,7 +11,6 @@
 // accumulators with the channel rows of each pair of 16-channel blocks interleaved, so a lane stores 8 consecutive channels
 // of its pixel (16 bytes).  BatchNorm statistics stay in registers for the whole kernel (one partial row per workgroup).
 // The padded NHWC bf16 copy of the input that the weight-gradient pass reads is written on the way (side output).
-#include <stdlib.h>
 #include "common.hpp"
 #include "segk_internal.h"
 
@@ -304,8 +303,6 @@ __global__ __launch_bounds__(STEM_WAVES * 64, 2) void stem_wgrad_kernel(const fl
 
 // workgroups (= slabs [64][32] fp32) of the stem weight-gradient kernel, or 0 where it does not apply
 int segk_stem_wgrad_slabs(int B, int H, int W, int Cin, int Cout, int dtype) {
-  static const bool off = getenv("SEGK_NO_STEM_WGRAD") != nullptr;      // A/B switch
-  if (off) return 0;
   const int rows = segk_stem_rows(B, H, W, Cin, Cout, dtype);           // the same shape conditions as the forward
   if (rows <= 0) return 0;
   const long nblk = (long)B * H * (W / 16);
@@ -328,8 +325,7 @@ int segk_stem_wgrad_launch(const float* x, const void* dz, float* slabs, int B, 
 
 // workgroups (= rows of BatchNorm partials) of the stem kernel for this problem, or 0 where it does not apply
 int segk_stem_rows(int B, int H, int W, int Cin, int Cout, int dtype) {
-  static const bool off = getenv("SEGK_NO_STEM") != nullptr;            // A/B switch
-  if (off || dtype != SEGK_DT_BF16 || B <= 0 || H <= 0 || W <= 0 || W % 16 != 0 || Cin < 1 || Cin > 3 || Cout != 64) return 0;
+  if (dtype != SEGK_DT_BF16 || B <= 0 || H <= 0 || W <= 0 || W % 16 != 0 || Cin < 1 || Cin > 3 || Cout != 64) return 0;
   if ((long long)B * H * W * 64 >= 2147483647LL * 16 || (long long)B * Cin * H * W >= 2147483647LL) return 0;
   const long nblk = (long)B * H * (W / 16);
   long g = (nblk + STEM_WAVES - 1) / STEM_WAVES;

@@ -19,7 +19,6 @@
 //   vit_tokens_to_grid   drop CLS, residual stream -> NHWC feature grid [B,G,G,D] (clipunet.py:48-63)
 // The residual stream stays fp32 in both compute modes (it is 2.4 MB per image batch of 16); GEMM operands are
 // the compute dtype.
-#include <stdlib.h>
 #include "common.hpp"
 #include "../../include/segk.h"
 
@@ -531,10 +530,8 @@ extern "C" int segk_attention(const void* qkv, void* ctx, int B, int T, int head
   SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "attention: bad dtype");
   SEGK_REQUIRE((long)B * heads <= 65535, "attention: B*heads exceeds the grid limit");
   hipStream_t st = (hipStream_t)s;
-  if (dtype == SEGK_DT_BF16 && head_dim == 64 && !getenv("SEGK_ATTENTION_VALU"))   // matrix-core kernel
-    return launch_attention_mfma(qkv, ctx, B, T, heads, ldq, ldo, scale, st);
-  if (dtype == SEGK_DT_BF16)
-    return head_dim == 64 ? launch_attention<bf16_t, 64>(qkv, ctx, B, T, heads, ldq, ldo, scale, st)
+  if (dtype == SEGK_DT_BF16)   // head_dim 64: matrix-core kernel
+    return head_dim == 64 ? launch_attention_mfma(qkv, ctx, B, T, heads, ldq, ldo, scale, st)
                           : launch_attention<bf16_t, 32>(qkv, ctx, B, T, heads, ldq, ldo, scale, st);
   return head_dim == 64 ? launch_attention<float, 64>(qkv, ctx, B, T, heads, ldq, ldo, scale, st)
                         : launch_attention<float, 32>(qkv, ctx, B, T, heads, ldq, ldo, scale, st);

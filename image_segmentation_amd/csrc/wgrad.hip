@@ -15,7 +15,6 @@
 // fp32: exact 32x32x2 MFMA, one ds_read_b32 per operand (lanes = 32 contiguous channels).
 // Each wave owns a 32x32 (n,k) block for ALL taps (9 accumulators); split-K over spatial tiles writes
 // fp32 slabs that segk_wgrad_reduce sums in fixed order (bit-stable, no atomics).
-#include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
 #include "segk_internal.h"
@@ -669,8 +668,7 @@ int launch_t(const WgradArgs& a, int geo, hipStream_t st) {
 
 // 32-channel blocks of the dz operand per workgroup (the host sizes the split-K slabs with it: segk_wgrad_split)
 int segk_wgrad_wc(int CD, int CA, int CB, int geo, int dtype) {
-  static const bool off = getenv("SEGK_WGRAD_NO_WC4") != nullptr;      // A/B switch for tools/kbench.py
-  if ((geo == 0 || geo == 2) && dtype == SEGK_DT_BF16 && !off && CD % 128 == 0 && CA % 64 == 0 && CB % 64 == 0) return 4;
+  if ((geo == 0 || geo == 2) && dtype == SEGK_DT_BF16 && CD % 128 == 0 && CA % 64 == 0 && CB % 64 == 0) return 4;
   return CD % 64 == 0 ? 2 : 1;
 }
 // split-K factor over spatial tiles: enough workgroups to fill the chip (two 4-wave workgroups or one 8-wave workgroup

@@ -82,7 +82,7 @@ def main():
                     # conv3x3_pipe_kernel (waves 0-3 consumers, 4-7 producers)
                     names = ["step work (MFMA | staging)", "step barrier wait", "stage tile | E1 wait", "store tile",
                              "E2..E3 (refill)", "prologue"]
-                    if not args.pro and os.environ.get("SEGK_PIPE_DMA", "1") != "0":     # LDS-DMA form (no prologue)
+                    if not args.pro:                                                  # LDS-DMA form (no prologue)
                         names = ["step work (MFMA | DMA issue)", "step barrier wait", "direct epilogue | vmcnt wait", "-",
                                  "zero + first reads", "prologue"]
                 print(f"      stamps over {t.shape[0]} workgroups: kernel {tot.mean():.0f} cycles per wave (min {tot.min():.0f} max {tot.max():.0f})")
@@ -198,7 +198,7 @@ def vit():
     def packed(n, k):
         w = torch.randn((n, k), device="cuda") / k ** 0.5
         return ops.pack_conv(w.reshape(n, k, 1, 1), k, 0, dt, 0, taps=1)
-    nosplit = os.environ.get("KB_NOSPLIT") is not None      # with SEGK_GEMM_PIPE_MIN_CHUNKS=1000: the generic kernel, no split-K
+    nosplit = os.environ.get("KB_NOSPLIT") is not None      # every GEMM in one piece (segk_linear), no split-K
     for name, K, N, act, S in (("qkv", D, 3 * D, 0, 1), ("out_proj", D, D, 0, 3), ("fc1", D, I, 1, 1), ("fc2", I, D, 0, 3)):
         S = 1 if nosplit else S
         a = torch.randn((Mp, K), device="cuda").to(dt)

@@ -6,7 +6,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/image_segmentation_amd/csrc
 mkdir -p $R/tools/ubench/bin/stamp_obj
 for f in api conv_igemm conv_rs convt_stream stem wgrad bn_pool pack head_loss resize vit gemm probe; do
-  if [ "$f" = conv_rs ]; then X="-DSEGK_RS_STAMPS ${RS_ABL:+-DRS_ABL=$RS_ABL} ${RS_EXTRA}";
+  if [ "$f" = conv_rs ]; then X="-DSEGK_RS_STAMPS ${RS_EXTRA}";
   elif [ "$f" = conv_igemm ]; then X="-DSEGK_PIPE_STAMPS ${PIPE_EXTRA}";
   elif [ "$f" = wgrad ]; then X="-DSEGK_WGRAD_STAMPS ${WGRAD_EXTRA}";
   elif [ "$f" = bn_pool ]; then X="${POOL_EXTRA}"; else X=""; fi
@@ -16,7 +16,7 @@ for f in api conv_igemm conv_rs convt_stream stem wgrad bn_pool pack head_loss r
     cp $C/$f.o $R/tools/ubench/bin/stamp_obj/$f.o
   fi
 done
-OUT=$R/tools/ubench/bin/libsegk_stamp${RS_ABL:+_abl$RS_ABL}${RS_TAG}.so   # RS_TAG also names PIPE_EXTRA builds
+OUT=$R/tools/ubench/bin/libsegk_stamp${RS_TAG}.so   # RS_TAG also names PIPE_EXTRA builds
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $R/tools/ubench/bin/stamp_obj/*.o
 python3 -c "import ctypes,sys; ctypes.CDLL(sys.argv[1])" $OUT   # every symbol resolves (a missing unit would only show on the GPU box)
 echo built $OUT
