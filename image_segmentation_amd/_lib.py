@@ -10,8 +10,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 310          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 311          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
+MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
 
 _vp, _fp, _i, _l, _f, _d = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
@@ -86,6 +87,10 @@ SIGNATURES = {
     "segk_prob_loss_fwd": (_i, [_fp, _vp, _fp, _i, _i, _l, _i, _f, _f, _f, _i, _f, _fp, _fp, _fp, _vp]),
     "segk_prob_loss_bwd": (_i, [_fp, _vp, _fp, _fp, _fp, _i, _i, _l, _i, _f, _f, _i, _f, _fp, _vp]),
     "segk_confusion": (_i, [_fp, _vp, _i, _i, _l, _vp, _vp]),
+    "segk_recon_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_recon_sigmoid_bwd": (_i, [_fp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_mse_fwd": (_i, [_fp, _fp, _fp, _i, _fp, _l, _i, _vp]),
+    "segk_mse_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _l, _i, _vp]),
 }
 
 

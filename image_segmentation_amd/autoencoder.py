@@ -9,7 +9,9 @@ parameters; forward drives the fused HIP kernels through image_segmentation_amd.
   DecoderWithSkips(base_channels)                 :96-114
   DecoderBlockNoSkips(din_up, dout)               :117-146
   DecoderNoSkips(base_channels)                   :149-168
-  ReconstructionAutoencoder(din, dout, base)      :171-200 (3x3 conv + bias head, Sigmoid; fp32 NCHW output)
+  ReconstructionAutoencoder(din, dout, base)      :171-200 (3x3 conv + bias + Sigmoid head fused into one kernel,
+                                                  ops.ReconHeadFn; contiguous fp32 NCHW output; pretrain it with
+                                                  training.trainReconstruction and losses.MSELoss)
   SegmentationEncoder / SegmentationAutoencoder   :203-305 (optional checkpoint loading and encoder freezing)
 """
 import torch
@@ -160,9 +162,8 @@ class ReconstructionAutoencoder(_FusedBase):
         with ops.defer_batch_counters():
             bottleneck, _s3, _s2, _s1 = self.encoder(x)
             decoded = self.decoder(bottleneck)
-            z = ops.Conv3x3Fn.apply(self, decoded, self.decoderOut[0].weight, self.decoderOut[0].bias)
-        # the 3-channel head output leaves the NHWC act layout through stock (differentiable) torch ops
-        return torch.sigmoid(z.float()).contiguous()
+            # 3x3 conv + bias + Sigmoid in one kernel, straight to the contiguous fp32 NCHW tensor the reference returns
+            return ops.ReconHeadFn.apply(self, decoded, self.decoderOut[0].weight, self.decoderOut[0].bias)
 
 
 class SegmentationEncoder(nn.Module):

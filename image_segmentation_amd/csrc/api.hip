@@ -40,6 +40,11 @@ int segk_loss_bwd_impl(const float*, const long long*, const float*, const float
 int segk_prompt_mix_impl(const float*, const float*, const float*, float*, int, long, hipStream_t);
 int segk_confusion_impl(const float*, const long long*, int, int, long, unsigned long long*, hipStream_t);
 
+int segk_recon_head_fwd_impl(const void*, const float*, const float*, float*, int, int, int, int, int, int, int, hipStream_t);
+int segk_recon_sigmoid_bwd_impl(const float*, const float*, void*, int, int, int, int, int, int, hipStream_t);
+int segk_mse_fwd_impl(const float*, const float*, float*, int, float*, long, int, hipStream_t);
+int segk_mse_bwd_impl(const float*, const float*, const float*, float*, float*, long, int, hipStream_t);
+
 int segk_clock_probe_impl(unsigned long long*, int, int, int, hipStream_t);
 int segk_debug_poison_tickets_impl(unsigned long long, hipStream_t);
 
@@ -350,6 +355,23 @@ int segk_loss_bwd(const float* logits, const int64_t* labels, const float* cw, c
                   segk_stream_t s) {
   return segk_loss_bwd_impl(logits, (const long long*)labels, cw, state, gout, N, C, HW, ignore_index, dice_weight,
                             ce_weight, dlogits, 0, 0, 0.f, (hipStream_t)s);
+}
+// autoencoder/autoencoder.py:188-191 (Conv2d(base, dout, 3, padding=1) + Sigmoid)
+int segk_recon_head_fwd(const void* x, const float* w, const float* bias, float* rec, int B, int H, int W, int Cp, int Cin,
+                        int Cout, int dtype, segk_stream_t s) {
+  return segk_recon_head_fwd_impl(x, w, bias, rec, B, H, W, Cp, Cin, Cout, dtype, (hipStream_t)s);
+}
+int segk_recon_sigmoid_bwd(const float* drec, const float* rec, void* dz, int B, int H, int W, int C, int Cp, int dtype,
+                           segk_stream_t s) {
+  return segk_recon_sigmoid_bwd_impl(drec, rec, dz, B, H, W, C, Cp, dtype, (hipStream_t)s);
+}
+// nn.MSELoss() (autoencoder.ipynb cell 0), called at utils/training.py:141,234
+int segk_mse_fwd(const float* a, const float* b, float* part, int part_floats, float* out, long n, int mean, segk_stream_t s) {
+  return segk_mse_fwd_impl(a, b, part, part_floats, out, n, mean, (hipStream_t)s);
+}
+int segk_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, long n, int mean,
+                 segk_stream_t s) {
+  return segk_mse_bwd_impl(a, b, grad_out, da, db, n, mean, (hipStream_t)s);
 }
 int segk_confusion(const float* logits, const int64_t* labels, int N, int C, long HW, uint64_t* M, segk_stream_t s) {
   return segk_confusion_impl(logits, (const long long*)labels, N, C, HW, (unsigned long long*)M, (hipStream_t)s);

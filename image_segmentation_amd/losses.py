@@ -1,6 +1,7 @@
 """Per-pixel segmentation losses on the fused HIP loss kernel -- drop-in for the reference's
 utils/weighted_loss.py:6-98 (WeightedMemoryEfficientDiceLoss), :102-166 (WeightedDiceCELoss), :170-265
-(WeightedMemoryEfficientDiceLossPrompt), :268-343 (WeightedDiceNLLLoss) and for torch.nn.CrossEntropyLoss as the reference constructs it (unet/unet.ipynb cell 0; weighted_loss.py:132-138).
+(WeightedMemoryEfficientDiceLossPrompt), :268-343 (WeightedDiceNLLLoss) and for torch.nn.CrossEntropyLoss as the reference constructs it (unet/unet.ipynb cell 0; weighted_loss.py:132-138);
+MSELoss replaces torch.nn.MSELoss of the autoencoder pretraining (autoencoder/autoencoder.ipynb cell 0) on its own kernels.
 Constructor signatures, accepted target shapes and error behaviour follow the reference."""
 from typing import Callable, Optional
 
@@ -33,6 +34,25 @@ class CrossEntropyLoss(nn.Module):
     def forward(self, outputs, targets):
         ign = self.ignore_index if self.ignore_index is not None and self.ignore_index >= 0 else None
         return ops.SegLossFn.apply(outputs, targets, self.weight, ign, 0.0, 0.0, 1.0)
+
+
+class MSELoss(nn.Module):
+    """nn.MSELoss(size_average=None, reduce=None, reduction='mean') for two same-shaped tensors (the reconstruction and its
+    input, utils/training.py:141,234).  'mean' and 'sum' run on the deterministic HIP reduction; 'none' and the legacy
+    size_average / reduce flags are not implemented."""
+
+    def __init__(self, size_average=None, reduce=None, reduction: str = "mean"):
+        super().__init__()
+        if size_average is not None or reduce is not None:
+            raise NotImplementedError("the deprecated size_average / reduce arguments are not supported: use reduction=")
+        if reduction == "none":
+            raise NotImplementedError("reduction='none' is not implemented (the reference uses 'mean')")
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        self.reduction = reduction
+
+    def forward(self, input, target):
+        return ops.MSELossFn.apply(input, target, self.reduction == "mean")
 
 
 class WeightedMemoryEfficientDiceLoss(nn.Module):

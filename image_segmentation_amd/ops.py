@@ -1237,56 +1237,102 @@ class Conv1x1Fn(torch.autograd.Function):
         return None, dx, dw, db
 
 
-class Conv3x3Fn(torch.autograd.Function):
-    """Plain nn.Conv2d(Cin, Cout, kernel_size=3, padding=1) with bias and no BatchNorm behind it -- the
-    reconstruction head of reference autoencoder/autoencoder.py:188-191 (the Sigmoid stays a stock torch op on the
-    small fp32 output).  Returns an act tensor."""
+class ReconHeadFn(torch.autograd.Function):
+    """The reconstruction head of reference autoencoder/autoencoder.py:188-191: nn.Conv2d(Cin, Cout, 3, padding=1) with
+    bias, then nn.Sigmoid, from an act tensor to the fp32 NCHW tensor the reference model returns.  Forward is one kernel
+    (segk_recon_head_fwd, the sigmoid on the fp32 accumulator); backward takes any fp32 gradient of the output (this
+    package's MSELoss or a stock one), turns it into the act-layout gradient of the pre-activation (segk_recon_sigmoid_bwd)
+    and runs the 3x3 data-gradient, weight-gradient and channel-sum kernels on it."""
 
     @staticmethod
     def forward(ctx, mod, x, w, b):
         dtype = mod.compute_dtype or _compute_dtype
-        _require_cuda(x, "Conv2d 3x3")
+        _require_cuda(x, "reconstruction head")
         dev = x.device
         B, Cin, H, W = x.shape
         Cout = w.shape[0]
-        Cinp, Coutp = pad32(Cin), pad32(Cout)
-        x_t, px, _ = _raw(x, dtype)
-        wp = mod.cache.get(("c3f", dtype), w, lambda: pack_conv(w, Cin, 0, dtype, 0))
-
-        def biasp():
-            t = torch.zeros((Coutp,), dtype=torch.float32, device=dev)
-            t[:Cout] = _param_f32(b)
-            return t
-        bp = None if b is None else mod.cache.get(("c3b", dtype), b, biasp)
-        out = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
-        P, e = B * H * W, _es(dtype)
-        with _span("conv3x3_igemm", 2.0 * P * 9 * Cin * Cout, P * (Cin + Cout) * e + 9.0 * Cin * Cout * e):
-            _lib.call("segk_conv3x3", px, 0, wp.data_ptr(), _p(bp), 0, 0, out.data_ptr(), 0, 0, B, H, W, Cinp, 0, Coutp, 0,
-                      _DT[dtype], _stream())
+        x_t, px, Cp = _raw(x, dtype)
+        rec = torch.empty((B, Cout, H, W), dtype=torch.float32, device=dev)
+        P = B * H * W
+        with _span("recon_head_fwd", 2.0 * P * 9 * Cin * Cout, P * (Cin * _es(dtype) + 4 * Cout)):
+            _lib.call("segk_recon_head_fwd", px, _param_f32(w).data_ptr(), 0 if b is None else _param_f32(b).data_ptr(),
+                      rec.data_ptr(), B, H, W, Cp, Cin, Cout, _DT[dtype], _stream())
         ctx.mod, ctx.dtype, ctx.dims = mod, dtype, (B, H, W, Cin, Cout)
         ctx.has_bias = b is not None
-        ctx.save_for_backward(x_t, w)
-        return act_view(out, Cout)
+        ctx.save_for_backward(x_t, w, rec)
+        return rec
 
     @staticmethod
-    def backward(ctx, dout):
-        x_t, w = ctx.saved_tensors
+    def backward(ctx, drec):
+        x_t, w, rec = ctx.saved_tensors
         mod, dtype = ctx.mod, ctx.dtype
         B, H, W, Cin, Cout = ctx.dims
         dev = x_t.device
         Cinp, Coutp = pad32(Cin), pad32(Cout)
-        d_t, pd, _ = _raw(dout, dtype)
+        g = drec.detach()
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        dzb = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
+        P = B * H * W
+        with _span("recon_sigmoid_bwd", 0.0, P * (8.0 * Cout + Coutp * _es(dtype))):
+            _lib.call("segk_recon_sigmoid_bwd", g.data_ptr(), rec.data_ptr(), dzb.data_ptr(), B, H, W, Cout, Coutp,
+                      _DT[dtype], _stream())
+        pd = dzb.data_ptr()
         px = act_info(x_t, dtype)[0]
-        dx = None
+        dx = dw = db = None
         if ctx.needs_input_grad[1]:
             wd = mod.cache.get(("c3d", dtype), w, lambda: pack_conv(w, Cin, 0, dtype, 1))
             dxb = torch.empty((B, H, W, Cinp), dtype=dtype, device=dev)
-            conv3x3(d_t, pd, Coutp, 0, 0, wd, dxb.data_ptr(), Cinp, 0, 0, B, H, W, dtype, alg=(Cout, Cin))
+            conv3x3(dzb, pd, Coutp, 0, 0, wd, dxb.data_ptr(), Cinp, 0, 0, B, H, W, dtype, alg=(Cout, Cin))
             dx = act_view(dxb, Cin)
-        slabs, S = wgrad(pd, Coutp, px, Cinp, 0, 0, B, H, W, 0, dtype, dev, alg=(Cout, Cin))
-        dw = wgrad_to_param(slabs, S, w.shape, Cout, Cin, 0, 9, dev, param=w)
-        db = channel_sum(pd, B * H * W, Cout, dtype, dev) if ctx.has_bias else None
+        if ctx.needs_input_grad[2]:
+            slabs, S = wgrad(pd, Coutp, px, Cinp, 0, 0, B, H, W, 0, dtype, dev, alg=(Cout, Cin))
+            dw = wgrad_to_param(slabs, S, w.shape, Cout, Cin, 0, 9, dev, param=w)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = channel_sum(pd, P, Cout, dtype, dev)
         return None, dx, dw, db
+
+
+def _mse_operand(t, what):
+    _require_cuda(t, what)
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()       # dtype/layout normalisation of a foreign tensor (edge only)
+    return t
+
+
+class MSELossFn(torch.autograd.Function):
+    """nn.MSELoss(reduction='mean' | 'sum') -- as reference autoencoder/autoencoder.ipynb constructs it and
+    utils/training.py:141,234 call it.  Deterministic: fixed per-block fp64 partials and a fixed-order finalize."""
+
+    @staticmethod
+    def forward(ctx, input, target, mean):
+        if input.shape != target.shape:
+            raise ValueError(f"MSELoss: input {tuple(input.shape)} and target {tuple(target.shape)} differ in shape")
+        a, b = _mse_operand(input, "MSELoss input"), _mse_operand(target, "MSELoss target")
+        n = a.numel()
+        if n == 0:
+            raise ValueError("MSELoss of empty tensors")
+        dev = a.device
+        part, out = _f32(_lib.MSE_PART_FLOATS, dev), _f32(1, dev)
+        with _span("mse_fwd", 0.0, 8.0 * n):
+            _lib.call("segk_mse_fwd", a.data_ptr(), b.data_ptr(), part.data_ptr(), part.numel(), out.data_ptr(), n, int(mean),
+                      _stream())
+        ctx.mean = int(mean)
+        ctx.save_for_backward(a, b)
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b = ctx.saved_tensors
+        go = gout.detach().float().reshape(1).contiguous()
+        da = torch.empty_like(a)
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        n = a.numel()
+        with _span("mse_bwd", 0.0, (12.0 if db is None else 16.0) * n):
+            _lib.call("segk_mse_bwd", a.data_ptr(), b.data_ptr(), go.data_ptr(), da.data_ptr(), _p(db), n, ctx.mean,
+                      _stream())
+        return da, db, None
 
 
 class BilinearFn(torch.autograd.Function):

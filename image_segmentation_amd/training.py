@@ -1,6 +1,6 @@
 """Training / evaluation driver -- drop-in for the reference's utils/training.py (train_loop :18-64,
-eval_loop :67-121, start :453-618): same signatures, same accumulation/step/zero_grad order, same returned
-averages, same checkpoint dictionary keys.  Pure host logic: the model, loss and metrics it drives are the
+eval_loop :67-121, trainReconstruction :123-151, evalReconstruction :202-239, start :453-618): same signatures, same
+accumulation/step/zero_grad order, same returned averages, same checkpoint dictionary keys.  Pure host logic: the model, loss and metrics it drives are the
 HIP-backed modules of this package (or anything honouring the same nn.Module protocol).
 
 Differences from the reference, all deliberate:
@@ -8,7 +8,10 @@ Differences from the reference, all deliberate:
   * eval_loop prints per-class IoU for agg.get_num_classes() classes instead of a hard-coded 4
     (training.py:81 raises IndexError with a 3-class aggregator);
   * an optional `grad_sync` hook (parallel.GradSync) all-reduces gradients over RCCL right before
-    optimizer.step() -- absent in the single-process reference.
+    optimizer.step() -- absent in the single-process reference;
+  * trainReconstruction / evalReconstruction take the device as an argument (default: the model's parameter device; the
+    reference reads a module-global) and keep the per-batch / per-image losses on the device, copying them to the host
+    once at the end instead of one `.item()` sync per batch or image.
 """
 import os
 
@@ -171,6 +174,76 @@ def eval_loop(dataloader, model, loss_fn, device, target_size, agg, grad_sync=No
     _say("-" * 25)
 
     return avg_loss, mean_dice, mean_iou
+
+
+def _model_device(model):
+    p = next(iter(model.parameters()), None)
+    return p.device if p is not None else torch.device("cpu")
+
+
+def _host_f64(losses):
+    """Scalar loss tensors (or numbers) -> float64 numpy array in ONE device-to-host copy: the values the reference's
+    per-batch `.item()` list holds."""
+    if not losses:
+        return np.array([], dtype=np.float64)
+    ts = [torch.as_tensor(v).detach().reshape(()).float() for v in losses]
+    return torch.stack([t.to(ts[0].device) for t in ts]).cpu().double().numpy()
+
+
+def trainReconstruction(dataloader, model, loss_fn, optimizer, accumulation_steps, device=None, grad_sync=None):
+    """One epoch of reconstruction pretraining (training.py:123-151): loss_fn(model(X), X) for every (X, _) batch, the
+    scaled loss backpropagated, a step (then zero_grad) every `accumulation_steps` micro-batches and after the last one.
+    Like the reference there is no zero_grad before the first batch.  Returns the mean UNSCALED loss over every
+    micro-batch (train_loop averages the stepping micro-batches only)."""
+    if device is None:
+        device = _model_device(model)
+    losses = []
+    model.train()
+    n = len(dataloader)
+    for batch_idx, (X, _) in enumerate(_bar(dataloader, total=n, desc="Training")):
+        X = X.to(device)
+        pred = model(X)
+        loss = loss_fn(pred, X)
+        losses.append(loss.detach())
+        scaled_loss = loss / accumulation_steps
+        stepping = (batch_idx + 1) % accumulation_steps == 0 or (batch_idx + 1) == n
+        if grad_sync is not None and stepping:
+            grad_sync.arm()
+        scaled_loss.backward()
+        if stepping:
+            if grad_sync is not None:
+                grad_sync.sync()
+            optimizer.step()
+            optimizer.zero_grad()
+    return np.mean(_host_f64(losses))
+
+
+def evalReconstruction(dataloader, model, loss_fn, target_size, interpolation='bilinear', device=None):
+    """training.py:202-239: resize+pad -> model (eval mode, no_grad) -> reverse resize -> per-image loss against the
+    ORIGINAL image (an RGBA image is cut to RGB, :231-232).  Returns (sum of per-image losses / number of batches,
+    mean per-image loss) -- the reference's two figures."""
+    if device is None:
+        device = _model_device(model)
+    model.eval()
+    num_batches = len(dataloader)
+    losses = []
+    with torch.no_grad():
+        for original_X, _ in _bar(dataloader, total=num_batches, desc="Evaluation"):
+            resized_X, meta_list = process_batch_forward(original_X, target_size=target_size, device=device)
+            resized_X = resized_X.to(device)
+            pred = model(resized_X)
+            pred = process_batch_reverse(pred, meta_list, interpolation=interpolation)
+            for p, label in zip(pred, original_X):
+                p = p.to(device).unsqueeze(0)
+                label = label.to(device).unsqueeze(0)
+                if label.shape[1] == 4 and label.ndim == 4:
+                    label = label[:, :3, :, :]
+                losses.append(loss_fn(p, label.squeeze(1)).detach())
+    vals = _host_f64(losses)
+    total_loss = 0.0
+    for v in vals:                      # the reference's running `total_loss += loss.item()`
+        total_loss += float(v)
+    return total_loss / num_batches, np.mean(vals)
 
 
 def train_loop_prompt(dataloader, model, loss_fn, optimizer, accumulation_steps, device, scheduler=None, target_size=None,

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 310
-#define SEGK_ENTRY_COUNT 69
+#define SEGK_ABI_VERSION 311
+#define SEGK_ENTRY_COUNT 73
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -308,6 +308,28 @@ int segk_prob_loss_fwd(const float* probs, const int64_t* labels, const float* c
 int segk_prob_loss_bwd(const float* probs, const int64_t* labels, const float* class_weights, const float* state,
                        const float* grad_out, int N, int C, long HW, int ignore_index, float dice_weight,
                        float nll_weight, int nll_log, float eps, float* dprobs, segk_stream_t s);
+
+/* ---- reconstruction head and MSE loss (autoencoder/autoencoder.py:188-191; nn.MSELoss as autoencoder.ipynb cell 0
+ * constructs it and utils/training.py:141,234 call it) ---------------------------------------------------------------
+ * rec NCHW fp32 [B,Cout,H,W] = sigmoid(bias + conv3x3_pad1(x)) with x an act tensor [B,H,W,Cp] (Cin <= Cp, zero halo) and
+ * the fp32 parameters themselves: w OIHW [Cout][Cin][3][3], bias [Cout] (may be NULL).  fp32: fp32 FMAs on the operands as
+ * given; bf16: the weights are rounded to bf16 and channel pairs are multiplied with fp32 accumulation.  Any Cout >= 1. */
+int segk_recon_head_fwd(const void* x, const float* w, const float* bias, float* rec, int B, int H, int W, int Cp, int Cin,
+                        int Cout, int dtype, segk_stream_t s);
+/* its Sigmoid backward into the act layout: dz [B,H,W,Cp] = drec * (1 - rec) * rec (ATen's sigmoid_backward order) in
+ * dtype, padding channels zeroed; drec, rec NCHW fp32 [B,C,H,W].  dx / dW / db follow from segk_conv3x3 (mode-1 weights),
+ * segk_wgrad (geo 0) and segk_channel_sum on dz. */
+int segk_recon_sigmoid_bwd(const float* drec, const float* rec, void* dz, int B, int H, int W, int C, int Cp, int dtype,
+                           segk_stream_t s);
+/* out[0] = scale * sum((a - b)^2) over n fp32 elements, scale = 1/n (mean = 1) or 1 (mean = 0): fixed per-block fp64
+ * partials in part (8-byte aligned, part_floats >= SEGK_MSE_PART_FLOATS suffices for every n), then a one-block
+ * fixed-order finalize -- the value depends on the data only, never on timing or the device.  Two launches. */
+#define SEGK_MSE_PART_FLOATS 1024
+int segk_mse_fwd(const float* a, const float* b, float* part, int part_floats, float* out, long n, int mean, segk_stream_t s);
+/* da = (norm * (a - b)) * grad_out[0] with norm = (float)(2/n) (mean) or 2 (ATen's mse_loss_backward); grad_out is read on
+ * the device.  db (may be NULL) = -da, the gradient of the target. */
+int segk_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, long n, int mean,
+                 segk_stream_t s);
 
 /* ---- diagnostics (not on the product path) ---------------------------------------------------------
  * The shader clock held under a dense bf16 MFMA load: `blocks` workgroups of four waves (one per SIMD) run `iters` rounds of

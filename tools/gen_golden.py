@@ -356,4 +356,34 @@ def gen_autoencoder():
 
 
 if want("autoencoder"): gen_autoencoder()
+
+
+# ---- reconstruction pretraining: trainReconstruction, reference utils/training.py:123-151 ----------------
+def gen_trainrecon():
+    # utils/training.py imports torchvision (absent here): its protocol is driven by hand, as gen_trainloop does
+    from autoencoder.autoencoder import ReconstructionAutoencoder as RefRecAE
+    res = {}
+    for acc in (1, 2):
+        m = RefRecAE(3, 3, base_channels=32); fill_module(m, 4100)
+        loss_fn = torch.nn.MSELoss()                              # autoencoder.ipynb cell 0
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3)
+        data = [(fill((2, 3, 32, 32), 40 + i, 0, 1), torch.zeros(2, 1, 32, 32)) for i in range(3)]
+        losses = []
+        m.train()
+        for bi, (X, _) in enumerate(data):                        # training.py:134-149 (no zero_grad before the first batch)
+            pred = m(X)
+            loss = loss_fn(pred, X)
+            losses.append(loss.item())
+            (loss / acc).backward()
+            if (bi + 1) % acc == 0 or (bi + 1) == len(data):
+                opt.step(); opt.zero_grad()
+        res[f"acc{acc}_losses"] = np.array(losses)
+        res[f"acc{acc}_mean"] = np.array(np.mean(losses))
+        res[f"acc{acc}_out_w"] = npy(m.decoderOut[0].weight).copy()
+        res[f"acc{acc}_w0"] = npy(m.encoder.encoderPart1.conv1.weight).copy()
+        res[f"acc{acc}_rm"] = npy(m.encoder.encoderPart1.bn1.running_mean).copy()
+    save("trainrecon_ae_32", **res)
+
+
+if want("trainrecon"): gen_trainrecon()
 print("done")

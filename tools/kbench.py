@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
-weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]"""
+weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
+(other families: convt, bn, loss, head, recon, vit, stem, pack)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -247,6 +248,61 @@ def pack():
     print(f"pack all 18 weights: one-pass {t_both:8.1f} us ({nbytes/t_both/1e3:7.1f} GB/s)   per-mode {t_two:8.1f} us")
 
 
+def recon():
+    """Reconstruction head + MSE of the autoencoder pretraining through the C ABI at B = 32, 256 x 256, Cin 64, Cout 3,
+    bf16: fused head forward (3x3 conv + bias + Sigmoid -> fp32 NCHW), MSE forward / backward, Sigmoid backward into the
+    act layout.  In the same process, the chain it replaces: segk_conv3x3 to 32 padded channels with bias, then stock
+    torch.sigmoid(z.float()).contiguous(), F.mse_loss forward and backward, the Sigmoid backward and to_act of the gradient."""
+    import torch.nn.functional as F
+    B, Cin, Cout, H, W = 32, 64, 3, 256, 256
+    dt = torch.bfloat16
+    P, Cp, Coutp = B * H * W, ops.pad32(Cin), ops.pad32(Cout)
+    x = torch.rand((B, H, W, Cp), device="cuda").to(dt)
+    w = torch.randn((Cout, Cin, 3, 3), device="cuda") / (3 * Cin ** 0.5); b = torch.randn(Cout, device="cuda") * 0.1
+    X = torch.rand((B, Cout, H, W), device="cuda")
+    rec = torch.empty((B, Cout, H, W), device="cuda"); drec = torch.empty_like(rec)
+    dz = torch.empty((B, H, W, Coutp), dtype=dt, device="cuda")
+    part = torch.empty(_lib.MSE_PART_FLOATS, device="cuda"); out = torch.empty(1, device="cuda"); go = torch.ones(1, device="cuda")
+    st = ops._stream()
+    hf = lambda: _lib.call("segk_recon_head_fwd", x.data_ptr(), w.data_ptr(), b.data_ptr(), rec.data_ptr(), B, H, W, Cp, Cin,
+                           Cout, 1, st)
+    sb = lambda: _lib.call("segk_recon_sigmoid_bwd", drec.data_ptr(), rec.data_ptr(), dz.data_ptr(), B, H, W, Cout, Coutp, 1, st)
+    mf = lambda: _lib.call("segk_mse_fwd", rec.data_ptr(), X.data_ptr(), part.data_ptr(), part.numel(), out.data_ptr(), rec.numel(),
+                           1, st)
+    mb = lambda: _lib.call("segk_mse_bwd", rec.data_ptr(), X.data_ptr(), go.data_ptr(), drec.data_ptr(), None, rec.numel(), 1, st)
+
+    def fused():
+        hf(); mf(); mb(); sb()
+    n = rec.numel()
+    rows = [("head fwd", hf, P * (Cp * 2 + 4 * Cout)), ("mse fwd", mf, 8.0 * n), ("mse bwd", mb, 12.0 * n),
+            ("sigmoid bwd", sb, P * (8.0 * Cout + 2 * Coutp))]
+    for name, fn, nbytes in rows:
+        t = timeit(fn, 50)
+        print(f"recon {name:12s} {t:8.1f} us  {nbytes / t / 1e3:7.1f} GB/s")
+    tf = timeit(fused, 30)
+    # the replaced chain
+    wp = ops.pack_conv(w, Cin, 0, dt, 0)
+    b32 = torch.zeros(Coutp, device="cuda"); b32[:Cout] = b
+    zb = torch.empty((B, H, W, Coutp), dtype=dt, device="cuda")
+    conv = lambda: _lib.call("segk_conv3x3", x.data_ptr(), 0, wp.data_ptr(), b32.data_ptr(), 0, 0, zb.data_ptr(), 0, 0, B, H, W,
+                             Cp, 0, Coutp, 0, 1, st)
+
+    def stock():
+        conv()
+        zl = ops.act_view(zb, Cout).detach().requires_grad_()
+        r = torch.sigmoid(zl.float()).contiguous()
+        F.mse_loss(r, X).backward()
+        ops.to_act(zl.grad, dt)
+    tc = timeit(conv, 30)
+    ts = timeit(stock, 30)
+    print(f"recon replaced: conv3x3 to {Coutp} ch + bias {tc:8.1f} us; whole chain (conv, stock sigmoid / mse fwd+bwd, to_act) "
+          f"{ts:8.1f} us")
+    print(f"recon fused chain (head fwd, mse fwd, mse bwd, sigmoid bwd) {tf:8.1f} us   = {ts / tf:5.2f}x faster than the "
+          f"replaced chain")
+    clk = ops.clock_probe()
+    print(f"recon clock probe: median {clk['median_ghz']} GHz (mfma_32x32x16), {clk['mfma_16x16x32']['median_ghz']} GHz (mfma_16x16x32)")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "pack":
         pack()
@@ -259,6 +315,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "head":
         head()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "recon":
+        recon()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "loss":
         loss()
