@@ -129,7 +129,11 @@ int segk_convt2x2_dgrad(const void* dout, const void* wpacked, void* din, int B,
  * scale/shift: BatchNorm+ReLU prologue on srcA (the conv input is relu(bn(z)) of the previous conv). */
 int segk_wgrad_tiles(int B, int H, int W, int geo, int dtype);
 /* split-K factor S the host sizes the slab buffer with ([S][CD][taps][CA+CB] fp32) for `tiles` = segk_wgrad_tiles():
- * enough workgroups to fill the chip for this layer's (n, k) tiling, never more slabs than tiles; 0 for invalid input */
+ * enough workgroups to fill the chip for this layer's (n, k) tiling, never more slabs than tiles; 0 for invalid input.
+ * The value is advice, not a requirement: segk_wgrad accepts ANY S in [1, 65535] for every kernel form.  Slab s sums the
+ * spatial tiles s, s + S, s + 2S, ...; every element of all S slabs is written by the call (the caller need not clear the
+ * buffer), a slab whose index is at or above the form's tile count is written as zeros, and nothing beyond slab S - 1 is
+ * touched (tests/test_gpu_wgrad_matrix.py runs S below, at and above the tile count on NaN-filled buffers). */
 int segk_wgrad_split(int tiles, int CD, int CA, int CB, int geo, int dtype);
 int segk_wgrad(const void* dz, const void* srcA, const void* srcB, const float* scale, const float* shift,
                float* slabs, const void* zeros64, int S, int B, int H, int W, int CD, int CA, int CB, int geo,

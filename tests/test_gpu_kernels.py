@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle.fill import fill, labels as fill_labels
+from bn_reference import apply_reference, bwd_reference, sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -290,8 +291,9 @@ def test_wgrad_conv3x3(ops, dtype, case):
         xbt = ops.to_act(dev(xb), dtype); pb, Bp = ops.act_info(xbt, dtype)
     slabs, S = ops.wgrad(pg, Gp, pa, Ap, pb, Bp, B, H, W, 0, dtype, "cuda")
     dw = ops.wgrad_to_param(slabs, S, w.shape, Cout, Cin, CB, 9, "cuda").cpu()
-    scale = np.sqrt(B * H * W)
-    assert (dw - w.grad).abs().max().item() < tol(dtype, 1) * scale * 0.5
+    # one bound for both dtypes (the fp32 one): the operands are exact in the reference, a product of two bf16 values is exact in
+    # fp32 and accumulation and slabs are fp32 in both modes; tests/test_gpu_wgrad_matrix.py holds every instance to it
+    assert (dw - w.grad).abs().max().item() < 1e-5 * np.sqrt(B * H * W)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -299,14 +301,16 @@ def test_wgrad_prologue(ops, dtype):
     B, C, H, W = 2, 64, 16, 24
     z = fill((B, C, H, W), 1, -2, 2); g = fill((B, 32, H, W), 2, -1, 1)
     sc = fill((C,), 3, -1.5, 1.5); sh = fill((C,), 4, -0.5, 0.5)
-    a = torch.relu(z.to(dtype).float() * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)).to(dtype).float()
+    # relu(fmaf(z, scale, shift)) rounded once to fp32 and then to dtype, as the kernels form it (a separate multiply and add in
+    # fp32 lands on the other side of a bf16 tie for about one element in 30000: 2^-8 relative on that element)
+    a = apply_reference(z.to(dtype).permute(0, 2, 3, 1), sc, sh, dtype).permute(0, 3, 1, 2).float()
     w = torch.zeros((32, C, 3, 3), requires_grad=True)
     F.conv2d(a, w, padding=1).backward(g.to(dtype).float())
     ga = ops.to_act(dev(g), dtype); pg, Gp = ops.act_info(ga, dtype)
     za = ops.to_act(dev(z), dtype); pz, Zp = ops.act_info(za, dtype)
     slabs, S = ops.wgrad(pg, Gp, pz, Zp, 0, 0, B, H, W, 0, dtype, "cuda", scale=dev(sc), shift=dev(sh))
     dw = ops.wgrad_to_param(slabs, S, w.shape, 32, C, 0, 9, "cuda").cpu()
-    assert (dw - w.grad).abs().max().item() < tol(dtype, 1) * np.sqrt(B * H * W) * 0.5
+    assert (dw - w.grad).abs().max().item() < 1e-5 * np.sqrt(B * H * W)      # both dtypes: see test_wgrad_conv3x3
 
 
 @pytest.mark.parametrize("case", [(7, 64), (512, 96), (1024, 32), (1025, 64), (4096, 64), (3000, 1024)])
@@ -368,9 +372,16 @@ def test_bn_relu_bwd(ops, dtype):
     out = torch.empty((B, H, W, Cp), dtype=dtype, device="cuda")
     dg, db = ops.bn_relu_bwd(ops.act_info(ga, dtype)[0], ops.act_info(za, dtype)[0], out.data_ptr(), scale, shift,
                              pad(mean), pad(rstd), B * H * W, C, dtype, "cuda")
+    # dgamma / dbeta: fp32 sums of inputs that are exact in either dtype, so one tolerance against autograd for both, and the
+    # derived bound (tests/bn_reference.py) against float64 on the same z, dy and the fp32 scale / shift / mean / rstd as passed
+    assert torch.allclose(dg.cpu(), gam.grad, rtol=1e-4, atol=5e-4)
+    assert torch.allclose(db.cpu(), bet.grad, rtol=1e-4, atol=5e-4)
+    P = B * H * W
+    rows = lambda v: v.permute(0, 2, 3, 1).reshape(P, C)
+    ref = bwd_reference(rows(z0), rows(g0), *(v.cpu()[:C] for v in (scale, shift, pad(mean), pad(rstd))))
+    assert ((db.cpu().double() - ref["dbeta"]).abs() <= sum_bound(P, Cp, dtype, ref["abs_g"])).all()
+    assert ((dg.cpu().double() - ref["dgamma"]).abs() <= sum_bound(P, Cp, dtype, ref["abs_gx"], per_term_roundings=3)).all()
     t = 1e-4 if dtype == torch.float32 else 3e-2
-    assert torch.allclose(dg.cpu(), gam.grad, rtol=t, atol=t * 5)
-    assert torch.allclose(db.cpu(), bet.grad, rtol=t, atol=t * 5)
     assert (back(ops.act_view(out, C)) - z.grad).abs().max().item() < t
 
 
