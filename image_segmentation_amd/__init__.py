@@ -8,3 +8,4 @@ from .losses import (CrossEntropyLoss, MSELoss, WeightedMemoryEfficientDiceLoss,
 from .clipunet import ClipUNet, UNetDecoder, DecoderBlock, ClipViTEncoder                   # noqa: F401
 from .autoencoder import SegmentationAutoencoder, ReconstructionAutoencoder               # noqa: F401
 from .prompt import PromptModel                                                            # noqa: F401
+from .inference import Segmenter, Prediction, predict, load_checkpoint, COLOR_MAP, CLASS_NAMES   # noqa: F401

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 311          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 312          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
 
@@ -71,6 +71,8 @@ SIGNATURES = {
     "segk_vit_tokens_to_grid": (_i, [_fp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_resize_pad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_crop_resize": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_resize_pad_u8": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_predict_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd_bn": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_bn": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),

@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "segk_internal.h"
 #include "../../include/segk.h"
+#include <type_traits>
 
 namespace {
 
@@ -218,6 +219,8 @@ extern "C" int segk_bilinear_bwd(const void* dy, void* dx, float* scratch, int B
 // mode "nearest": src = min(floor(o*scale), in-1).
 // crop_resize: slot [C,T,T] -> crop the (nh,nw) window -> [C,oh,ow] with F.interpolate bilinear
 // (align_corners=False, no anti-aliasing) or nearest (utils.py:51-75).
+// resize_pad_u8 / predict_mask: the same two steps for prediction (reference segmentation_webapp/app.py:250-326): an 8-bit
+// interleaved image straight into its slot, and slot -> class mask + colour image without the full-size logits.
 namespace {
 
 struct AA {
@@ -248,6 +251,53 @@ __device__ __forceinline__ float aa_w(const AA& a, int j) {
   return a.total != 0.f ? w / a.total : w;
 }
 
+// The two-tap blend and the nearest source index of F.interpolate, shared by every kernel below: with -ffp-contract=off
+// one source expression gives one bit pattern, which is what lets the fused prediction kernel agree with crop_resize
+// exactly (tests/test_gpu_inference.py).
+__device__ __forceinline__ float bilerp(float a, float b, float d, float e, float ly, float lx) {
+  // ATen: (1-ly)*((1-lx)*a + lx*b) + ly*((1-lx)*d + lx*e)
+  return (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e);
+}
+__device__ __forceinline__ int nearest_index(int o, float scale, int in_size) {
+  const int s = (int)floorf((float)o * scale);
+  return s > in_size - 1 ? in_size - 1 : s;
+}
+
+// One output pixel (oy, ox) of the resize of an (H, W) image, N channels at a time; ld(y, x, v) fetches the N source
+// values of pixel (y, x) as floats.  mode 0: anti-aliased triangle filter, mode 2: plain two-tap bilinear.
+template <int N, typename L>
+__device__ __forceinline__ void resize_sample(L ld, int oy, int ox, float sh, float sw, int H, int W, int mode, float (&v)[N]) {
+  if (mode == 2) {   // plain two-tap bilinear, align_corners=False (torchvision's tensor resize before 0.17)
+    int y0, y1, x0, x1;
+    float ly, lx;
+    src_index(oy, sh, H, y0, y1, ly);
+    src_index(ox, sw, W, x0, x1, lx);
+    float a[N], b[N], d[N], e[N];
+    ld(y0, x0, a); ld(y0, x1, b); ld(y1, x0, d); ld(y1, x1, e);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = bilerp(a[k], b[k], d[k], e[k], ly, lx);
+  } else {
+    const AA ay = aa_taps(oy, sh, H), ax = aa_taps(ox, sw, W);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = 0.f;
+    for (int jy = 0; jy < ay.n; ++jy) {
+      const float wy = aa_w(ay, jy);
+      float row[N];
+#pragma unroll
+      for (int k = 0; k < N; ++k) row[k] = 0.f;
+      for (int jx = 0; jx < ax.n; ++jx) {
+        const float wx = aa_w(ax, jx);
+        float t[N];
+        ld(ay.lo + jy, ax.lo + jx, t);
+#pragma unroll
+        for (int k = 0; k < N; ++k) row[k] = fmaf(wx, t[k], row[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < N; ++k) v[k] = fmaf(wy, row[k], v[k]);
+    }
+  }
+}
+
 template <typename V>
 __global__ __launch_bounds__(256) void resize_pad_kernel(const V* __restrict__ img, V* __restrict__ out, int C, int H, int W,
                                                          int nh, int nw, int T, int pt, int pl, int mode) {
@@ -262,31 +312,51 @@ __global__ __launch_bounds__(256) void resize_pad_kernel(const V* __restrict__ i
     if (oy >= 0 && oy < nh && ox >= 0 && ox < nw) {
       const V* src = img + (size_t)c * H * W;
       if (mode == 1) {
-        int sy = (int)floorf((float)oy * sh), sx = (int)floorf((float)ox * sw);
-        sy = sy > H - 1 ? H - 1 : sy;
-        sx = sx > W - 1 ? W - 1 : sx;
-        v = src[(size_t)sy * W + sx];
-      } else if (mode == 2) {   // plain two-tap bilinear, align_corners=False (torchvision's tensor resize before 0.17)
-        int y0, y1, x0, x1;
-        float ly, lx;
-        src_index(oy, sh, H, y0, y1, ly);
-        src_index(ox, sw, W, x0, x1, lx);
-        const float a = (float)src[(size_t)y0 * W + x0], b = (float)src[(size_t)y0 * W + x1];
-        const float d = (float)src[(size_t)y1 * W + x0], e = (float)src[(size_t)y1 * W + x1];
-        v = (V)((1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e));
+        v = src[(size_t)nearest_index(oy, sh, H) * W + nearest_index(ox, sw, W)];
       } else {
-        const AA ay = aa_taps(oy, sh, H), ax = aa_taps(ox, sw, W);
-        float acc = 0.f;
-        for (int jy = 0; jy < ay.n; ++jy) {
-          const float wy = aa_w(ay, jy);
-          float row = 0.f;
-          for (int jx = 0; jx < ax.n; ++jx) row = fmaf(aa_w(ax, jx), (float)src[(size_t)(ay.lo + jy) * W + ax.lo + jx], row);
-          acc = fmaf(wy, row, acc);
-        }
-        v = (V)acc;
+        float r[1];
+        resize_sample<1>([&](int y, int x, float (&t)[1]) { t[0] = (float)src[(size_t)y * W + x]; }, oy, ox, sh, sw, H, W, mode, r);
+        v = (V)r[0];
       }
     }
     out[i] = v;
+  }
+}
+
+// 8-bit interleaved image [H,W,CIN] (what PIL / decode_image hand out) -> float slot [min(CIN,3),T,T]: to_tensor's
+// (float)u8 / 255.0f on every tap, then the tap / weight code of resize_pad_kernel, so the slot carries the bits the float
+// route produces from the converted image.  One thread per slot pixel: the CO channels of a source pixel sit in one
+// dword-or-less and are fetched together.  Reads H*W*CIN bytes at most, writes 4*CO*T*T.
+template <int CIN, int MODE>
+__global__ __launch_bounds__(256) void resize_pad_u8_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H, int W,
+                                                            int nh, int nw, int T, int pt, int pl) {
+  constexpr int CO = CIN < 3 ? CIN : 3;
+  const int total = T * T;
+  const float sh = (float)H / (float)nh, sw = (float)W / (float)nw;
+  auto ld = [&](int y, int x, float (&t)[CO]) {
+    const uint8_t* q = img + ((size_t)y * W + x) * CIN;
+    if constexpr (CIN == 4) {   // one aligned dword; the alpha byte is dropped (process_batch_forward does the same)
+      const uint32_t w = *(const uint32_t*)q;
+      t[0] = (float)(w & 255u) / 255.0f;
+      t[1] = (float)((w >> 8) & 255u) / 255.0f;
+      t[2] = (float)((w >> 16) & 255u) / 255.0f;
+    } else {
+#pragma unroll
+      for (int k = 0; k < CO; ++k) t[k] = (float)q[k] / 255.0f;
+    }
+  };
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int ty = i / T, tx = i - ty * T;
+    const int oy = ty - pt, ox = tx - pl;
+    float v[CO];
+#pragma unroll
+    for (int k = 0; k < CO; ++k) v[k] = 0.f;
+    if (oy >= 0 && oy < nh && ox >= 0 && ox < nw) {
+      if (MODE == 1) ld(nearest_index(oy, sh, H), nearest_index(ox, sw, W), v);
+      else resize_sample<CO>(ld, oy, ox, sh, sw, H, W, MODE, v);
+    }
+#pragma unroll
+    for (int k = 0; k < CO; ++k) out[(size_t)k * total + i] = v[k];
   }
 }
 
@@ -301,22 +371,145 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const float* __restric
     const float* src = slot + ((size_t)c * T + pt) * T + pl;       // window origin; row pitch T
     float v;
     if (mode == 1) {
-      int sy = (int)floorf((float)oy * sh), sx = (int)floorf((float)ox * sw);
-      sy = sy > nh - 1 ? nh - 1 : sy;
-      sx = sx > nw - 1 ? nw - 1 : sx;
-      v = src[(size_t)sy * T + sx];
+      v = src[(size_t)nearest_index(oy, sh, nh) * T + nearest_index(ox, sw, nw)];
     } else {
       int y0, y1, x0, x1;
       float ly, lx;
       src_index(oy, sh, nh, y0, y1, ly);
       src_index(ox, sw, nw, x0, x1, lx);
-      const float a = src[(size_t)y0 * T + x0], b = src[(size_t)y0 * T + x1];
-      const float d = src[(size_t)y1 * T + x0], e = src[(size_t)y1 * T + x1];
-      // ATen: (1-ly)*((1-lx)*a + lx*b) + ly*((1-lx)*d + lx*e)
-      v = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e);
+      v = bilerp(src[(size_t)y0 * T + x0], src[(size_t)y0 * T + x1], src[(size_t)y1 * T + x0], src[(size_t)y1 * T + x1], ly, lx);
     }
     out[i] = v;
   }
+}
+
+// Prediction: slot [C,T,T] -> crop + resize (the arithmetic of crop_resize_kernel) -> argmax over classes (first maximum,
+// NaN maximal: confusion_kernel / torch.argmax) -> uint8 mask [oh,ow], optional RGB [oh,ow,3], class counts and confusion
+// counts.  The full-size logits are never stored: 1 + 3 bytes leave per pixel where crop_resize + argmax + palette
+// index move ~50, and the source is a C*T*T*4-byte slot that stays in L2.
+// A thread owns four consecutive FLAT pixels p = oy*ow + ox, p % 4 == 0: the mask leaves as one aligned dword, the colour
+// as three; a thread may straddle a row end, so (oy, ox) advance per pixel.  Loads are unconditional with clamped
+// indices (pixels past the end repeat the last one, classes past C repeat class C-1 and can never win the strict
+// comparison), so the 4*NC taps of a pixel are in flight together.  Class counts live in registers over the grid-stride
+// loop and are summed per wave, confusion counts go to an LDS histogram; a block ends with one 64-bit atomic per non-zero
+// bin (integers: order-independent, bit-stable).
+template <int NC, int MODE, bool LAB>
+__global__ __launch_bounds__(256) void predict_mask_kernel(const float* __restrict__ slot, uint8_t* __restrict__ mask,
+                                                           uint8_t* __restrict__ color, const uint8_t* __restrict__ palette,
+                                                           unsigned long long* __restrict__ counts,
+                                                           const long long* __restrict__ labels, unsigned long long* __restrict__ M,
+                                                           int C, int T, int pt, int pl, int nh, int nw, int oh, int ow) {
+  constexpr int NB = SEGK_MAX_CLASSES * SEGK_MAX_CLASSES;
+  __shared__ unsigned int hist[NB + SEGK_MAX_CLASSES];            // confusion bins, then class counts
+  if (threadIdx.x < NB + SEGK_MAX_CLASSES) hist[threadIdx.x] = 0;
+  unsigned int pal[NC], cnt[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) { pal[k] = 0; cnt[k] = 0; }
+  if (color) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const uint8_t* q = palette + 3 * (k < C ? k : C - 1);
+      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
+    }
+  }
+  __syncthreads();
+  const int total = oh * ow;
+  const float sh = (float)nh / (float)oh, sw = (float)nw / (float)ow;
+  // per-class window origins are uniform (scalar registers); a tap is origin + a 32-bit BYTE offset, the addressing form
+  // that costs no 64-bit vector arithmetic per load
+  const char* wk[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) wk[k] = (const char*)(slot + ((size_t)(k < C ? k : C - 1) * T + pt) * T + pl);
+  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
+  const unsigned pitch = 4u * (unsigned)T;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
+    const int p = (int)(q * 4);
+    long long lab[4];
+    if (LAB) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
+    }
+    int oy = p / ow, ox = p - oy * ow;
+    // the row's taps change only where the thread steps over a row end
+    int y0, y1;
+    float ly = 0.f;
+    auto row_taps = [&]() {
+      if (MODE == 1) y0 = y1 = nearest_index(oy, sh, nh);
+      else src_index(oy, sh, nh, y0, y1, ly);
+    };
+    row_taps();
+    int best[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v[NC];
+      if (MODE == 1) {
+        const unsigned o = (unsigned)y0 * pitch + 4u * (unsigned)nearest_index(ox, sw, nw);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k] = tap(wk[k], o);
+      } else {
+        int x0, x1;
+        float lx;
+        src_index(ox, sw, nw, x0, x1, lx);
+        const unsigned r0 = (unsigned)y0 * pitch, r1 = (unsigned)y1 * pitch, c0 = 4u * (unsigned)x0, c1 = 4u * (unsigned)x1;
+        float a[NC], b[NC], d[NC], e[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          a[k] = tap(wk[k], r0 + c0); b[k] = tap(wk[k], r0 + c1); d[k] = tap(wk[k], r1 + c0); e[k] = tap(wk[k], r1 + c1);
+        }
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k] = bilerp(a[k], b[k], d[k], e[k], ly, lx);
+      }
+      int bi = 0;
+      float bv = v[0];
+#pragma unroll
+      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
+        const bool take = (v[k] > bv) | ((v[k] != v[k]) & (bv == bv));
+        bv = take ? v[k] : bv;
+        bi = take ? k : bi;
+      }
+      best[j] = bi;
+      if (p + j + 1 < total && ++ox == ow) { ox = 0; ++oy; row_taps(); }
+    }
+    const bool full = p + 3 < total;
+    unsigned int c4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned live = p + j < total ? 1u : 0u;
+      c4[j] = 0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        cnt[k] += best[j] == k ? live : 0u;
+        c4[j] = best[j] == k ? pal[k] : c4[j];
+      }
+      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[best[j] * SEGK_MAX_CLASSES + (int)lab[j]], 1u);
+    }
+    if (full) {
+      *(uint32_t*)(mask + (unsigned)p) = (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
+      if (color)
+        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (p + j < total) {
+          mask[p + j] = (uint8_t)best[j];
+          if (color)
+            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
+        }
+    }
+  }
+  if (counts) {   // wave sums first: 64 lanes adding to one LDS word serialise
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      unsigned int c = cnt[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
+    }
+  }
+  __syncthreads();
+  // integer sums: one 64-bit atomic per non-zero bin per block, order-independent and bit-stable
+  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+  if (counts && threadIdx.x >= NB && threadIdx.x < NB + SEGK_MAX_CLASSES && hist[threadIdx.x])
+    atomicAdd(&counts[threadIdx.x - NB], (unsigned long long)hist[threadIdx.x]);
 }
 
 }  // namespace
@@ -350,5 +543,73 @@ extern "C" int segk_crop_resize(const float* slot, float* out, int C, int T, int
   hipLaunchKernelGGL(crop_resize_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)s, slot, out, C, T, pad_top, pad_left, nh, nw, oh,
                      ow, mode);
   SEGK_CHECK_LAUNCH("crop_resize");
+  return 0;
+}
+
+extern "C" int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T, int pad_top,
+                                  int pad_left, int mode, segk_stream_t s) {
+  SEGK_REQUIRE(img_hwc && out && H > 0 && W > 0 && nh > 0 && nw > 0 && T > 0 && T <= 16384, "resize_pad_u8: bad shape");
+  SEGK_REQUIRE(Cin == 1 || Cin == 3 || Cin == 4, "resize_pad_u8: 1, 3 or 4 interleaved channels, got %d", Cin);
+  SEGK_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + nh <= T && pad_left + nw <= T, "resize_pad_u8: window outside the target");
+  SEGK_REQUIRE(mode >= 0 && mode <= 2, "resize_pad_u8: bad mode %d", mode);
+  SEGK_REQUIRE(Cin != 4 || ((uintptr_t)img_hwc & 3) == 0, "resize_pad_u8: a 4-channel image must be 4-byte aligned");
+  long g = ((long)T * T + 255) / 256;
+  if (g > 16384) g = 16384;
+  hipStream_t st = (hipStream_t)s;
+  auto launch = [&](auto cin, auto md) {
+    hipLaunchKernelGGL((resize_pad_u8_kernel<decltype(cin)::value, decltype(md)::value>), dim3((int)g), dim3(256), 0, st, img_hwc, out,
+                       H, W, nh, nw, T, pad_top, pad_left);
+  };
+  auto by_mode = [&](auto cin) {
+    if (mode == 0) launch(cin, std::integral_constant<int, 0>{});
+    else if (mode == 1) launch(cin, std::integral_constant<int, 1>{});
+    else launch(cin, std::integral_constant<int, 2>{});
+  };
+  if (Cin == 1) by_mode(std::integral_constant<int, 1>{});
+  else if (Cin == 3) by_mode(std::integral_constant<int, 3>{});
+  else by_mode(std::integral_constant<int, 4>{});
+  SEGK_CHECK_LAUNCH("resize_pad_u8");
+  return 0;
+}
+
+extern "C" int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts,
+                                 const int64_t* labels, uint64_t* M, int C, int T, int pad_top, int pad_left, int nh, int nw,
+                                 int oh, int ow, int mode, segk_stream_t s) {
+  SEGK_REQUIRE(slot && mask && T > 0 && nh > 0 && nw > 0 && oh > 0 && ow > 0, "predict_mask: bad shape");
+  SEGK_REQUIRE(C >= 1 && C <= SEGK_MAX_CLASSES, "predict_mask: 1..%d classes supported, got %d", SEGK_MAX_CLASSES, C);
+  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "predict_mask: color and palette come together");
+  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "predict_mask: labels and M come together");
+  SEGK_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + nh <= T && pad_left + nw <= T, "predict_mask: window outside the slot");
+  SEGK_REQUIRE(mode == 0 || mode == 1, "predict_mask: bad mode %d", mode);
+  SEGK_REQUIRE((long)T * T < (1L << 30) && (long)oh * ow < (1L << 31) - 4, "predict_mask: slot or output too large for 32-bit offsets");
+  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0, "predict_mask: mask and color must be 4-byte aligned");
+  long g = (((long)oh * ow + 3) / 4 + 255) / 256;
+  // Block cap: the neighbours' 16384 for the mask / colour alone.  With counts or labels every block ends in 64-bit atomics
+  // on the same few words, and those serialise in L2 at ~12 ns per block (measured: 11719 blocks at 3000x4000 took 150 us
+  // against 30 us without the counts), so the grid becomes persistent: three blocks per CU, one resident round for every
+  // instance (the 8-class bilinear one fits three), 17 us at 1200x1600 and 36-42 us at 3000x4000.
+  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;
+  if (g > cap) g = cap;
+  hipStream_t st = (hipStream_t)s;
+  auto launch = [&](auto nc, auto md, auto lab) {
+    hipLaunchKernelGGL((predict_mask_kernel<decltype(nc)::value, decltype(md)::value, decltype(lab)::value>), dim3((int)g), dim3(256), 0,
+                       st, slot, mask, color, palette, (unsigned long long*)counts, (const long long*)labels, (unsigned long long*)M, C,
+                       T, pad_top, pad_left, nh, nw, oh, ow);
+  };
+  auto by_lab = [&](auto nc, auto md) {
+    if (labels) launch(nc, md, std::true_type{});
+    else launch(nc, md, std::false_type{});
+  };
+  auto by_mode = [&](auto nc) {
+    if (mode == 0) by_lab(nc, std::integral_constant<int, 0>{});
+    else by_lab(nc, std::integral_constant<int, 1>{});
+  };
+  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
+  if (C == 1) by_mode(std::integral_constant<int, 1>{});
+  else if (C == 2) by_mode(std::integral_constant<int, 2>{});
+  else if (C == 3) by_mode(std::integral_constant<int, 3>{});
+  else if (C == 4) by_mode(std::integral_constant<int, 4>{});
+  else by_mode(std::integral_constant<int, SEGK_MAX_CLASSES>{});
+  SEGK_CHECK_LAUNCH("predict_mask");
   return 0;
 }

@@ -1,0 +1,235 @@
+"""Prediction with a trained model -- the arithmetic of the reference's demo service (prompt_based/segmentation_webapp/
+app.py:38-88 load_model, :250-326 decode -> to_tensor -> resize + pad -> model -> reverse -> argmax(0) -> uint8 ->
+COLOR_MAP) as a library call; the Flask / base64 / HTML part and create_prompt_mask stay out.
+
+    model = load_checkpoint(seg.unet(3, 4), "unet.pt").cuda()
+    pred = Segmenter(model)([np.asarray(PIL.Image.open("cat.jpg").convert("RGB"))])[0]
+    PIL.Image.fromarray(pred.color.cpu().numpy(), "RGB").save("cat_mask.png")
+
+Both ends of the forward are HIP kernels of their own (csrc/resize.hip): segk_resize_pad_u8 takes the decoder's 8-bit
+interleaved image straight into the network batch, and segk_predict_mask goes from the network output to the uint8 class
+mask, the RGB image, the class counts and (with labels) the confusion counts in one pass, without storing the full-size
+logits that process_batch_reverse + argmax + a palette index would.  Nothing here synchronises with the host when the
+inputs are already on the device; there is no CPU path."""
+import inspect
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from . import utils as U
+
+# app.py:187-208 -- the demo's palette and the two class-name tables
+COLOR_MAP = {0: (0, 0, 0), 1: (255, 0, 0), 2: (0, 255, 0), 3: (0, 0, 255)}
+CLASS_NAMES = {"standard": {0: "Background", 1: "Cat", 2: "Dog", 3: "Boundary"},
+               "prompt_model": {0: "Deactivated", 1: "Background+Boundary", 2: "Cat", 3: "Dog"}}
+
+
+def load_checkpoint(model, path, map_location="cpu", strict=True):
+    """app.py:65-84 -- load a checkpoint file into an already built model and return it in eval() mode.  The file may
+    hold {"model_state_dict": ...}, {"state_dict": ...} or a bare state dict; a `module.` prefix (DataParallel /
+    DistributedDataParallel) is stripped from the keys.  Host-only."""
+    checkpoint = torch.load(path, map_location=map_location, weights_only=False)
+    if "model_state_dict" in checkpoint:
+        state_dict = checkpoint["model_state_dict"]
+    elif "state_dict" in checkpoint:
+        state_dict = checkpoint["state_dict"]
+    else:
+        state_dict = checkpoint
+    state_dict = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+    model.load_state_dict(state_dict, strict=strict)
+    return model.eval()
+
+
+@dataclass
+class Prediction:
+    mask: torch.Tensor                      # uint8 [H,W] class indices at the image's own size
+    color: Optional[torch.Tensor]           # uint8 [H,W,3] (what Image.fromarray(..., "RGB") takes), None without a palette
+    counts: torch.Tensor                    # int64 [C] pixels per predicted class
+    confusion: Optional[torch.Tensor]       # int64 [C,C], [pred][label]; None without labels
+    meta: dict                              # the resize / padding record of process_batch_forward
+
+
+def _num_classes(model):
+    """Classes of the model's output head, read from the module tree (None when it cannot be told before a forward)."""
+    if hasattr(model, "clip") and hasattr(model, "mask"):              # PromptModel: the probabilities of its CLIP branch
+        return _num_classes(model.clip)
+    for name in ("output", "output_layer", "finalConv"):
+        head = getattr(model, name, None)
+        if isinstance(head, torch.nn.Conv2d):
+            return head.out_channels
+    convs = [m for m in model.modules() if isinstance(m, torch.nn.Conv2d)]
+    return convs[-1].out_channels if convs else None
+
+
+def _palette_tensor(palette):
+    if palette is None:
+        return None
+    if isinstance(palette, dict):
+        if sorted(palette) != list(range(len(palette))):
+            raise ValueError("palette: a mapping must have the keys 0..K-1")
+        palette = [palette[k] for k in range(len(palette))]
+    t = torch.as_tensor(np.asarray(palette)).cpu()
+    if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1 or bool(((t < 0) | (t > 255)).any()):
+        raise ValueError(f"palette: expected K rows of three values in 0..255, got shape {tuple(t.shape)}")
+    return t.to(torch.uint8).contiguous()
+
+
+def _check_classes(C, pal):
+    if C > _lib.MAX_CLASSES:
+        raise ValueError(f"the model has {C} classes, prediction supports at most {_lib.MAX_CLASSES}")
+    if pal is not None and pal.shape[0] < C:
+        raise ValueError(f"palette has {pal.shape[0]} rows, the model has {C} classes")
+
+
+def _as_tensor(a):
+    return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+
+
+def _into_slot(image, slot, T, interpolation, antialias, what):
+    """One image or heat-map -> its slot [c,T,T]: uint8 [H,W,Cin] / [H,W] through segk_resize_pad_u8, float [C,H,W]
+    through segk_resize_pad.  Returns the metadata."""
+    if image.dtype == torch.uint8:
+        if image.ndim == 2:
+            image = image.unsqueeze(-1)
+        if image.ndim != 3 or image.shape[2] not in (1, 3, 4):
+            raise ValueError(f"{what}: 8-bit inputs are [H,W,C] with 1, 3 or 4 channels (or [H,W]), got {tuple(image.shape)}")
+        H, W, cin = image.shape
+        if min(cin, 3) != slot.shape[0]:
+            raise ValueError(f"{what}: {min(cin, 3)} channels where the batch has {slot.shape[0]}")
+        nh, nw, pt, pl, meta = U._geometry(H, W, T)
+        antialias = U.ANTIALIAS if antialias is None else antialias
+        mode = 1 if interpolation == U.NEAREST else (0 if antialias else 2)
+        src = image.contiguous()
+        if cin == 4 and src.data_ptr() % 4:
+            src = src.clone()
+        _lib.call("segk_resize_pad_u8", src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, mode, ops._stream())
+        return meta
+    if not torch.is_floating_point(image) or image.ndim != 3:
+        raise ValueError(f"{what}: expected a float [C,H,W] tensor or a uint8 [H,W,C] image, got {image.dtype} {tuple(image.shape)}")
+    if image.shape[0] == 4:
+        image = image[:3]
+    if image.shape[0] != slot.shape[0]:
+        raise ValueError(f"{what}: {image.shape[0]} channels where the batch has {slot.shape[0]}")
+    return U._resize_pad_into(image, slot, T, interpolation, antialias)
+
+
+def _channels(image):
+    if image.dtype == torch.uint8:
+        return 1 if image.ndim == 2 else min(int(image.shape[-1]), 3)
+    return min(int(image.shape[0]), 3)
+
+
+class Segmenter:
+    """Callable prediction pipeline around a trained model: `Segmenter(model)(images)` -> list of Prediction.
+
+    images    list of float [C,H,W] tensors (the contract of process_batch_forward) or uint8 [H,W,C] tensors / NumPy
+              arrays, on the host or the device, of any sizes
+    heatmaps  for two-input models (PromptModel.forward(x, heatmap)): one float [1,H,W] or uint8 [H,W] / [H,W,1] per image
+    labels    optional integer [H,W] / [1,H,W] maps at the images' own sizes: the confusion counts come from the same pass
+              (labels outside [0,C) are skipped, as the eval loops skip 255 / ignore)"""
+
+    def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None):
+        if interpolation not in (U.BILINEAR, U.NEAREST):
+            raise ValueError(f"interpolation: '{U.BILINEAR}' or '{U.NEAREST}', got {interpolation!r}")
+        if int(batch_size) < 1 or int(target_size) < 1:
+            raise ValueError("batch_size and target_size are positive")
+        self.model, self.target_size, self.interpolation = model, int(target_size), interpolation
+        self.batch_size, self.antialias = int(batch_size), antialias
+        self._palette = _palette_tensor(palette)
+        self._palette_dev = {}
+        self._two_input = len([p for p in inspect.signature(model.forward).parameters.values()
+                               if p.default is p.empty and p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]) >= 2
+        self.num_classes = _num_classes(model)
+        if self.num_classes is not None:
+            _check_classes(self.num_classes, self._palette)
+
+    def _palette_on(self, dev):
+        if self._palette is None:
+            return None
+        if dev not in self._palette_dev:
+            self._palette_dev[dev] = self._palette.to(dev)
+        return self._palette_dev[dev]
+
+    def __call__(self, images, heatmaps=None, labels=None):
+        images = [_as_tensor(im) for im in images]
+        n = len(images)
+        if self._two_input and heatmaps is None:
+            raise ValueError("this model takes (image, heatmap): pass heatmaps=")
+        if not self._two_input and heatmaps is not None:
+            raise ValueError("heatmaps were given to a model whose forward takes the image alone")
+        if heatmaps is not None and len(heatmaps) != n:
+            raise ValueError(f"{len(heatmaps)} heatmaps for {n} images")
+        if labels is not None and len(labels) != n:
+            raise ValueError(f"{len(labels)} label maps for {n} images")
+        param = next(self.model.parameters(), None)
+        if param is None:
+            raise ValueError("the model has no parameters")
+        ops._require_cuda(param, "Segmenter")
+        dev = param.device
+        modes = [(m, m.training) for m in self.model.modules()]
+        out = []
+        try:
+            self.model.eval()
+            with torch.no_grad(), torch.cuda.device(dev):
+                for i in range(0, n, self.batch_size):
+                    j = min(i + self.batch_size, n)
+                    out += self._chunk(dev, images[i:j], None if heatmaps is None else heatmaps[i:j],
+                                       None if labels is None else labels[i:j])
+        finally:
+            for m, was in modes:
+                m.training = was
+        return out
+
+    def _chunk(self, dev, images, heatmaps, labels):
+        T, n = self.target_size, len(images)
+        images = [im.to(dev, non_blocking=True) for im in images]
+        X = torch.empty((n, _channels(images[0]), T, T), dtype=torch.float32, device=dev)
+        metas = [_into_slot(im, X[k], T, self.interpolation, self.antialias, "image") for k, im in enumerate(images)]
+        if heatmaps is None:
+            y = self.model(X)
+        else:
+            Hm = torch.empty((n, 1, T, T), dtype=torch.float32, device=dev)
+            for k, hm in enumerate(heatmaps):
+                hm = _as_tensor(hm).to(dev, non_blocking=True)
+                hmeta = _into_slot(hm, Hm[k], T, self.interpolation, self.antialias, "heatmap")
+                if hmeta["original_size"] != metas[k]["original_size"]:
+                    raise ValueError(f"heatmap {k} is {hmeta['original_size']}, its image {metas[k]['original_size']}")
+            y = self.model(X, Hm)
+        ops._require_cuda(y, "Segmenter (model output)")
+        y = y.detach()
+        if y.ndim != 4 or y.shape[0] != n or y.shape[2] != T or y.shape[3] != T:
+            raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
+        if y.dtype != torch.float32 or not y.is_contiguous():
+            y = y.float().contiguous()
+        C = int(y.shape[1])
+        pal = self._palette_on(dev)
+        _check_classes(C, pal)
+        counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
+        M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
+        mode = 1 if self.interpolation == U.NEAREST else 0
+        s = ops._stream()
+        preds = []
+        for k, meta in enumerate(metas):
+            pl, pt, _, _ = meta["pad"]
+            nh, nw = meta["new_size"]
+            oh, ow = meta["original_size"]
+            mask = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+            color = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev) if pal is not None else None
+            lab = None
+            if labels is not None:
+                lab = _as_tensor(labels[k])
+                if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
+                    raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
+                lab = lab.to(dev, non_blocking=True).long().contiguous()
+            _lib.call("segk_predict_mask", y[k].data_ptr(), mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(),
+                      ops._p(lab), ops._p(None if M is None else M[k]), C, T, pt, pl, nh, nw, oh, ow, mode, s)
+            preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
+        return preds
+
+
+def predict(model, images, heatmaps=None, labels=None, **kw):
+    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels)."""
+    return Segmenter(model, **kw)(images, heatmaps=heatmaps, labels=labels)

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 311
-#define SEGK_ENTRY_COUNT 73
+#define SEGK_ABI_VERSION 312
+#define SEGK_ENTRY_COUNT 75
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -253,6 +253,21 @@ int segk_resize_pad(const void* img, void* out, int C, int H, int W, int nh, int
  * (align_corners=False; mode 0) or nearest (mode 1) (utils.py:51-75) */
 int segk_crop_resize(const float* slot, float* out, int C, int T, int pad_top, int pad_left, int nh, int nw, int oh,
                      int ow, int mode, segk_stream_t s);
+/* prediction pre-processing (segmentation_webapp/app.py:266-273: TF.to_tensor + process_batch_forward): an 8-bit
+ * interleaved image [H,W,Cin], Cin 1 / 3 / 4 (alpha dropped; 4-channel images 4-byte aligned), -> its float slot
+ * [min(Cin,3),T,T].  Every tap is (float)u8 / 255.0f fed to the tap / weight code of segk_resize_pad, so the slot equals
+ * bit for bit what segk_resize_pad makes of the converted image.  mode as in segk_resize_pad (0 / 1 / 2). */
+int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T, int pad_top,
+                       int pad_left, int mode, segk_stream_t s);
+/* prediction post-processing in one pass (app.py:291-326; utils.py:51-75): slot [C,T,T] fp32 (logits or probabilities) ->
+ * crop + resize with the arithmetic, geometry arguments and modes of segk_crop_resize -> argmax over the classes (first
+ * maximum, NaN maximal: torch.argmax / segk_confusion) -> mask [oh,ow] uint8.  The full-size logits are never stored.
+ * Optional outputs: color [oh,ow,3] uint8 = palette[C][3] looked up per pixel (color and palette come together);
+ * counts[8] += pixels per class; M[pred*8 + label] += 1 as segk_confusion does, for labels [oh,ow] inside [0,C) (labels
+ * and M come together; the caller zeroes counts and M).  1 <= C <= 8; mask and color 4-byte aligned. */
+int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts,
+                      const int64_t* labels, uint64_t* M, int C, int T, int pad_top, int pad_left, int nh, int nw, int oh,
+                      int ow, int mode, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

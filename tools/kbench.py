@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -303,7 +303,52 @@ def recon():
     print(f"recon clock probe: median {clk['median_ghz']} GHz (mfma_32x32x16), {clk['mfma_16x16x32']['median_ghz']} GHz (mfma_16x16x32)")
 
 
+def predict():
+    """Prediction post-processing through the C ABI: the fused segk_predict_mask (mask + colour + class counts in one pass)
+    against the route it replaces -- segk_crop_resize to full-size fp32 logits, torch.argmax, a palette index and
+    bincount -- at three output sizes, C = 3 and 4, from a 224 x 224 slot.  Both run in this process, alternating, seven
+    rounds each; the line gives the median and the min..max spread.  Bytes per pixel are what each route WRITES."""
+    from image_segmentation_amd.utils import _geometry
+    T = 224
+    st = ops._stream()
+    for oh, ow in ((375, 500), (1200, 1600), (3000, 4000)):
+        for C in (3, 4):
+            nh, nw, pt, pl, _ = _geometry(oh, ow, T)
+            slot = torch.randn((C, T, T), device="cuda")
+            pal = torch.tensor([(0, 0, 0), (255, 0, 0), (0, 255, 0), (0, 0, 255)], dtype=torch.uint8, device="cuda")
+            pal_l = pal[:C]
+            mask = torch.empty((oh, ow), dtype=torch.uint8, device="cuda")
+            color = torch.empty((oh, ow, 3), dtype=torch.uint8, device="cuda")
+            counts = torch.zeros(8, dtype=torch.int64, device="cuda")
+            full = torch.empty((C, oh, ow), device="cuda")
+
+            def fused():
+                _lib.call("segk_predict_mask", slot.data_ptr(), mask.data_ptr(), color.data_ptr(), pal.data_ptr(), counts.data_ptr(),
+                          None, None, C, T, pt, pl, nh, nw, oh, ow, 0, st)
+
+            def old():
+                _lib.call("segk_crop_resize", slot.data_ptr(), full.data_ptr(), C, T, pt, pl, nh, nw, oh, ow, 0, st)
+                m = full.argmax(0)
+                return m.to(torch.uint8), pal_l[m], torch.bincount(m.flatten(), minlength=C)
+            m_old, c_old, n_old = old()
+            counts.zero_(); fused()
+            same = bool(torch.equal(mask, m_old) and torch.equal(color, c_old) and torch.equal(counts[:C], n_old))
+            iters = 200 if oh * ow < 10 ** 6 else 50
+            tf, to = [], []
+            for _ in range(7):
+                tf.append(timeit(fused, iters)); to.append(timeit(old, iters))
+            tf.sort(); to.sort()
+            P = oh * ow
+            bf, bo = 4, 4 * C + 8 + 1 + 3          # fused: mask + RGB; old: fp32 logits, int64 argmax, uint8 mask, RGB
+            print(f"predict {oh}x{ow} C={C}  fused {tf[3]:8.1f} us [{tf[0]:.1f}..{tf[-1]:.1f}] {bf} B/px {P*bf/tf[3]/1e3:7.1f} GB/s   "
+                  f"replaced {to[3]:8.1f} us [{to[0]:.1f}..{to[-1]:.1f}] {bo} B/px {P*bo/to[3]/1e3:7.1f} GB/s   "
+                  f"{to[3]/tf[3]:5.1f}x   outputs equal: {same}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "predict":
+        predict()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "pack":
         pack()
         sys.exit(0)
