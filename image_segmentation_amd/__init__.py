@@ -9,3 +9,4 @@ from .clipunet import ClipUNet, UNetDecoder, DecoderBlock, ClipViTEncoder       
 from .autoencoder import SegmentationAutoencoder, ReconstructionAutoencoder               # noqa: F401
 from .prompt import PromptModel                                                            # noqa: F401
 from .inference import Segmenter, Prediction, predict, load_checkpoint, COLOR_MAP, CLASS_NAMES   # noqa: F401
+from .prompts import PromptSampler, PromptBatch, PromptBatches, TRIMAP_TO_PROMPT, heat_tables, point_heatmap   # noqa: F401

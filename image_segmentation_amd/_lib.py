@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 312          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 313          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
 
@@ -93,6 +93,9 @@ SIGNATURES = {
     "segk_recon_sigmoid_bwd": (_i, [_fp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_mse_fwd": (_i, [_fp, _fp, _fp, _i, _fp, _l, _i, _vp]),
     "segk_mse_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _l, _i, _vp]),
+    "segk_prompt_scores": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "segk_prompt_make": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _fp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "segk_prompt_heatmap": (_i, [_vp, _i, _vp, _i, _fp, _i, _i, _vp]),
 }
 
 

@@ -44,6 +44,11 @@ int segk_recon_head_fwd_impl(const void*, const float*, const float*, float*, in
 int segk_recon_sigmoid_bwd_impl(const float*, const float*, void*, int, int, int, int, int, int, hipStream_t);
 int segk_mse_fwd_impl(const float*, const float*, float*, int, float*, long, int, hipStream_t);
 int segk_mse_bwd_impl(const float*, const float*, const float*, float*, float*, long, int, hipStream_t);
+int segk_prompt_scores_impl(const long long*, const uint8_t*, const int*, const double*, int, int, double*, int*, int, int, int, int,
+                            hipStream_t);
+int segk_prompt_make_impl(const long long*, const uint8_t*, const int*, const int*, const uint8_t*, int, float*, long long*, int*,
+                          int*, uint8_t*, int, int, int, int, int, hipStream_t);
+int segk_prompt_heatmap_impl(const int*, int, const uint8_t*, int, float*, int, int, hipStream_t);
 
 int segk_clock_probe_impl(unsigned long long*, int, int, int, hipStream_t);
 int segk_debug_poison_tickets_impl(unsigned long long, hipStream_t);
@@ -372,6 +377,20 @@ int segk_mse_fwd(const float* a, const float* b, float* part, int part_floats, f
 int segk_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, long n, int mean,
                  segk_stream_t s) {
   return segk_mse_bwd_impl(a, b, grad_out, da, db, n, mean, (hipStream_t)s);
+}
+// point prompts (utils/augmentation.ipynb, "Prompt Augmentation")
+int segk_prompt_scores(const int64_t* labels, const uint8_t* lut, const int32_t* centers, const double* w, int nw, int R,
+                       double* scores, int32_t* cls, int B, int K, int H, int W, segk_stream_t s) {
+  return segk_prompt_scores_impl((const long long*)labels, lut, centers, w, nw, R, scores, cls, B, K, H, W, (hipStream_t)s);
+}
+int segk_prompt_make(const int64_t* labels, const uint8_t* lut, const int32_t* centers, const int32_t* cls, const uint8_t* q,
+                     int nq, float* heat, int64_t* target, int32_t* classes, int32_t* out_centers, uint8_t* valid, int B, int K,
+                     int per_image, int H, int W, segk_stream_t s) {
+  return segk_prompt_make_impl((const long long*)labels, lut, centers, cls, q, nq, heat, (long long*)target, classes,
+                               out_centers, valid, B, K, per_image, H, W, (hipStream_t)s);
+}
+int segk_prompt_heatmap(const int32_t* points, int P, const uint8_t* q, int nq, float* heat, int H, int W, segk_stream_t s) {
+  return segk_prompt_heatmap_impl(points, P, q, nq, heat, H, W, (hipStream_t)s);
 }
 int segk_confusion(const float* logits, const int64_t* labels, int N, int C, long HW, uint64_t* M, segk_stream_t s) {
   return segk_confusion_impl(logits, (const long long*)labels, N, C, HW, (unsigned long long*)M, (hipStream_t)s);

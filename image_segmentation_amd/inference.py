@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, prompts
 from . import utils as U
 
 # app.py:187-208 -- the demo's palette and the two class-name tables
@@ -128,10 +128,17 @@ class Segmenter:
     images    list of float [C,H,W] tensors (the contract of process_batch_forward) or uint8 [H,W,C] tensors / NumPy
               arrays, on the host or the device, of any sizes
     heatmaps  for two-input models (PromptModel.forward(x, heatmap)): one float [1,H,W] or uint8 [H,W] / [H,W,1] per image
+    points    instead of heatmaps: per image one click (y, x) or a list of clicks, in the image's own pixels; the heat-map
+              (the 8-bit Gaussian of the training data, sigma as given to the constructor; several clicks: the maximum of
+              theirs) is made on the device by segk_prompt_heatmap and takes the route of a float heat-map
     labels    optional integer [H,W] / [1,H,W] maps at the images' own sizes: the confusion counts come from the same pass
               (labels outside [0,C) are skipped, as the eval loops skip 255 / ignore)"""
 
-    def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None):
+    def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
+                 sigma=3.0):
+        if not float(sigma) > 0:
+            raise ValueError(f"sigma must be positive, got {sigma}")
+        self.sigma = float(sigma)
         if interpolation not in (U.BILINEAR, U.NEAREST):
             raise ValueError(f"interpolation: '{U.BILINEAR}' or '{U.NEAREST}', got {interpolation!r}")
         if int(batch_size) < 1 or int(target_size) < 1:
@@ -153,11 +160,20 @@ class Segmenter:
             self._palette_dev[dev] = self._palette.to(dev)
         return self._palette_dev[dev]
 
-    def __call__(self, images, heatmaps=None, labels=None):
+    def __call__(self, images, heatmaps=None, labels=None, points=None):
         images = [_as_tensor(im) for im in images]
         n = len(images)
-        if self._two_input and heatmaps is None:
-            raise ValueError("this model takes (image, heatmap): pass heatmaps=")
+        if points is not None:
+            if heatmaps is not None:
+                raise ValueError("pass either heatmaps or points, not both")
+            if not self._two_input:
+                raise ValueError("points were given to a model whose forward takes the image alone")
+            if len(points) != n:
+                raise ValueError(f"{len(points)} point sets for {n} images")
+            sizes = [tuple(im.shape[:2]) if im.dtype == torch.uint8 else tuple(im.shape[-2:]) for im in images]
+            points = [prompts._points_array(p, H, W, f"points[{k}]") for k, (p, (H, W)) in enumerate(zip(points, sizes))]
+        if self._two_input and heatmaps is None and points is None:
+            raise ValueError("this model takes (image, heatmap): pass heatmaps= or points=")
         if not self._two_input and heatmaps is not None:
             raise ValueError("heatmaps were given to a model whose forward takes the image alone")
         if heatmaps is not None and len(heatmaps) != n:
@@ -176,8 +192,11 @@ class Segmenter:
             with torch.no_grad(), torch.cuda.device(dev):
                 for i in range(0, n, self.batch_size):
                     j = min(i + self.batch_size, n)
-                    out += self._chunk(dev, images[i:j], None if heatmaps is None else heatmaps[i:j],
-                                       None if labels is None else labels[i:j])
+                    hm = None if heatmaps is None else heatmaps[i:j]
+                    if points is not None:      # click(s) -> heat-map on the device, at the image's own size
+                        hm = [prompts._heatmap_on(torch.from_numpy(p).to(dev, non_blocking=True), *sizes[i + k], self.sigma, dev)
+                              for k, p in enumerate(points[i:j])]
+                    out += self._chunk(dev, images[i:j], hm, None if labels is None else labels[i:j])
         finally:
             for m, was in modes:
                 m.training = was
@@ -230,6 +249,6 @@ class Segmenter:
         return preds
 
 
-def predict(model, images, heatmaps=None, labels=None, **kw):
-    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels)."""
-    return Segmenter(model, **kw)(images, heatmaps=heatmaps, labels=labels)
+def predict(model, images, heatmaps=None, labels=None, points=None, **kw):
+    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels, points)."""
+    return Segmenter(model, **kw)(images, heatmaps=heatmaps, labels=labels, points=points)

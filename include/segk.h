@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 312
-#define SEGK_ENTRY_COUNT 75
+#define SEGK_ABI_VERSION 313
+#define SEGK_ENTRY_COUNT 78
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -327,6 +327,32 @@ int segk_prob_loss_fwd(const float* probs, const int64_t* labels, const float* c
 int segk_prob_loss_bwd(const float* probs, const int64_t* labels, const float* class_weights, const float* state,
                        const float* grad_out, int N, int C, long HW, int ignore_index, float dice_weight,
                        float nll_weight, int nll_log, float eps, float* dprobs, segk_stream_t s);
+
+/* ---- point prompts (utils/augmentation.ipynb, cell "Prompt Augmentation": create_gaussian_heatmap, select_dominant_class
+ * and the retry loop; prompt_based/prompt.py reads what that cell wrote) ----------------------------------------------------
+ * Two host-built tables carry every value that decides a result, indexed by the integer squared distance d2 = dy*dy + dx*dx:
+ * w[d2] = exp(-d2 / (2 sigma^2)) in float64 (nw entries) and q[d2] = (uint8)(255 * w[d2]) (nq entries, the non-zero head).
+ * labels int64 [B,H,W]; lut (may be NULL): uint8[256] applied to the labels first -- labels outside 0..255 and table results
+ * >= SEGK_MAX_CLASSES count as class 0; without a table the labels are the classes.  H, W <= 32768.  Centres, classes and
+ * points are device data: a centre outside the image scores nothing, gets class 0, is never taken and makes no heat; every
+ * table index is bounded by nw / nq.
+ *
+ * scores[B,K,8] float64 = per-class sums of w over the window |dy|, |dx| <= R around centers[B,K,2] (int32, y then x) clipped
+ * to the image, summed in a fixed order; cls[B,K] int32 = the class 1..7 with the largest sum (the lowest on a tie), 0 when
+ * every sum is < 1e-9 (select_dominant_class). */
+int segk_prompt_scores(const int64_t* labels, const uint8_t* lut, const int32_t* centers, const double* w, int nw, int R,
+                       double* scores, int32_t* cls, int B, int K, int H, int W, segk_stream_t s);
+/* the retry loop and the files it writes: per image, candidate k is taken if cls[b][k] is non-zero and not taken yet, until
+ * per_image (1..7) are taken.  For the j-th taken candidate: heat[B,per_image,1,H,W] fp32 = (float)q[d2] / 255.0f (0 beyond
+ * nq), target[B,per_image,H,W] int64 = label == class ? class : 0, classes[B,per_image] int32, out_centers[B,per_image,2]
+ * int32, valid[B] uint8 = 1.  An image with fewer distinct classes gets valid = 0 and zeros everywhere (the reference skips
+ * it).  H*W % 4 == 0 takes the 16-byte path (labels, heat, target 16-byte aligned). */
+int segk_prompt_make(const int64_t* labels, const uint8_t* lut, const int32_t* centers, const int32_t* cls, const uint8_t* q,
+                     int nq, float* heat, int64_t* target, int32_t* classes, int32_t* out_centers, uint8_t* valid, int B, int K,
+                     int per_image, int H, int W, segk_stream_t s);
+/* prediction side: P points [P,2] (int32, y then x; 1 <= P <= 1024) -> heat[1,H,W] fp32 = (float)q[min over the points of
+ * d2] / 255.0f, the maximum of the points' Gaussians; one point gives the training form */
+int segk_prompt_heatmap(const int32_t* points, int P, const uint8_t* q, int nq, float* heat, int H, int W, segk_stream_t s);
 
 /* ---- reconstruction head and MSE loss (autoencoder/autoencoder.py:188-191; nn.MSELoss as autoencoder.ipynb cell 0
  * constructs it and utils/training.py:141,234 call it) ---------------------------------------------------------------

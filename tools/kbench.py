@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -345,7 +345,97 @@ def predict():
                   f"{to[3]/tf[3]:5.1f}x   outputs equal: {same}")
 
 
+def prompt():
+    """Point prompts through the C ABI (csrc/prompt.hip): device-event times of the two launches of PromptSampler -- the score
+    pass over K candidate windows per image and the make pass that writes heat-maps and targets -- at B = 32, 256 x 256 and
+    B = 8, 512 x 512 for K = 64, 256, 1000 (warmed, 100 repetitions per round, seven rounds: median and min..max), the make
+    kernel's bytes/s from its byte count (8 B read + 12 B x per_image written per pixel), the whole sampler call, and beside
+    them the HOST time of the route it replaces, written out in NumPy as the reference's cell computes it (whole-image
+    Gaussian per draw, per-class sums, retry loop; one thread, same label maps).  Also written to
+    profiles/prompt_points.json (or the file given with --out)."""
+    import json, time
+    import numpy as np
+    from image_segmentation_amd import prompts
+    st = ops._stream()
+    PI, sigma = 2, 3.0
+    rows = []
+
+    def host_route(maps, max_attempts=1000):
+        rng = np.random.RandomState(0)
+        t0 = time.perf_counter()
+        done = 0
+        for m in maps:
+            H, W = m.shape
+            present = np.unique(m)
+            if len(present[present > 0]) < 2:
+                continue
+            yy, xx = np.indices((H, W))
+            found, attempts = [], 0
+            while len(found) < 2 and attempts < max_attempts:
+                attempts += 1
+                cy, cx = rng.randint(0, H), rng.randint(0, W)
+                heat = np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2 * sigma ** 2))
+                sc = {c: heat[m == c].sum() for c in present[present > 0]}
+                best = 0 if all(v < 1e-9 for v in sc.values()) else max(sc, key=sc.get)
+                if best > 0 and best not in found:
+                    found.append(best)
+                    _ = (heat * 255).astype(np.uint8), np.where(m == best, best, 0).astype(np.uint8)
+            done += 1
+        return done / (time.perf_counter() - t0)
+
+    for B, S in ((32, 256), (8, 512)):
+        blocks = torch.randint(1, 4, (B, S // 32, S // 32), device="cuda")
+        lab = blocks.repeat_interleave(32, 1).repeat_interleave(32, 2).contiguous()           # blocky class regions 1..3
+        wt, nw, qt, nq, R = prompts._tables_on(sigma, S, S, lab.device)
+        host_ips = host_route(list(lab.cpu().numpy()))
+        for K in (64, 256, 1000):
+            cen = torch.stack((torch.randint(0, S, (B, K), device="cuda", dtype=torch.int32),
+                               torch.randint(0, S, (B, K), device="cuda", dtype=torch.int32)), -1).contiguous()
+            scores = torch.empty((B, K, 8), dtype=torch.float64, device="cuda")
+            cls = torch.empty((B, K), dtype=torch.int32, device="cuda")
+            heat = torch.empty((B, PI, 1, S, S), device="cuda")
+            tgt = torch.empty((B, PI, S, S), dtype=torch.int64, device="cuda")
+            classes = torch.empty((B, PI), dtype=torch.int32, device="cuda")
+            oc = torch.empty((B, PI, 2), dtype=torch.int32, device="cuda")
+            valid = torch.empty((B,), dtype=torch.bool, device="cuda")
+            f_sc = lambda: _lib.call("segk_prompt_scores", lab.data_ptr(), 0, cen.data_ptr(), wt.data_ptr(), nw, R,
+                                     scores.data_ptr(), cls.data_ptr(), B, K, S, S, st)
+            f_mk = lambda: _lib.call("segk_prompt_make", lab.data_ptr(), 0, cen.data_ptr(), cls.data_ptr(), qt.data_ptr(), nq,
+                                     heat.data_ptr(), tgt.data_ptr(), classes.data_ptr(), oc.data_ptr(), valid.data_ptr(), B, K,
+                                     PI, S, S, st)
+            sampler = prompts.PromptSampler(sigma=sigma, candidates=K, per_image=PI, seed=0)
+            f_all = lambda: sampler(lab)
+            f_sc(); f_mk(); f_all()
+            ts, tm, ta = [], [], []
+            for _ in range(7):
+                ts.append(timeit(f_sc, 100)); tm.append(timeit(f_mk, 100)); ta.append(timeit(f_all, 100))
+            ts.sort(); tm.sort(); ta.sort()
+            nbytes = B * S * S * (8 + 12 * PI)
+            row = {"B": B, "size": S, "K": K, "R": R, "valid_images": int(valid.sum()),
+                   "scores_us": {"median": ts[3], "min": ts[0], "max": ts[-1]},
+                   "make_us": {"median": tm[3], "min": tm[0], "max": tm[-1]}, "make_bytes": nbytes,
+                   "make_GBps": nbytes / tm[3] / 1e3,
+                   "sampler_call_us": {"median": ta[3], "min": ta[0], "max": ta[-1]},
+                   "host_numpy_route_images_per_s": host_ips, "device_images_per_s": B / (ta[3] * 1e-6)}
+            rows.append(row)
+            print(f"prompt B={B} {S}x{S} K={K:4d} R={R}  scores {ts[3]:8.1f} us [{ts[0]:.1f}..{ts[-1]:.1f}]   make {tm[3]:7.1f} us "
+                  f"[{tm[0]:.1f}..{tm[-1]:.1f}] {nbytes / tm[3] / 1e3:7.1f} GB/s   sampler call (draw + 2 launches) {ta[3]:8.1f} us "
+                  f"[{ta[0]:.1f}..{ta[-1]:.1f}] = {B / (ta[3] * 1e-6):9.0f} images/s   host NumPy route {host_ips:7.1f} images/s "
+                  f"(host time, one thread)")
+    clk = ops.clock_probe()
+    out = {"rows": rows, "clock_probe_ghz": clk["median_ghz"], "build_id": _lib.build_id(), "per_image": PI, "sigma": sigma}
+    path = os.path.join(ROOT, "profiles", "prompt_points.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print(f"prompt clock probe: median {clk['median_ghz']} GHz; written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "prompt":
+        prompt()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "predict":
         predict()
         sys.exit(0)

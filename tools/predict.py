@@ -2,8 +2,10 @@
 """Segment image files with a trained checkpoint: a thin shell over image_segmentation_amd.Segmenter (the prediction path
 of the reference's demo service, segmentation_webapp/app.py:250-326, without the web part).  For every IMG it writes
 DIR/<name>_mask.png (8-bit class indices) and, while the palette covers the classes, DIR/<name>_color.png (RGB).
-Usage: python tools/predict.py --model {unet,autoencoder} --checkpoint F --classes 4 --size 224 --out DIR IMG...
-(models that need the hub to construct -- ClipUNet, PromptModel -- are driven from the library: Segmenter(model))"""
+Usage: python tools/predict.py --model {unet,autoencoder,prompt} --checkpoint F --classes 4 --size 224 --out DIR IMG...
+--model prompt is the prompt model (a ViT-B/16 ClipUNet built from its configuration, no hub access: every weight comes
+from the checkpoint of the whole PromptModel) and needs --point Y,X (repeatable; the clicks apply to every image).  A ClipUNet
+alone is driven from the library: Segmenter(model)."""
 import argparse
 import os
 import sys
@@ -14,7 +16,11 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--model", choices=["unet", "autoencoder"], default="unet")
+    ap.add_argument("--model", choices=["unet", "autoencoder", "prompt"], default="unet")
+    ap.add_argument("--point", action="append", default=[], metavar="Y,X",
+                    help="a click in image pixels for --model prompt; repeat for several (the heat-map is the maximum of "
+                         "their Gaussians); applies to every image")
+    ap.add_argument("--sigma", type=float, default=3.0, help="spread of the click heat-map, as in training")
     ap.add_argument("--checkpoint", required=True, help="{'model_state_dict': ...}, {'state_dict': ...} or a bare state dict")
     ap.add_argument("--classes", type=int, default=4)
     ap.add_argument("--size", type=int, default=224, help="side of the square network input")
@@ -23,6 +29,14 @@ def main():
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("images", nargs="+", metavar="IMG")
     args = ap.parse_args()
+    try:
+        clicks = [tuple(int(v) for v in p.split(",")) for p in args.point]
+        if any(len(c) != 2 for c in clicks):
+            raise ValueError
+    except ValueError:
+        ap.error("--point takes Y,X (two integers)")
+    if (args.model == "prompt") != bool(clicks):
+        ap.error("--model prompt needs --point Y,X, and --point needs --model prompt")
 
     import numpy as np
     from PIL import Image
@@ -30,17 +44,22 @@ def main():
 
     if args.model == "unet":
         model = seg.unet(3, args.classes)
+    elif args.model == "prompt":
+        if args.classes != 4:
+            ap.error("the prompt model has 4 classes")
+        model = seg.PromptModel(clip=seg.ClipUNet(num_classes=4, encoder=seg.ClipViTEncoder.from_config()))
     else:
         model = seg.SegmentationAutoencoder(3, num_classes=args.classes)
     model = seg.load_checkpoint(model, args.checkpoint).cuda()
     palette = seg.COLOR_MAP if args.classes <= len(seg.COLOR_MAP) else None
     segmenter = seg.Segmenter(model, target_size=args.size, interpolation=args.interpolation, palette=palette,
-                              batch_size=args.batch_size)
+                              batch_size=args.batch_size, sigma=args.sigma)
     os.makedirs(args.out, exist_ok=True)
-    names = seg.CLASS_NAMES["standard"]
+    names = seg.CLASS_NAMES["prompt_model" if clicks else "standard"]
     for i in range(0, len(args.images), args.batch_size):
         paths = args.images[i:i + args.batch_size]
-        preds = segmenter([np.asarray(Image.open(p).convert("RGB")) for p in paths])
+        preds = segmenter([np.asarray(Image.open(p).convert("RGB")) for p in paths],
+                          points=[clicks] * len(paths) if clicks else None)
         for p, pred in zip(paths, preds):
             stem = os.path.join(args.out, os.path.splitext(os.path.basename(p))[0])
             Image.fromarray(pred.mask.cpu().numpy(), "L").save(stem + "_mask.png")
