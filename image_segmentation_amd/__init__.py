@@ -10,3 +10,5 @@ from .autoencoder import SegmentationAutoencoder, ReconstructionAutoencoder     
 from .prompt import PromptModel                                                            # noqa: F401
 from .inference import Segmenter, Prediction, predict, load_checkpoint, COLOR_MAP, CLASS_NAMES   # noqa: F401
 from .prompts import PromptSampler, PromptBatch, PromptBatches, TRIMAP_TO_PROMPT, heat_tables, point_heatmap   # noqa: F401
+from .augment import (Augmenter, AugPlan, AugmentedBatches, merge_pairs, class_weights, convert_rgb_label_to_classes,   # noqa: F401
+                      cubic_table, contrast_lut, laplace_table, rotation_plan, merge_plan, ALL_OPS, TARGET_REMAP)

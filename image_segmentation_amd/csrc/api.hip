@@ -50,6 +50,13 @@ int segk_prompt_make_impl(const long long*, const uint8_t*, const int*, const in
                           int*, uint8_t*, int, int, int, int, int, hipStream_t);
 int segk_prompt_heatmap_impl(const int*, int, const uint8_t*, int, float*, int, int, hipStream_t);
 
+int segk_aug_prefilter_impl(const segk_aug_desc*, int, int, hipStream_t);
+int segk_aug_resample_impl(const segk_aug_desc*, int, int, const int32_t*, const int16_t*, int, const uint8_t*, int, const int16_t*, int,
+                           const uint8_t*, float*, uint8_t*, long long*, hipStream_t);
+int segk_aug_merge_impl(const segk_merge_desc*, const int32_t*, int, int, const uint8_t*, float*, uint8_t*, long long*, hipStream_t);
+int segk_label_hist_impl(const void*, long, int, int, int, long, unsigned long long*, hipStream_t);
+int segk_rgb_label_to_classes_impl(const uint8_t*, uint8_t*, long, hipStream_t);
+
 int segk_clock_probe_impl(unsigned long long*, int, int, int, hipStream_t);
 int segk_debug_poison_tickets_impl(unsigned long long, hipStream_t);
 
@@ -391,6 +398,29 @@ int segk_prompt_make(const int64_t* labels, const uint8_t* lut, const int32_t* c
 }
 int segk_prompt_heatmap(const int32_t* points, int P, const uint8_t* q, int nq, float* heat, int H, int W, segk_stream_t s) {
   return segk_prompt_heatmap_impl(points, P, q, nq, heat, H, W, (hipStream_t)s);
+}
+// training augmentation (utils/augmentation.ipynb: the eight augmenters + "pad to square, resize"; cell 17)
+int segk_aug_prefilter(const segk_aug_desc* descs, int n, int max_tiles, segk_stream_t s) {
+  return segk_aug_prefilter_impl(descs, n, max_tiles, (hipStream_t)s);
+}
+int segk_aug_resample(const segk_aug_desc* descs, int n, int T, const int32_t* cub_idx, const int16_t* cub_coef, int n_cub,
+                      const uint8_t* contrast, int n_contrast, const int16_t* laplace, int n_laplace, const uint8_t* label_lut,
+                      float* X, uint8_t* X8, int64_t* y, segk_stream_t s) {
+  return segk_aug_resample_impl(descs, n, T, cub_idx, cub_coef, n_cub, contrast, n_contrast, laplace, n_laplace, label_lut, X,
+                                X8, (long long*)y, (hipStream_t)s);
+}
+int segk_aug_merge(const segk_merge_desc* descs, const int32_t* tables, int n, int T, const uint8_t* label_lut, float* X,
+                   uint8_t* X8, int64_t* y, segk_stream_t s) {
+  return segk_aug_merge_impl(descs, tables, n, T, label_lut, X, X8, (long long*)y, (hipStream_t)s);
+}
+// utils/utils.py:166-177 (the counting loop of calculate_class_weights) and :201-250 (convert_rgb_label_to_classes)
+int segk_label_hist(const void* labels, long n, int elem_bytes, int num_classes, int has_ignore, long ignore_index,
+                    uint64_t* counts, segk_stream_t s) {
+  return segk_label_hist_impl(labels, n, elem_bytes, num_classes, has_ignore, ignore_index, (unsigned long long*)counts,
+                              (hipStream_t)s);
+}
+int segk_rgb_label_to_classes(const uint8_t* rgb, uint8_t* out, long n, segk_stream_t s) {
+  return segk_rgb_label_to_classes_impl(rgb, out, n, (hipStream_t)s);
 }
 int segk_confusion(const float* logits, const int64_t* labels, int N, int C, long HW, uint64_t* M, segk_stream_t s) {
   return segk_confusion_impl(logits, (const long long*)labels, N, C, HW, (unsigned long long*)M, (hipStream_t)s);

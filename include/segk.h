@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 313
-#define SEGK_ENTRY_COUNT 78
+#define SEGK_ABI_VERSION 314
+#define SEGK_ENTRY_COUNT 83
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -353,6 +353,71 @@ int segk_prompt_make(const int64_t* labels, const uint8_t* lut, const int32_t* c
 /* prediction side: P points [P,2] (int32, y then x; 1 <= P <= 1024) -> heat[1,H,W] fp32 = (float)q[min over the points of
  * d2] / 255.0f, the maximum of the points' Gaussians; one point gives the training form */
 int segk_prompt_heatmap(const int32_t* points, int P, const uint8_t* q, int nq, float* heat, int H, int W, segk_stream_t s);
+
+/* ---- training augmentation and dataset preparation (utils/augmentation.ipynb: the eight imgaug augmenters, each followed by
+ * "pad to square, resize to 256"; cell 17 combine_images_preserve_aspect_ratio; utils/utils.py:201-250
+ * convert_rgb_label_to_classes; utils/utils.py:117-198 calculate_class_weights) ------------------------------------------------
+ * All arithmetic is integer and every deciding value comes from a host-built table, so results are bit-stable; the exact
+ * definition is DESIGN.md 3 (and, as NumPy, tests/augment_reference.py).  One launch serves a whole batch of differently sized
+ * samples through a descriptor table in DEVICE memory; the entry points cannot see it, so the kernels clamp every coordinate to
+ * its buffer and every table row to the table length, and treat an unknown op as SEGK_AUG_RESIZE.  Sides are 1..8192. */
+#define SEGK_AUG_RESIZE 0
+#define SEGK_AUG_CENTER_CROP 1
+#define SEGK_AUG_RANDOM_CROP 2
+#define SEGK_AUG_ROTATION 3      /* stage A: bilinear (image) / nearest (label) gather through the Q16 inverse map A */
+#define SEGK_AUG_MASKING 4       /* CoarseDropout: cell grid gh x gw, a cell is dropped by the hash of (seed, cell) */
+#define SEGK_AUG_GRAYSCALE 5
+#define SEGK_AUG_LAPLACE 6       /* per-element noise: row `aux` of the Laplace tables, indexed by the hash of (seed, element) */
+#define SEGK_AUG_BLUR 7          /* stage A: 12 x 12 box, reflect-101 borders, image only */
+#define SEGK_AUG_CONTRAST 8      /* row `aux` of the contrast tables */
+#define SEGK_AUG_LAPLACE_ENTRIES 4096
+typedef struct segk_aug_desc {   /* one sample; 160 bytes */
+  const uint8_t* img;            /* source image uint8 [H][W][img_c], img_c 3 | 4 (the fourth channel is ignored) */
+  const uint8_t* lab;            /* source label uint8 [H][W][lab_c], lab_c 1 (class ids / trimap) | 3 (colour), or NULL */
+  uint8_t* a_img;                /* stage-A image [Ha][Wa][3] in caller scratch (rotation, blur), else NULL */
+  uint8_t* a_lab;                /* stage-A label [Ha][Wa], colour labels already as classes (rotation), else NULL */
+  int64_t A[6];                  /* rotation: SX = A[0] x + A[1] y + A[2], SY = A[3] x + A[4] y + A[5], Q16 */
+  uint64_t seed;                 /* per-image seed of the hash (masking, Laplace) */
+  int32_t H, W, img_c, lab_c;
+  int32_t Ha, Wa;                /* stage-A output size */
+  int32_t op;                    /* SEGK_AUG_* */
+  int32_t wy, wx, wh, ww;        /* window of stage B in its input (stage-A output if there is one, else the source) */
+  int32_t tab, aux;              /* row of the cubic tables (the one built for S = max(wh, ww)); row of the op's own table */
+  int32_t gh, gw;                /* masking grid */
+  int32_t label_fill;            /* rotation: label value outside the source */
+  int32_t pad_[2];
+} segk_aug_desc;
+/* stage A for `n` samples (only those that have one need to be in the table): a_img (and a_lab) of each are written.
+ * max_tiles = the largest ceil(Ha/16) * ceil(Wa/16) of the table.  Rotation: image (sum of w p + 32768) >> 16 with the four
+ * integer weights of the 8-bit fractions (SX >> 8) & 255, taps outside the source read 0; label (SX + 32768) >> 16, outside
+ * label_fill.  Blur: (sum of rows y-6..y+5, columns x-6..x+5 + 72) / 144. */
+int segk_aug_prefilter(const segk_aug_desc* descs, int n, int max_tiles, segk_stream_t s);
+/* stage B for `n` samples: window -> pointwise op on every tap -> pad to the square S = max(wh, ww) (centred, 0) -> resize to
+ * T x T.  Image: separable cubic from cub_idx int32 [n_cub][T] (floor of the source coordinate) and cub_coef int16
+ * [n_cub][T][4] (rows sum to 2048), clamp((sum_r c[r] sum_c c[c] p + 2^21) >> 22, 0, 255), written as X fp32 [n,3,T,T] = u8 /
+ * 255.0f (utils/dataset.py:39) and / or X8 uint8 [n,T,T,3] (either may be NULL, not both).  Label: nearest (dst S) / T, the
+ * colour -> class map, then label_lut uint8[256] (may be NULL) -> y int64 [n,1,T,T] (may be NULL).  contrast uint8
+ * [n_contrast][256], laplace int16 [n_laplace][4096]. */
+int segk_aug_resample(const segk_aug_desc* descs, int n, int T, const int32_t* cub_idx, const int16_t* cub_coef, int n_cub,
+                      const uint8_t* contrast, int n_contrast, const int16_t* laplace, int n_laplace, const uint8_t* label_lut,
+                      float* X, uint8_t* X8, int64_t* y, segk_stream_t s);
+typedef struct segk_merge_desc { /* one pair; 64 bytes */
+  const uint8_t* img[2];         /* uint8 [H][W][img_c] */
+  const uint8_t* lab[2];         /* uint8 [H][W][lab_c]; a one-channel label counts as grey RGB (cell 17 loads RGB); or NULL */
+  int32_t H[2], W[2], img_c[2], lab_c[2];
+} segk_merge_desc;
+/* cell 17 for `n` pairs: tables int32 [n][4][T] = source row of image 0 per canvas row, source column of image 0 per canvas
+ * column, the same two for image 1 (-1: none); image 1 is pasted over image 0, the rest of the canvas is 0.  Outputs as
+ * segk_aug_resample; the label canvas goes through the colour -> class map, then label_lut. */
+int segk_aug_merge(const segk_merge_desc* descs, const int32_t* tables, int n, int T, const uint8_t* label_lut, float* X,
+                   uint8_t* X8, int64_t* y, segk_stream_t s);
+/* utils.py:166-177: counts[c] += number of labels with clamp(label, 0, num_classes - 1) == c among those != ignore_index (when
+ * has_ignore).  labels: n elements of elem_bytes 1 (uint8) or 8 (int64); counts uint64 [num_classes <= 256], caller-zeroed,
+ * accumulates across calls; integer sums, so the result does not depend on the order. */
+int segk_label_hist(const void* labels, long n, int elem_bytes, int num_classes, int has_ignore, long ignore_index,
+                    uint64_t* counts, segk_stream_t s);
+/* utils.py:201-250: rgb uint8 [n][3] -> out uint8 [n]: black or white 0, (128,0,0) 1, (0,128,0) 2, else 255 */
+int segk_rgb_label_to_classes(const uint8_t* rgb, uint8_t* out, long n, segk_stream_t s);
 
 /* ---- reconstruction head and MSE loss (autoencoder/autoencoder.py:188-191; nn.MSELoss as autoencoder.ipynb cell 0
  * constructs it and utils/training.py:141,234 call it) ---------------------------------------------------------------

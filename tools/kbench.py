@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -432,7 +432,56 @@ def prompt():
     print(f"prompt clock probe: median {clk['median_ghz']} GHz; written to {path}")
 
 
+def augment():
+    """Device-side augmentation through the C ABI (csrc/augment.hip): B = 32 sources of 375 x 500 (uint8 RGB + a one-channel
+    label) -> 256 x 256, for plain resize, each of the eight ops and the mixed default.  Per row: device-event time of the
+    batch's launches replayed alone (prefilter + resample; warmed, 50 repetitions per round, seven rounds: median and
+    min..max), GB/s over the algorithmic bytes (every source read once + X fp32 and y int64 written), the fraction of the
+    6.29 TB/s copy ceiling, and the whole Augmenter.apply call (host table work + one pinned upload + the launches).  Also
+    written to profiles/kbench_augment.json (or the file given with --out)."""
+    import json
+    import numpy as np
+    from image_segmentation_amd import augment as A
+    B, H, W, T, COPY = 32, 375, 500, 256, 6.29e12
+    g = torch.Generator(device="cuda").manual_seed(0)
+    imgs = [torch.randint(0, 256, (H, W, 3), generator=g, device="cuda", dtype=torch.uint8) for _ in range(B)]
+    labs = [torch.randint(0, 3, (H, W), generator=g, device="cuda", dtype=torch.uint8) for _ in range(B)]
+    nbytes = B * (H * W * 4 + T * T * (12 + 8))
+    rows = []
+    for name, ops_ in [(A.OP_NAMES[o], (o,)) for o in range(9)] + [("mixed", A.ALL_OPS)]:
+        aug = A.Augmenter(target_size=T, ops=ops_, label_lut=A.TARGET_REMAP, seed=0)
+        plans = aug.plan([(H, W)] * B)
+        out = aug.apply(imgs, labs, plans)
+        launches = list(aug.last_launches)
+        f_k = lambda: [_lib.call(n, *a) for n, a in launches]
+        f_all = lambda: aug.apply(imgs, labs, plans)
+        tk, ta = [], []
+        for _ in range(7):
+            tk.append(timeit(f_k, 50)); ta.append(timeit(f_all, 50))
+        tk.sort(); ta.sort()
+        row = {"op": name, "launches": [n for n, _ in launches], "kernels_us": {"median": tk[3], "min": tk[0], "max": tk[-1]},
+               "apply_call_us": {"median": ta[3], "min": ta[0], "max": ta[-1]}, "bytes": nbytes,
+               "GBps": nbytes / tk[3] / 1e3, "copy_ceiling_fraction": nbytes / (tk[3] * 1e-6) / COPY,
+               "images_per_s_call": B / (ta[3] * 1e-6)}
+        rows.append(row)
+        print(f"augment {name:12s} B={B} {H}x{W}->{T}  kernels {tk[3]:8.1f} us [{tk[0]:.1f}..{tk[-1]:.1f}] {row['GBps']:7.1f} GB/s "
+              f"= {100 * row['copy_ceiling_fraction']:5.2f} % of the copy ceiling   apply() call {ta[3]:8.1f} us "
+              f"[{ta[0]:.1f}..{ta[-1]:.1f}] = {row['images_per_s_call']:8.0f} images/s   ({' + '.join(row['launches'])})")
+        del out
+    clk = ops.clock_probe()
+    res = {"rows": rows, "clock_probe_ghz": clk["median_ghz"], "build_id": _lib.build_id(), "B": B, "source": [H, W], "T": T}
+    path = os.path.join(ROOT, "profiles", "kbench_augment.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(f"augment clock probe: median {clk['median_ghz']} GHz; written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "augment":
+        augment()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "prompt":
         prompt()
         sys.exit(0)
