@@ -404,7 +404,9 @@ __device__ __forceinline__ void loss_finalize_block(const float* __restrict__ pa
     const bool valid = !(ignore_index >= 0 && ignore_index < C && k == ignore_index);
     state[4 + 2 * MAXC + k] = valid ? (float)((cw ? (double)cw[k] : 1.0) / wsum) : 0.f;
   }
-  state[0] = (float)((double)dice_weight * dice + (double)ce_weight * ce);
+  // ce_weight == 0: the Dice-only losses, which have no CrossEntropy term -- a NaN ce (no pixel counts: every label is the
+  // ignored class, or every class weight present is zero) must not reach them through 0 * NaN
+  state[0] = (float)((double)dice_weight * dice + (ce_weight != 0.f ? (double)ce_weight * ce : 0.0));
   if (loss_out) *loss_out = state[0];
   state[1] = (float)ce;
   state[2] = (float)dice;
@@ -547,7 +549,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
       m = fmaxf(m, l[k]);
     }
     const long long y = labels[p];
-    const bool ce_valid = (y >= 0 && y < C && y != ignore_index);
+    const bool ce_valid = (ce_weight != 0.f && y >= 0 && y < C && y != ignore_index);   // no term, no 0 / 0 weight
     float wy = 0.f;
     if (ce_valid) wy = (cw ? cw[y] : 1.f) / ce_den;
     if constexpr (PROB) {   // d/dx of  dice(x) + nll(log(x + eps) | x)

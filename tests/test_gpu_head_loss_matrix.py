@@ -1,0 +1,385 @@
+"""GPU (-m gpu): every kernel of csrc/head_loss.hip through the C ABI against float64 (tests/loss_reference.py), at every class
+count 1..8 -- the kernels are compiled per class count (head 2 / 3 / 4 / 8, loss 2 / 4 / 8) and C = 1, 5, 6, 7 run the
+"clamped class index, selected afterwards" loads -- and at pixel counts chosen from the launch arithmetic rather than from the
+models.  Outputs and partial buffers are NaN-filled with guard elements behind them, so an unwritten or over-written element shows.
+
+Loss (loss_fwd_kernel: blocks = ceil(P / 4096) capped at 256, 1024 threads, four pixels in flight per thread; loss_bwd_kernel:
+256-thread blocks capped at 4096), as N x HW so that the host side stays cheap:
+  1 x 1          one pixel
+  2 x 240        the shape of tests/golden/losses_small.npz: one block, more than half of it idle
+  64 x 64        4096: one full block, every thread runs the main loop exactly once
+  241 x 17       4097: two blocks, remainder loop only
+  400 x 35       14 000 pixels in 35-pixel images: split_hw crosses images inside a block
+  1000 x 123, 1024 x 128, 1311 x 100     31 / 32 / 33 partial rows (loss_finalize_block reads rows in groups of 32)
+  1044 x 1000, 1045 x 1000               255 / 256 rows (the cap; clamped-row loads); at 1 045 000 only threads below 258 568
+                                         enter the four-in-flight loop
+  1000 x 1050    just above 256 * 4096: every thread runs the main loop once, 1424 threads one remainder pass; the backward
+                 kernel strides its grid (C = 2, 5, 8)
+  3001 x 1000    two main-loop passes, a third for some threads, a remainder, three backward passes (C = 2, 5, 8)
+Up to 131 100 pixels the inputs are dense (logits in [-3, 3], uniform labels); above, one pixel in 64 is such a foreground pixel
+and the rest is confident background -- an fp32 sum over a million dense terms cannot resolve one pixel, and the floors below
+could not hold.  The options (class weights none / some / one zero; ignore_index none / inside / 255 with such labels / -100
+labels; smooth 0 / 1e-5 / 1; dice and ce weights (1, 0) / (0, 1) / (0.7, 1.3); upstream gradient 1 / 0.5; nll_log 0 / 1) walk
+through the cells with strides of their own (loss_reference.loss_case).
+
+Every non-degenerate cell asserts two floors on its OWN bounds, from the reference alone: the allowed loss error is below what
+removing the most visible single pixel from the sums changes, and the allowed gradient error is below 1e-3 of the largest
+gradient.  Unweighted pixel counts (state[3]) must be exact, which catches a dropped or doubled pixel at any size.
+
+Head (head_fwd_kernel: 256-pixel tiles, grid capped at 4096; head_bwd_kernel: blocks = ceil(P / 32) capped at 1024, rows =
+256 / min(Cp / 4, 64) pixel rows per block, two pixels in flight): ncls 1..8, both dtypes, Cp 32 / 64 / 96 / 288 / 512 with three
+channels fewer than the padding, P = 1, 5 (fewer than rows), 255 / 256 / 257; 400 x 35 at Cp = 256 (one backward step spans 50
+images: advance() walks); 70 000 pixels at Cp 32 and 96 (main loop plus tail at 32 rows); 1021 x 1029 at Cp = 32, ncls 2 and 8
+(forward grid stride).  All five entry points: segk_head_fwd, _fwd_bn, _bwd, _bwd_bnstat, _bwd_bn.
+
+Tolerances: derived or measured in tests/loss_reference.py, none tuned to what the kernels return."""
+import pytest
+import torch
+
+import loss_reference as L
+
+pytestmark = pytest.mark.gpu
+
+SEGK_DT = {torch.float32: 0, torch.bfloat16: 1}
+NAN = float("nan")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from image_segmentation_amd import _lib
+    _lib.load()
+    return _lib
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def nans(n, dtype=torch.float32):
+    return torch.full((n,), NAN, dtype=dtype, device="cuda")
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def worst(err, bound):
+    """largest err / bound and where (bound 0 demands err 0)"""
+    err, bound = err.reshape(-1), bound.expand(err.shape).reshape(-1)
+    r = torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    i = int(r.argmax())
+    return r[i].item(), i
+
+
+# ------------------------------------------------------------------------------------------------ loss
+def run_loss(lib, x, y, kw, gout):
+    """-> state [28] (unwritten entries NaN), loss_out, gradient [N, C, HW], all on the CPU"""
+    N, C, HW = x.shape
+    P = N * HW
+    prob = kw.get("prob", False)
+    ign = -1 if kw.get("ignore_index") is None else int(kw["ignore_index"])
+    smooth, dwt, cwt = float(kw.get("smooth", 1e-5)), float(kw.get("dice_weight", 1.0)), float(kw.get("ce_weight", 1.0))
+    xd, yd = x.cuda().contiguous(), y.cuda().contiguous()
+    cwd = None if kw.get("cw") is None else kw["cw"].float().cuda()
+    nb = L.loss_launch(P)[0]
+    assert lib.query("segk_loss_part_floats", P) == nb * 26 and lib.query("segk_loss_state_floats") == 28
+    part, state, out = nans(nb * 26 + 26), nans(28 + 4), nans(1 + 3)
+    tail = (int(kw.get("nll_log", 1)), float(kw.get("eps", 0.0))) if prob else ()
+    lib.call("segk_prob_loss_fwd" if prob else "segk_loss_fwd", xd.data_ptr(), yd.data_ptr(), ptr(cwd), N, C, HW, ign, smooth, dwt, cwt,
+             *tail, part.data_ptr(), state.data_ptr(), out.data_ptr(), _stream())
+    go = torch.tensor([gout], dtype=torch.float32, device="cuda")
+    dl = nans(P * C + 5)
+    lib.call("segk_prob_loss_bwd" if prob else "segk_loss_bwd", xd.data_ptr(), yd.data_ptr(), ptr(cwd), state.data_ptr(), go.data_ptr(),
+             N, C, HW, ign, dwt, cwt, *tail, dl.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    part, state, out, dl = part.cpu(), state.cpu(), out.cpu(), dl.cpu()
+    assert torch.isfinite(part[:nb * 26]).all(), "a partial row was not written"
+    assert torch.isnan(part[nb * 26:]).all() and torch.isnan(state[28:]).all() and torch.isnan(out[1:]).all(), "wrote past a buffer"
+    assert torch.isnan(dl[P * C:]).all(), "the gradient kernel wrote past its buffer"
+    return state[:28], out[0], dl[:P * C].view(N, C, HW)
+
+
+def check_loss(lib, x, y, kw, gout, desc, floors=True):
+    C = x.shape[1]
+    r = L.loss_reference(x, y, **kw)
+    gr = L.loss_grad_reference(r, gout)
+    sb, _ = L.state_bound(r)
+    gb = L.grad_bound(r, gr)
+    if floors and not L.degenerate(r):
+        eff, gmax = L.one_pixel_effect(r), gr["grad"].abs().max().item()
+        print(f"{desc}: allowed loss error {sb[0].item():.3g}, one pixel changes it by {eff:.3g}; allowed gradient error "
+              f"{gb.max().item():.3g}, largest gradient {gmax:.3g}")
+        assert sb[0].item() < eff, f"{desc}: the loss bound could hide a dropped pixel"
+        assert gb.max().item() < 1e-3 * gmax, f"{desc}: the gradient bound is too loose to mean anything"
+    state, out, grad = run_loss(lib, x, y, kw, gout)
+    written = [0, 1, 2, 3] + [4 + 8 * j + k for j in range(3) for k in range(C)]
+    rest = [i for i in range(28) if i not in written]
+    assert torch.isnan(state[rest]).all(), f"{desc}: state entries of classes >= C were written"
+    names = ["loss", "ce", "dice", "ce_den"] + [f"{n}[{k}]" for n in ("dc", "den_raw", "a") for k in range(8)]
+    for i in written:
+        got, want = state[i].double().item(), r["state"][i].item()
+        if want != want:
+            assert got != got, f"{desc}: {names[i]} = {got!r}, the reference is NaN"
+            continue
+        err = abs(got - want)
+        print(f"{desc} {names[i]}: {got!r} vs {want!r}, error / bound = {err / sb[i].item() if sb[i] > 0 else err:.4f}")
+        assert err <= sb[i].item(), f"{desc}: {names[i]} = {got!r}, float64 {want!r}, error {err:.3g} > bound {sb[i].item():.3g}"
+    assert out.item() == state[0].item() or (out != out and state[0] != state[0]), f"{desc}: loss_out is not a copy of state[0]"
+    want_nan = torch.isnan(gr["grad"])                       # a counted pixel whose weights sum to zero: 0 / 0, like torch
+    assert torch.equal(torch.isnan(grad), want_nan), f"{desc}: the gradient has elements that were not written (or are NaN where float64 is not)"
+    assert torch.isfinite(grad[~want_nan]).all(), f"{desc}: the gradient is not finite"
+    ratio, at = worst((grad.double() - gr["grad"]).abs().nan_to_num(0.0), gb.nan_to_num(0.0) + want_nan)
+    print(f"{desc} gradient: worst error / bound = {ratio:.4f}")
+    assert ratio <= 1.0, (f"{desc}: gradient element {at} = {grad.reshape(-1)[at].item()!r}, float64 {gr['grad'].reshape(-1)[at].item()!r}, "
+                          f"{ratio:.3f} x the bound")
+    return state, grad
+
+
+@pytest.mark.parametrize("prob", [False, True], ids=["softmax", "prob"])
+@pytest.mark.parametrize("si", range(len(L.LOSS_SHAPES)), ids=[f"{n}x{hw}" for n, hw, _ in L.LOSS_SHAPES])
+@pytest.mark.parametrize("C", range(1, 9))
+def test_loss_matrix(lib, C, si, prob):
+    x, y, kw, gout, desc = L.loss_case(C, si, prob)
+    s1, g1 = check_loss(lib, x, y, kw, gout, desc)
+    s2, _, g2 = run_loss(lib, x, y, kw, gout)                             # one fixed order of additions: bit-stable
+    assert torch.equal(s1.view(torch.int32), s2.view(torch.int32)) and torch.equal(g1.view(torch.int32), g2.view(torch.int32)), desc
+
+
+@pytest.mark.parametrize("prob", [False, True], ids=["softmax", "prob"])
+@pytest.mark.parametrize("si", range(len(L.LOSS_SHAPES_LARGE)), ids=[f"{n}x{hw}" for n, hw, _ in L.LOSS_SHAPES_LARGE])
+@pytest.mark.parametrize("C", L.LARGE_CLASSES)
+def test_loss_matrix_large(lib, C, si, prob):
+    x, y, kw, gout, desc = L.loss_case(C, si, prob, large=True)
+    check_loss(lib, x, y, kw, gout, desc)
+
+
+def test_loss_semantic_edges(lib):
+    """One case each (loss_reference.edge_cases).  Every pixel ignored: the loss is NaN like torch's, and the gradient the
+    kernel gives is PINNED here as the finite Dice part alone (an ignored pixel gets no CrossEntropy gradient; torch's
+    cross_entropy returns zeros there too).  All class weights zero with a Dice-only loss, and a Dice-only loss whose every pixel
+    carries the ignored class: no pixel counts for the CrossEntropy, ce is NaN, and the Dice-only losses (ce_weight = 0), which have
+    no CrossEntropy term in the reference project, must stay finite -- the kernels formed 0 * NaN there until this test."""
+    for name, x, y, kw, gout in L.edge_cases():
+        state, grad = check_loss(lib, x, y, kw, gout, name, floors=False)
+        if name == "every pixel ignored":
+            assert state[0] != state[0] and state[1] != state[1] and state[3].item() == 0.0 and state[2] == state[2]
+        if "clip branch" in name:
+            assert state[4 + 1].item() == 0.0 and state[4 + 8 + 1].item() == 0.0 and (grad[:, 1] == 0).all(), name
+        if "Dice only" in name or "weights zero" in name:
+            assert state[1] != state[1] and torch.isfinite(state[0]), name
+
+
+def test_loss_wrappers_normalise_their_inputs(lib):
+    """ops.SegLossFn / ProbLossFn on non-contiguous and bf16 logits, uint8 / int32 labels and [N, 1, H, W] targets give bit for
+    bit what the call on fp32 contiguous logits and int64 [N, H, W] labels gives; CrossEntropyLoss's default ignore_index
+    (-100) with such labels present equals torch's."""
+    from image_segmentation_amd import losses, ops
+    N, C, H, W = 2, 5, 12, 20
+    x, y = L.loss_inputs(C, N, H * W, 31)
+    x, y = x.view(N, C, H, W), y.view(N, H, W)
+    cw = torch.linspace(0.3, 1.7, C)
+
+    def run(fn, logits, target, *args):
+        leaf = logits.detach().clone().requires_grad_(True) if logits.is_contiguous() else logits.detach().requires_grad_(True)
+        v = fn.apply(leaf, target, *args)
+        v.backward()
+        torch.cuda.synchronize()
+        return v.detach().cpu(), leaf.grad.cpu()
+
+    for fn, args, xin in ((ops.SegLossFn, (cw, 1, 1.0, 0.7, 1.3), x), (ops.ProbLossFn, (cw, 1, 1.0, 0.7, 1.3, 1, 1e-9), torch.softmax(x, 1))):
+        v0, g0 = run(fn, xin.cuda(), y.cuda(), *args)
+        nc = xin.cuda().permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)               # channels-last strides
+        assert not nc.is_contiguous()
+        for what, lg, tg in (("non-contiguous logits", nc, y.cuda()), ("uint8 labels", xin.cuda(), y.to(torch.uint8).cuda()),
+                             ("int32 labels", xin.cuda(), y.to(torch.int32).cuda()), ("[N,1,H,W] target", xin.cuda(), y.unsqueeze(1).cuda()),
+                             ("non-contiguous int64 labels", xin.cuda(), y.cuda().transpose(1, 2).contiguous().transpose(1, 2))):
+            v, g = run(fn, lg, tg, *args)
+            assert torch.equal(v, v0) and torch.equal(g, g0), f"{fn.__name__}: {what}"
+        xb = xin.to(torch.bfloat16)
+        v, g = run(fn, xb.cuda(), y.cuda(), *args)
+        vf, gf = run(fn, xb.float().cuda(), y.cuda(), *args)
+        assert torch.equal(v, vf) and g.dtype == torch.bfloat16 and torch.equal(g, gf.to(torch.bfloat16)), f"{fn.__name__}: bf16 logits"
+    y100 = y.clone()
+    y100.view(-1)[::7] = -100
+    leaf = x.cuda().requires_grad_(True)
+    v = losses.CrossEntropyLoss(weight=cw)(leaf, y100.cuda())
+    v.backward()
+    r = L.loss_reference(x.view(N, C, H * W), y100.view(N, H * W), cw=cw, smooth=0.0, dice_weight=0.0, ce_weight=1.0)
+    sb, _ = L.state_bound(r)
+    assert abs(v.item() - r["loss"].item()) <= sb[0].item()
+    assert abs(r["loss"].item() - torch.nn.functional.cross_entropy(x.double(), y100, weight=cw.double()).item()) < 1e-12
+    gr = L.loss_grad_reference(r)
+    ratio, at = worst((leaf.grad.cpu().view(N, C, H * W).double() - gr["grad"]).abs(), L.grad_bound(r, gr))
+    assert ratio <= 1.0, ratio
+
+
+# ------------------------------------------------------------------------------------------------ head
+def head_inputs(N, HW, Cp, C, ncls, dtype, seed):
+    """y in [-1, 1] and z in [-2, 2] rounded to dtype, zero in the padded channels; w in [-0.2, 0.2], bias in [-0.1, 0.1], dlogits in
+    [-1, 1]; BatchNorm vectors like tests/test_gpu_bn_backward_matrix.py (negative gamma on every fifth channel), zero beyond C."""
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda shape, lo, hi: torch.rand(shape, generator=g, dtype=torch.float32) * (hi - lo) + lo
+    P = N * HW
+    y, z = rnd((P, Cp), -1, 1).to(dtype), rnd((P, Cp), -2, 2).to(dtype)
+    w, b, dl = rnd((ncls, C), -0.2, 0.2), rnd((ncls,), -0.1, 0.1), rnd((N, ncls, HW), -1, 1)
+    gamma, beta, mean, rstd = rnd((Cp,), 0.5, 1.5), rnd((Cp,), -0.5, 0.5), rnd((Cp,), -0.3, 0.3), rnd((Cp,), 0.5, 2.0)
+    gamma[1::5] *= -1
+    scale = gamma * rstd
+    shift = beta - mean * scale
+    for v in (scale, shift, mean, rstd):
+        v[C:] = 0
+    y[:, C:] = 0; z[:, C:] = 0
+    return dict(y=y, z=z, w=w, b=b, dl=dl, bn=(scale, shift, mean, rstd))
+
+
+def check_head(lib, N, HW, Cp, C, ncls, dtype, backward=True):
+    P = N * HW
+    tag = f"head N={N} HW={HW} Cp={Cp} C={C} ncls={ncls} {dtype} bwd launch={L.head_bwd_launch(P, Cp)} lanes={L.head_lane_geometry(Cp)}"
+    h = head_inputs(N, HW, Cp, C, ncls, dtype, Cp * 131 + P % 9973 + 17 * ncls)
+    d = {k: v.cuda() for k, v in h.items() if k != "bn"}
+    bn = [t.cuda() for t in h["bn"]]
+    yz = L.head_input(h["z"], h["bn"][0], h["bn"][1], dtype)
+    dt = SEGK_DT[dtype]
+    # forward, on y and re-formed from z
+    for name, src in (("segk_head_fwd", h["y"]), ("segk_head_fwd_bn", yz)):
+        lg = nans(P * ncls + 7)
+        if name == "segk_head_fwd":
+            lib.call(name, d["y"].data_ptr(), d["w"].data_ptr(), d["b"].data_ptr(), lg.data_ptr(), N, HW, 1, Cp, C, ncls, dt, _stream())
+        else:
+            lib.call(name, d["z"].data_ptr(), bn[0].data_ptr(), bn[1].data_ptr(), d["w"].data_ptr(), d["b"].data_ptr(), lg.data_ptr(), N, HW, 1,
+                     Cp, C, ncls, dt, _stream())
+        torch.cuda.synchronize()
+        lg = lg.cpu()
+        assert torch.isnan(lg[P * ncls:]).all(), f"{tag} {name}: wrote past the logits"
+        assert torch.isfinite(lg[:P * ncls]).all(), f"{tag} {name}: logits that were not written"
+        want, ab = L.head_fwd_reference(src, h["w"], h["b"], N, HW)
+        ratio, at = worst((lg[:P * ncls].view(N, ncls, HW).double() - want).abs(), L.head_fwd_bound(ab, C))
+        assert ratio <= 1.0, f"{tag} {name}: logit {at} = {lg[at].item()!r}, float64 {want.reshape(-1)[at].item()!r}, {ratio:.3f} x the bound"
+    if not backward:
+        return
+    nb = L.head_blocks(P)
+    assert lib.query("segk_head_bwd_blocks", P) == nb and lib.query("segk_head_part_floats", P, Cp) == nb * 8 * (Cp + 1)
+    for name in ("segk_head_bwd", "segk_head_bwd_bnstat", "segk_head_bwd_bn"):
+        zin, stat = name == "segk_head_bwd_bn", name != "segk_head_bwd"
+        src = yz if zin else h["y"]
+        dy = torch.full((P + 3, Cp), NAN, dtype=dtype, device="cuda")
+        part, dw, db = nans(nb * 8 * (Cp + 1) + 9), nans(ncls * C + 5), nans(ncls + 5)
+        bnpart = nans(nb * Cp * 2 + 6)
+        inp = d["z"] if zin else d["y"]
+        args = [d["dl"].data_ptr(), inp.data_ptr(), d["w"].data_ptr(), dy.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(), N, HW, 1,
+                Cp, C, ncls]
+        if stat:
+            args += [t.data_ptr() for t in bn] + [bnpart.data_ptr()]
+        lib.call(name, *args, dt, _stream())
+        torch.cuda.synchronize()
+        dy, part, dw, db, bnpart = dy.cpu(), part.cpu(), dw.cpu(), db.cpu(), bnpart.cpu()
+        assert torch.isnan(dy[P:].float()).all() and torch.isnan(part[nb * 8 * (Cp + 1):]).all() and torch.isnan(dw[ncls * C:]).all() \
+            and torch.isnan(db[ncls:]).all() and torch.isnan(bnpart[nb * Cp * 2:]).all(), f"{tag} {name}: wrote past a buffer"
+        assert torch.isfinite(dy[:P].float()).all(), f"{tag} {name}: dy has elements that were not written"
+        assert (dy[:P, C:].float() == 0).all(), f"{tag} {name}: padded channels of dy are not zero"
+        r = L.head_bwd_reference(h["dl"], src, h["w"], h["bn"] if stat else None, h["z"] if zin else None)
+        ratio, at = worst((dy[:P].double() - r["dy"]).abs(), L.head_dy_bound(r, ncls, dtype))
+        assert ratio <= 1.0, f"{tag} {name}: dy element {at} is {ratio:.3f} x the bound off"
+        for what, got, want, ab in (("dW", dw[:ncls * C].view(ncls, C), r["dw"], r["dw_abs"]), ("db", db[:ncls], r["db"], r["db_abs"])):
+            ratio, at = worst((got.double() - want).abs(), L.head_sum_bound(P, Cp, ab))
+            assert ratio <= 1.0, f"{tag} {name}: {what} element {at} = {got.reshape(-1)[at].item()!r}, float64 {want.reshape(-1)[at].item()!r}, {ratio:.3f} x the bound"
+        if stat:
+            rows = bnpart[:nb * Cp * 2].view(nb, Cp, 2).double().sum(0)
+            for what, got, want, ab, carried in (("sum g", rows[:, 0], r["sg"], r["sg_abs"], r["sg_in"]),
+                                                 ("sum g xhat", rows[:, 1], r["sgx"], r["sgx_abs"], r["sgx_in"])):
+                ratio, at = worst((got - want).abs(), L.head_sum_bound(P, Cp, ab, carried))
+                assert ratio <= 1.0, f"{tag} {name}: {what}[{at}] = {got[at].item()!r}, float64 {want[at].item()!r}, {ratio:.3f} x the bound"
+        else:
+            assert torch.isnan(bnpart).all()
+
+
+SMALL = [(1, 1), (5, 1), (3, 85), (4, 64), (1, 257)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("Cp", [32, 64, 96, 288, 512])
+@pytest.mark.parametrize("ncls", range(1, 9))
+def test_head_matrix_small(lib, ncls, Cp, dtype):
+    for N, HW in SMALL:
+        check_head(lib, N, HW, Cp, Cp - 3, ncls, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("ncls", range(1, 9))
+def test_head_many_images_per_step(lib, ncls, dtype):
+    check_head(lib, 400, 35, 256, 253, ncls, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("Cp", [32, 96])
+@pytest.mark.parametrize("ncls", range(1, 9))
+def test_head_main_loop_and_tail(lib, ncls, Cp, dtype):
+    check_head(lib, 70, 1000, Cp, Cp - 3, ncls, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("ncls", [2, 8])
+def test_head_forward_grid_stride(lib, ncls, dtype):
+    check_head(lib, 1021, 1029, 32, 29, ncls, dtype, backward=False)
+
+
+# ------------------------------------------------------------------------------------------------ confusion
+@pytest.mark.parametrize("shape", [(3, 99), (263, 1001)], ids=["297", "263263"])
+@pytest.mark.parametrize("C", range(1, 9))
+def test_confusion_matrix(lib, C, shape):
+    """exact.  263 x 1001 pixels: beyond the 1024-block cap (grid stride).  Planted: ties (the lowest index wins), NaN logits (NaN
+    counts as the maximum, the first NaN wins, like torch.argmax), labels -100 / 255 / C (skipped: the histogram index is guarded
+    by 0 <= y < C in the kernel); the counts are ADDED to a non-zero matrix."""
+    N, HW = shape
+    assert L.confusion_launch(N * HW)[1] == (2 if N * HW > 262144 else 1)
+    g = torch.Generator().manual_seed(50 + C)
+    x = torch.rand((N, C, HW), generator=g) * 2 - 1
+    y = torch.randint(0, C, (N, HW), generator=g)
+    flat = x.permute(0, 2, 1).reshape(-1, C)
+    flat[::11] = 0.75                                            # every class ties
+    if C > 2:
+        flat[5::13, 1] = 5.0; flat[5::13, C - 1] = 5.0           # two classes tie at the top
+    flat[7::17, C - 1] = NAN
+    if C > 1:
+        flat[9::19, 0] = NAN; flat[9::19, C - 1] = NAN           # two NaN: the first wins
+    x = flat.view(N, HW, C).permute(0, 2, 1).contiguous()
+    y.view(-1)[1::23] = -100; y.view(-1)[2::29] = 255; y.view(-1)[3::31] = C
+    hard = torch.where(torch.isnan(x), torch.full_like(x, float("inf")), x).argmax(1)
+    ok = (y >= 0) & (y < C)
+    start = (torch.arange(64, dtype=torch.int64) * 3 + 1).view(8, 8)
+    want = start.clone()
+    want.view(-1).index_add_(0, (hard[ok] * 8 + y[ok]), torch.ones(int(ok.sum()), dtype=torch.int64))
+    M, xd, yd = start.cuda(), x.cuda(), y.cuda()
+    lib.call("segk_confusion", xd.data_ptr(), yd.data_ptr(), N, C, HW, M.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    assert torch.equal(M.cpu(), want)
+
+
+# ------------------------------------------------------------------------------------------------ prompt remix
+@pytest.mark.parametrize("si", range(len(L.MIX_SHAPES)), ids=[f"{n}x{hw}" for n, hw in L.MIX_SHAPES])
+def test_prompt_mix_matrix(lib, si):
+    """forward and backward at one pixel, 257 pixels and beyond 4096 * 256 (grid stride), mask logits saturated at +-40"""
+    cl, ml = L.mix_cases()[si]
+    N, _, HW = cl.shape
+    P = N * HW
+    assert L.loss_bwd_launch(P)[1] == (2 if si == 2 else 1)
+    g = torch.Generator().manual_seed(60 + si)
+    dout = torch.rand((N, 4, HW), generator=g) * 2 - 1
+    cd, md, dd = cl.cuda(), ml.cuda(), dout.cuda()
+    out, dm = nans(P * 4 + 3), nans(P + 3)
+    lib.call("segk_prompt_mix_fwd", cd.data_ptr(), md.data_ptr(), out.data_ptr(), N, HW, _stream())
+    lib.call("segk_prompt_mix_bwd", cd.data_ptr(), md.data_ptr(), dd.data_ptr(), dm.data_ptr(), N, HW, _stream())
+    torch.cuda.synchronize()
+    out, dm = out.cpu(), dm.cpu()
+    assert torch.isnan(out[P * 4:]).all() and torch.isnan(dm[P:]).all(), "wrote past a buffer"
+    assert torch.isfinite(out[:P * 4]).all() and torch.isfinite(dm[:P]).all(), "elements that were not written"
+    want, _, _ = L.prompt_mix_reference(cl, ml)
+    ratio, at = worst((out[:P * 4].view(N, 4, HW).double() - want).abs(), L.prompt_mix_bound(ml).expand(N, 4, HW))
+    assert ratio <= 1.0, f"prompt_mix_fwd P={P}: element {at} is {ratio:.3f} x the bound off"
+    gw, ab = L.prompt_mix_grad_reference(cl, ml, dout)
+    gb = L.prompt_mix_grad_bound(ml, ab)
+    assert gb.max().item() < 1e-3 * gw.abs().max().item() or P == 1
+    ratio, at = worst((dm[:P].view(N, HW).double() - gw).abs(), gb)
+    assert ratio <= 1.0, f"prompt_mix_bwd P={P}: element {at} is {ratio:.3f} x the bound off"
