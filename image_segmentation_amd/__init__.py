@@ -12,3 +12,5 @@ from .inference import Segmenter, Prediction, predict, load_checkpoint, COLOR_MA
 from .prompts import PromptSampler, PromptBatch, PromptBatches, TRIMAP_TO_PROMPT, heat_tables, point_heatmap   # noqa: F401
 from .augment import (Augmenter, AugPlan, AugmentedBatches, merge_pairs, class_weights, convert_rgb_label_to_classes,   # noqa: F401
                       cubic_table, contrast_lut, laplace_table, rotation_plan, merge_plan, ALL_OPS, TARGET_REMAP)
+from .robustness import (PERTURBATIONS, DEFAULT_LEVELS, PerturbPlan, gauss_table, value_lut, perturb_plan, perturb,      # noqa: F401
+                         robustness_sweep, cell_seed, image_seed)

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 314          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 315          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
 
@@ -101,6 +101,8 @@ SIGNATURES = {
     "segk_aug_merge": (_i, [_vp, _vp, _i, _i, _vp, _fp, _vp, _vp, _vp]),
     "segk_label_hist": (_i, [_vp, _l, _i, _i, _i, _l, _vp, _vp]),
     "segk_rgb_label_to_classes": (_i, [_vp, _vp, _l, _vp]),
+    "segk_perturb_point": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "segk_perturb_blur": (_i, [_vp, _i, _i, _i, _vp]),
 }
 
 

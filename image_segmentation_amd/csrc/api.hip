@@ -56,6 +56,8 @@ int segk_aug_resample_impl(const segk_aug_desc*, int, int, const int32_t*, const
 int segk_aug_merge_impl(const segk_merge_desc*, const int32_t*, int, int, const uint8_t*, float*, uint8_t*, long long*, hipStream_t);
 int segk_label_hist_impl(const void*, long, int, int, int, long, unsigned long long*, hipStream_t);
 int segk_rgb_label_to_classes_impl(const uint8_t*, uint8_t*, long, hipStream_t);
+int segk_perturb_point_impl(const segk_perturb_desc*, int, int, int, const void*, hipStream_t);
+int segk_perturb_blur_impl(const segk_perturb_desc*, int, int, int, hipStream_t);
 
 int segk_clock_probe_impl(unsigned long long*, int, int, int, hipStream_t);
 int segk_debug_poison_tickets_impl(unsigned long long, hipStream_t);
@@ -421,6 +423,13 @@ int segk_label_hist(const void* labels, long n, int elem_bytes, int num_classes,
 }
 int segk_rgb_label_to_classes(const uint8_t* rgb, uint8_t* out, long n, segk_stream_t s) {
   return segk_rgb_label_to_classes_impl(rgb, out, n, (hipStream_t)s);
+}
+// robustness perturbations (report section 4.1: eight perturbation types at ten severity levels)
+int segk_perturb_point(const segk_perturb_desc* descs, int n, int total_tiles, int kind, const void* table, segk_stream_t s) {
+  return segk_perturb_point_impl(descs, n, total_tiles, kind, table, (hipStream_t)s);
+}
+int segk_perturb_blur(const segk_perturb_desc* descs, int n, int total_tiles, int k, segk_stream_t s) {
+  return segk_perturb_blur_impl(descs, n, total_tiles, k, (hipStream_t)s);
 }
 int segk_confusion(const float* logits, const int64_t* labels, int N, int C, long HW, uint64_t* M, segk_stream_t s) {
   return segk_confusion_impl(logits, (const long long*)labels, N, C, HW, (unsigned long long*)M, (hipStream_t)s);

@@ -30,16 +30,6 @@ constexpr int OP_ROTATION = SEGK_AUG_ROTATION, OP_MASKING = SEGK_AUG_MASKING, OP
 constexpr int LAP_N = SEGK_AUG_LAPLACE_ENTRIES;
 constexpr unsigned DROP_BELOW = 2516582u;          // floor(0.15 * 2^24)
 
-// splitmix64 finaliser of i + seed * 0x9E3779B97F4A7C15
-__device__ __forceinline__ unsigned long long splitmix(unsigned long long seed, unsigned long long i) {
-  unsigned long long z = i + seed * 0x9E3779B97F4A7C15ULL;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 // utils/utils.py:201-250: black or white -> 0, (128,0,0) -> 1, (0,128,0) -> 2, else 255
 __device__ __forceinline__ int rgb_class(int r, int g, int b) {
   const int p = (r << 16) | (g << 8) | b;
@@ -59,14 +49,6 @@ __device__ __forceinline__ int label_at(const uint8_t* __restrict__ lab, size_t 
 __device__ __forceinline__ bool dropped(const segk_aug_desc& d, int y, int x) {
   const int cy = (int)(((long long)y * d.gh) / d.H), cx = (int)(((long long)x * d.gw) / d.W);
   return (unsigned)(splitmix(d.seed, (unsigned long long)((long long)cy * d.gw + cx)) >> 40) < DROP_BELOW;
-}
-
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  const int p = 2 * (n - 1);
-  int m = i % p;
-  m = m < 0 ? m + p : m;
-  return m < n ? m : p - m;
 }
 
 // ------------------------------------------------------------------------------------------------ stage A

@@ -130,4 +130,23 @@ __device__ __forceinline__ Idx4 split4(unsigned i, unsigned CV, unsigned Wc, uns
   r.cv = (int)(i - p * CV); r.x = (int)(p - q * Wc); r.y = (int)(q - b * Hc); r.b = (int)b;
   return r;
 }
+// ---- shared by the 8-bit image kernels (augment.hip, perturb.hip)
+// splitmix64 finaliser of i + seed * 0x9E3779B97F4A7C15
+__device__ __forceinline__ unsigned long long splitmix(unsigned long long seed, unsigned long long i) {
+  unsigned long long z = i + seed * 0x9E3779B97F4A7C15ULL;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+__device__ __forceinline__ int reflect101(int i, int n) {
+  if (n == 1) return 0;
+  const int p = 2 * (n - 1);
+  int m = i % p;
+  m = m < 0 ? m + p : m;
+  return m < n ? m : p - m;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 314
-#define SEGK_ENTRY_COUNT 83
+#define SEGK_ABI_VERSION 315
+#define SEGK_ENTRY_COUNT 85
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -418,6 +418,37 @@ int segk_label_hist(const void* labels, long n, int elem_bytes, int num_classes,
                     uint64_t* counts, segk_stream_t s);
 /* utils.py:201-250: rgb uint8 [n][3] -> out uint8 [n]: black or white 0, (128,0,0) 1, (0,128,0) 2, else 255 */
 int segk_rgb_label_to_classes(const uint8_t* rgb, uint8_t* out, long n, segk_stream_t s);
+
+/* ---- robustness perturbations (report section 4.1 / figure 6; the reference holds no code for them: DESIGN.md 3.x) --------
+ * 8-bit interleaved images at their own sizes in, uint8 [H][W][3] out; integer arithmetic and host-built tables only, so the
+ * result is bit-stable and independent of the launch shape.  One launch serves a ragged batch: the device table has one
+ * entry per image, sorted by tile0, and total_tiles is the sum of the images' tile counts.  A launch applies ONE kind (or one
+ * number of blur passes) to all its images: the table lives in device memory, so what the host must validate is an argument. */
+#define SEGK_PERTURB_LUT 0           /* out = lut[v]; table: uint8 [256] (contrast, brightness) */
+#define SEGK_PERTURB_GAUSS_NOISE 1   /* out = clip(v + tab[hash(seed, e) >> 52], 0, 255), e = (y W + x) 3 + c; table: int16 [4096] */
+#define SEGK_PERTURB_SALT_PEPPER 2   /* h = hash(seed, e); (h >> 40) < p0 ? ((h >> 39) & 1 ? 255 : 0) : v; p0 = floor(amount 2^24) */
+#define SEGK_PERTURB_OCCLUDE 3       /* rows [p0, p0 + p2) x columns [p1, p1 + p2) become 0 in every channel */
+#define SEGK_PERTURB_GAUSS_ENTRIES 4096
+#define SEGK_PERTURB_POINT_TILE 4096 /* output bytes per tile of segk_perturb_point: ceil(H W 3 / 4096) tiles per image */
+#define SEGK_PERTURB_BLUR_TH 32      /* output rows and columns per tile of segk_perturb_blur: */
+#define SEGK_PERTURB_BLUR_TW 64      /*   ceil(H / 32) ceil(W / 64) tiles per image */
+#define SEGK_PERTURB_BLUR_MAX 9      /* most passes one launch runs (the halo the tile in LDS is sized for) */
+typedef struct segk_perturb_desc {   /* one image; 56 bytes */
+  const uint8_t* src;                /* uint8 [H][W][src_c], src_c 3 | 4 (the fourth channel is ignored) */
+  uint8_t* dst;                      /* uint8 [H][W][3]; must not overlap src */
+  uint64_t seed;                     /* per-image seed of the hash (noise, salt and pepper) */
+  int32_t H, W, src_c;               /* H W 3 < 2^31 */
+  int32_t tile0;                     /* first tile of this image in the launch */
+  int32_t p0, p1, p2;                /* the kind's parameters (above) */
+  int32_t pad_;
+} segk_perturb_desc;
+/* hash = the splitmix64 finaliser of e + seed 0x9E3779B97F4A7C15 (the one of SEGK_AUG_LAPLACE).  table: see the kinds (NULL
+ * for salt and pepper and occlusion).  total_tiles == 0 launches nothing. */
+int segk_perturb_point(const segk_perturb_desc* descs, int n, int total_tiles, int kind, const void* table, segk_stream_t s);
+/* k passes (0..SEGK_PERTURB_BLUR_MAX; 0 copies) of the mask [1 2 1; 2 4 2; 1 2 1] / 16, each (sum + 8) >> 4 on 8-bit values
+ * with reflect-101 borders (index i mod 2 (n - 1), folded; 0 for n = 1).  All passes run in LDS: the tile is loaded with a
+ * halo of k reflected once, which equals reflecting at every pass because the mask is symmetric. */
+int segk_perturb_blur(const segk_perturb_desc* descs, int n, int total_tiles, int k, segk_stream_t s);
 
 /* ---- reconstruction head and MSE loss (autoencoder/autoencoder.py:188-191; nn.MSELoss as autoencoder.ipynb cell 0
  * constructs it and utils/training.py:141,234 call it) ---------------------------------------------------------------

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -478,7 +478,63 @@ def augment():
     print(f"augment clock probe: median {clk['median_ghz']} GHz; written to {path}")
 
 
+def perturb():
+    """Robustness perturbations through the C ABI (csrc/perturb.hip): B = 32 images of 375 x 500 uint8 RGB at their own size,
+    every kind at its strongest default level plus blur at 1 pass.  Per row: device-event time of the one launch replayed
+    alone (warmed, 50 repetitions per round, seven rounds: median and min..max), GB/s over the 6 bytes per pixel every kind
+    must move (3 read + 3 written), the time that floor takes at the copy rate measured here (a device-to-device copy of the
+    same bytes, same rounds), and the whole perturb() call (host tables + one pinned upload + the launch).  The last row is
+    what follows in a sweep: the 32 segk_resize_pad_u8 launches that bring the batch to 224 x 224.  Also written to
+    profiles/kbench_perturb.json (or the file given with --out)."""
+    import json
+    from image_segmentation_amd import robustness as P
+    from image_segmentation_amd.inference import _into_slot
+    B, H, W, T = 32, 375, 500, 224
+    g = torch.Generator(device="cuda").manual_seed(0)
+    imgs = [torch.randint(0, 256, (H, W, 3), generator=g, device="cuda", dtype=torch.uint8) for _ in range(B)]
+    nbytes = B * H * W * 6
+
+    def rounds(fn):
+        t = sorted(timeit(fn, 50) for _ in range(7))
+        return {"median": t[3], "min": t[0], "max": t[-1]}
+    src, dst = torch.cat([im.reshape(-1) for im in imgs]), torch.empty(B * H * W * 3, dtype=torch.uint8, device="cuda")
+    tc = rounds(lambda: dst.copy_(src))
+    copy_rate = nbytes / (tc["median"] * 1e-6)
+    print(f"perturb copy of the same bytes (read {nbytes // 2} + write {nbytes // 2}): {tc['median']:.1f} us = {copy_rate / 1e9:.1f} GB/s")
+    rows = []
+    cases = [(k, P.DEFAULT_LEVELS[k][-1]) for k in P.PERTURBATIONS]
+    cases.insert(2, ("gaussian_blur", 1))
+    for kind, level in cases:
+        plan = P.perturb_plan(kind, level, [(H, W)] * B, seed=0)
+        out, (name, args), keep = P._launch(imgs, plan)
+        tk = rounds(lambda: _lib.call(name, *args))
+        ta = rounds(lambda: P.perturb(imgs, kind, level, seed=0))
+        row = {"kind": kind, "level": level, "launch": name, "kernel_us": tk, "perturb_call_us": ta, "bytes": nbytes,
+               "GBps": nbytes / tk["median"] / 1e3, "floor_us_at_copy_rate": tc["median"],
+               "copy_rate_fraction": tc["median"] / tk["median"]}
+        rows.append(row)
+        print(f"perturb {kind:20s} level {level:<5} B={B} {H}x{W}  kernel {tk['median']:8.1f} us [{tk['min']:.1f}..{tk['max']:.1f}] "
+              f"{row['GBps']:7.1f} GB/s = {100 * row['copy_rate_fraction']:5.1f} % of the copy rate   perturb() call "
+              f"{ta['median']:8.1f} us [{ta['min']:.1f}..{ta['max']:.1f}]   ({name})")
+        del out, keep
+    X = torch.empty((B, 3, T, T), dtype=torch.float32, device="cuda")
+    tr = rounds(lambda: [_into_slot(im, X[k], T, "bilinear", None, "image") for k, im in enumerate(imgs)])
+    print(f"perturb then: {B} x segk_resize_pad_u8 -> {T}x{T}  {tr['median']:8.1f} us [{tr['min']:.1f}..{tr['max']:.1f}]")
+    clk = ops.clock_probe()
+    res = {"rows": rows, "copy_us": tc, "copy_GBps": copy_rate / 1e9, "resize_pad_u8_x32_us": tr, "clock_probe_ghz": clk["median_ghz"],
+           "build_id": _lib.build_id(), "B": B, "source": [H, W], "T": T}
+    path = os.path.join(ROOT, "profiles", "kbench_perturb.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(f"perturb clock probe: median {clk['median_ghz']} GHz; written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "perturb":
+        perturb()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "augment":
         augment()
         sys.exit(0)
