@@ -1,0 +1,260 @@
+"""CPU: the case table of the 3x3 convolution matrix (tests/conv_cases.py) reaches every 3x3 kernel instance that
+csrc/conv_igemm.hip and csrc/conv_rs.hip compile to, except the ones listed -- and proved -- unreachable, and nothing else.
+The units are compiled device-only exactly as tools/spill_report.py does and the kernel names of the resource-usage remarks
+are parsed: a new instance without a case, or a dispatch change that strands a case, fails here on any machine.  Also the
+table's own conditions: image kinds per instance, the W = 16 / 17 pairs, the spread of the features, the cases with three or
+more work units per workgroup, the size of the float64 references and the exactness conditions of the lattice run."""
+import itertools
+import os
+import re
+import sys
+
+import pytest
+
+from conv_cases import (CASES, LONG_CASES, PERSISTENT_FAMILIES, REF_MADD_CAP, UNREACHABLE, Case, case_id, family_of, image_kind,
+                        instance_of, is_valid, logical_of, probe_passes, ref_madds, select, spell, tile_shape, tiles_of,
+                        units_per_workgroup, writes_act)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+
+
+def parse_instance(mangled):
+    """Mangled kernel name -> the spelling instance_of() uses; None for a 1x1 / ConvTranspose (GEO == 1) instance and for
+    anything that is not a convolution kernel.  (The mangled name is parsed because c++filt garbles __bf16, DF16b.)"""
+    b = lambda v: "true" if v == "1" else "false"
+    m = re.search(r"14conv_rs_kernelILi(\d)ELb([01])EE", mangled)
+    if m:
+        return f"conv_rs_kernel<{m.group(1)},{b(m.group(2))}>"
+    m = re.search(r"14conv_ws_kernelI(DF16b|f)Li(\d)ELb([01])EE", mangled)
+    if m:
+        return f"conv_ws_kernel<{'bf16' if m.group(1) == 'DF16b' else 'fp32'},{m.group(2)},{b(m.group(3))}>"
+    m = re.search(r"19conv3x3_pipe_kernelILi(\d)ELb([01])ELi(\d+)ELb([01])EE", mangled)
+    if m:
+        return f"conv3x3_pipe_kernel<{m.group(1)},{b(m.group(2))},{m.group(3)},{b(m.group(4))}>"
+    m = re.search(r"17conv_igemm_kernelI(DF16b|f)Li(\d)E" + r"Li(\d)E" * 6 + r"Lb([01])EE", mangled)
+    if m and m.group(2) == "0":
+        return "conv_igemm_kernel<{},0,{},{},{},{},{},{},{}>".format("bf16" if m.group(1) == "DF16b" else "fp32",
+                                                                     *m.group(3, 4, 5, 6, 7, 8), b(m.group(9)))
+    return None
+
+
+@pytest.fixture(scope="module")
+def compiled_instances():
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc is absent")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import spill_report
+    finally:
+        sys.path.pop(0)
+    names = []
+    for unit in ("conv_igemm", "conv_rs"):
+        rows = spill_report.report(unit)
+        assert rows, f"the resource-usage remarks of {unit}.hip were not found"
+        assert all("conv" in r["name"] for r in rows), [r["name"] for r in rows]
+        names += [n for n in (parse_instance(r["name"]) for r in rows) if n is not None]
+        geo1 = [r["name"] for r in rows if parse_instance(r["name"]) is None]
+        assert all(re.search(r"17conv_igemm_kernelI(DF16b|f)Li1E", n) for n in geo1), geo1      # only GEO == 1 is ignored
+    assert len(set(names)) == len(names)
+    return set(names)
+
+
+def test_parse_instance():
+    p = parse_instance
+    assert p("_ZN12_GLOBAL__N_114conv_ws_kernelIDF16bLi5ELb1EEEv8ConvArgs") == "conv_ws_kernel<bf16,5,true>"
+    assert p("_ZN12_GLOBAL__N_119conv3x3_pipe_kernelILi4ELb0ELi128ELb1EEEv8ConvArgs") == "conv3x3_pipe_kernel<4,false,128,true>"
+    assert p("_ZN12_GLOBAL__N_119conv3x3_pipe_kernelILi5ELb1ELi64ELb0EEEv8ConvArgs") == "conv3x3_pipe_kernel<5,true,64,false>"
+    assert p("_ZN12_GLOBAL__N_117conv_igemm_kernelIDF16bLi0ELi4ELi2ELi2ELi2ELi1ELi1ELb1EEEv8ConvArgs") == \
+        "conv_igemm_kernel<bf16,0,4,2,2,2,1,1,true>"
+    assert p("_ZN12_GLOBAL__N_117conv_igemm_kernelIfLi0ELi5ELi4ELi2ELi2ELi2ELi2ELb0EEEv8ConvArgs") == \
+        "conv_igemm_kernel<fp32,0,5,4,2,2,2,2,false>"
+    assert p("_ZN12_GLOBAL__N_117conv_igemm_kernelIfLi1ELi5ELi8ELi1ELi1ELi1ELi2ELb0EEEv8ConvArgs") is None      # GEO == 1
+    assert p("_ZN12_GLOBAL__N_114conv_rs_kernelILi2ELb1EEEv8ConvArgs") == "conv_rs_kernel<2,true>"
+
+
+@pytest.mark.timeout(900)
+def test_table_and_unreachable_list_account_for_every_compiled_instance(compiled_instances):
+    table = {instance_of(c) for c in CASES}
+    unreachable = set(UNREACHABLE)
+    assert not table & unreachable, sorted(table & unreachable)
+    print(f"{len(compiled_instances & (table | unreachable))} of {len(compiled_instances)} compiled 3x3 instances accounted for: "
+          f"{len(table)} reached by the table, {len(unreachable)} listed unreachable")
+    missing, stranded = compiled_instances - table - unreachable, (table | unreachable) - compiled_instances
+    assert not missing, f"compiled instances without a case: {sorted(missing)}"
+    assert not stranded, f"cases or UNREACHABLE entries whose instance is not compiled (dispatch changed?): {sorted(stranded)}"
+    assert len(compiled_instances) == 36
+    assert {instance_of(c) for c in LONG_CASES} <= table
+
+
+def test_every_case_is_a_valid_call_and_distinct():
+    assert len(set(CASES)) == len(CASES) and not set(CASES) & set(LONG_CASES)
+    for c in CASES + LONG_CASES:
+        assert is_valid(c), c
+        assert c.mode in (0, 1) and c.dtype in ("bf16", "fp32")
+        la, lb, lo1, lo2 = logical_of(c)
+        assert 0 < la <= c.CA and 0 <= lb <= c.CB and (lb > 0) == (c.CB > 0) and 0 < lo1 <= c.CO1 and (lo2 > 0) == (c.CO2 > 0)
+    assert any(logical_of(c)[0] == 40 and c.CA == 64 for c in CASES) and any(logical_of(c)[3] == 70 and c.CO2 == 96 for c in CASES)
+    assert len({case_id(c) for c in CASES + LONG_CASES}) == len(CASES) + len(LONG_CASES)
+
+
+def test_unreachable_instances_are_selected_by_no_valid_call():
+    """The mirror over every padded (Cin, N) in 32..512 step 32 x W x bias x prologue x dtype (odd and even chunk counts, the
+    LDS-DMA condition, among them) selects none of the UNREACHABLE instances -- and does select every other one."""
+    seen = set()
+    for dtype, cin, n, W, bias, pro in itertools.product(("bf16", "fp32"), range(32, 513, 32), range(32, 513, 32), (8, 16, 17, 64),
+                                                         (False, True), (False, True)):
+        seen.add(spell(*select(dtype, cin, n, W, bias, pro)))
+    assert not seen & set(UNREACHABLE), sorted(seen & set(UNREACHABLE))
+    assert seen == {instance_of(c) for c in CASES}
+    for name, reason in UNREACHABLE.items():
+        assert name.startswith("conv_igemm_kernel<bf16,0,") and len(reason) > 40
+
+
+def test_instance_of_follows_the_dispatch_rules():
+    mk = lambda **k: Case(**{**dict(dtype="bf16", B=2, H=40, W=72, CA=64, CB=0, CO1=64, CO2=0, prologue=False, act_out=False,
+                                    bias=False, stats=False, mode=0), **k})
+    assert instance_of(mk(prologue=True, act_out=True)) == "conv_rs_kernel<2,true>"      # test_conv3x3_bf16_prologue_side_output, C = 64
+    assert instance_of(mk(CA=128, CO1=128, prologue=True, act_out=True)) == "conv3x3_pipe_kernel<5,true,128,false>"     # ... C = 128
+    assert instance_of(mk(CA=32)) == "conv_rs_kernel<1,false>" and tile_shape(mk(CA=32)) == (8, 32)
+    assert instance_of(mk(bias=True)) == "conv_ws_kernel<bf16,5,false>"                   # conv_rs carries no bias
+    assert instance_of(mk(W=16)) == "conv_ws_kernel<bf16,4,false>" and tile_shape(mk(W=16)) == (16, 16)
+    assert instance_of(mk(CA=32, CB=32, CO1=128)) == "conv_rs_kernel<2,false>"
+    assert instance_of(mk(CA=128, CO1=128)) == "conv3x3_pipe_kernel<5,false,128,true>"   # the benchmark's 128 -> 128 layers
+    assert instance_of(mk(CA=128, CO1=128, bias=True)) == "conv3x3_pipe_kernel<5,false,128,false>"
+    assert instance_of(mk(CA=96, CO1=128)) == "conv3x3_pipe_kernel<5,false,128,false>"    # three chunks: odd
+    assert instance_of(mk(CA=64, CB=96, CO1=256, W=16)) == "conv3x3_pipe_kernel<4,false,128,false>"
+    assert instance_of(mk(CA=128, CO1=64)) == "conv3x3_pipe_kernel<5,false,64,true>" and tile_shape(mk(CA=128, CO1=64)) == (16, 32)
+    assert instance_of(mk(CA=128, CO1=64, CO2=128, W=9)) == "conv3x3_pipe_kernel<4,false,64,true>"
+    assert tile_shape(mk(CA=128, CO1=64, W=9)) == (32, 16)
+    assert instance_of(mk(CA=96)) == "conv_igemm_kernel<bf16,0,4,2,2,2,1,1,false>" and tile_shape(mk(CA=96)) == (8, 16)
+    assert instance_of(mk(CA=96, CO1=192, prologue=True)) == "conv_igemm_kernel<bf16,0,4,2,2,2,1,1,true>"
+    assert instance_of(mk(CO1=96)) == "conv_igemm_kernel<bf16,0,4,4,1,1,1,1,false>"
+    assert instance_of(mk(dtype="fp32", CO1=128)) == "conv_igemm_kernel<fp32,0,5,4,2,2,2,2,false>"
+    assert instance_of(mk(dtype="fp32", CO1=128, W=16, prologue=True)) == "conv_igemm_kernel<fp32,0,4,4,2,2,2,2,true>"
+    assert instance_of(mk(dtype="fp32")) == "conv_igemm_kernel<fp32,0,4,2,2,2,1,1,false>"
+    assert instance_of(mk(dtype="fp32", CO1=32)) == "conv_igemm_kernel<fp32,0,4,4,1,1,1,1,false>"
+    # segk_conv_tiles: per tile, except conv_rs (one row per wave slab and workgroup of a channel tile, 256 compute units)
+    assert tiles_of(mk(CA=128, CO1=128)) == 2 * 5 * 3 and tiles_of(mk(CA=128, CO1=64)) == 2 * 3 * 3
+    assert tiles_of(mk(CA=96)) == 2 * 5 * 5 and tiles_of(mk(W=16)) == 2 * 3 * 1
+    assert tiles_of(mk()) == 8 * 4 * 4 and tiles_of(mk(CO1=128)) == 8 * 4 * 4 and tiles_of(mk(B=64, CO1=192)) == 8 * 10 * 4
+    assert not is_valid(mk(bias=True, stats=True)) and is_valid(mk(bias=True, stats=True, W=16))
+    assert not is_valid(mk(dtype="fp32", prologue=True, act_out=True)) and not is_valid(mk(prologue=True, CB=32))
+
+
+def test_every_instance_has_whole_ragged_and_sub_tile_images():
+    per, fam = {}, {}
+    for c in CASES:
+        per.setdefault(instance_of(c), set()).add(image_kind(c))
+        fam.setdefault(family_of(c), set()).add((c.H, c.W))
+        if image_kind(c) == "ragged":
+            assert c.B >= 2, c
+    assert len(per) == 32
+    for name, k in per.items():
+        assert {"whole", "ragged", "sub-tile"} <= k, (name, k)
+    assert len(fam) == 8, sorted(fam)
+    for f, imgs in fam.items():      # conv_rs serves W > 16 only: its smallest images are 3 x 17
+        assert ({(3, 17)} if f == "rs" else {(1, 1), (3, 5)}) <= imgs, (f, sorted(imgs))
+
+
+def test_w16_and_w17_pairs_in_every_family_whose_dispatch_depends_on_the_width():
+    table = set(CASES)
+    depends = {family_of(c) for c in CASES if instance_of(c) != instance_of(c._replace(W=33 - c.W if c.W in (16, 17) else c.W))}
+    pairs = {}
+    for c in CASES:
+        if c.W == 16 and c._replace(W=17) in table:
+            a, b = instance_of(c), instance_of(c._replace(W=17))
+            assert a != b
+            pairs.setdefault(family_of(c), set()).add((a, b))
+            pairs.setdefault(family_of(c._replace(W=17)), set()).add((a, b))
+    assert depends == set(pairs) == {"rs", "ws", "pipe-dma-128", "pipe-staged-128", "pipe-dma-64", "pipe-staged-64", "generic-fp32"}
+    wdep = {instance_of(c) for c in CASES if instance_of(c._replace(W=16)) != instance_of(c._replace(W=17))}
+    assert wdep == {i for p in pairs.values() for ab in p for i in ab} and len(wdep) == 24
+
+
+def test_features_are_spread_over_every_instance_that_supports_them():
+    by = {}
+    for c in CASES:
+        by.setdefault(instance_of(c), []).append(c)
+    for name, cs in by.items():
+        rs, ws5 = name.startswith("conv_rs"), name.startswith("conv_ws_kernel<bf16,5")      # conv_ws<5> runs only what conv_rs
+        pro, dma = cs[0].prologue, family_of(cs[0]).startswith("pipe-dma")                  # refuses: a bias, so no statistics
+        assert all(c.prologue == pro for c in cs), name
+        assert any(c.CO2 and c.CO1 != c.CO2 for c in cs), f"{name}: no case with two destinations"
+        assert {c.stats for c in cs} == ({False} if ws5 else {False, True}), f"{name}: statistics on and off"
+        if not pro and name != "conv_rs_kernel<1,false>":          # the prologue form has one source; one chunk cannot be split
+            two = [c for c in cs if c.CB]
+            assert two, f"{name}: no case with two sources"
+            assert any(c.CA != c.CB for c in two) or max(c.CA + c.CB for c in cs) <= 64, name     # 32 + 32 is the only split of 64
+        if not rs and not dma:
+            assert any(c.bias for c in cs), f"{name}: no case with a bias"
+        if rs or dma:
+            assert not any(c.bias for c in cs), name
+        if pro and any(writes_act(c.CA, c.CO1 + c.CO2, c.dtype) for c in cs) and not ws5:
+            assert any(c.act_out for c in cs), f"{name}: no case through segk_conv3x3_act"
+    # an odd chunk count over two sources forces the staged form of the producer/consumer kernel, at both channel tiles
+    odd = {instance_of(c) for c in CASES if c.CB and c.CA != c.CB and ((c.CA + c.CB) // 32) % 2 == 1 and not c.bias
+           and instance_of(c).startswith("conv3x3_pipe")}
+    assert odd == {f"conv3x3_pipe_kernel<{t},false,{bn},false>" for t in (4, 5) for bn in (128, 64)}
+    act = {family_of(c) for c in CASES if c.act_out}
+    assert act == {"ws", "rs", "pipe-staged-128", "pipe-staged-64"}
+    # mode-1 (data-gradient) weights on a whole-tile and a ragged image of every family
+    for f in {family_of(c) for c in CASES}:
+        kinds = {image_kind(c) for c in CASES if family_of(c) == f and c.mode == 1}
+        assert {"whole", "ragged"} <= kinds, (f, kinds)
+        assert {"whole", "ragged"} <= {image_kind(c) for c in CASES if family_of(c) == f and c.mode == 0}, f
+
+
+def test_three_or_more_units_per_workgroup_in_every_persistent_family():
+    assert all(units_per_workgroup(c) >= 3 for c in LONG_CASES), [units_per_workgroup(c) for c in LONG_CASES]
+    assert {family_of(c) for c in LONG_CASES} == set(PERSISTENT_FAMILIES)
+    assert all(c.stats and image_kind(c) == "ragged" for c in LONG_CASES)
+    # the three-run cases stay small: one unit per workgroup, a float64 reference below the cap
+    for c in CASES:
+        assert units_per_workgroup(c) == 1 and ref_madds(c) <= REF_MADD_CAP, c
+    assert len(CASES) <= 160 and sum(len(probe_passes(c)) for c in CASES) <= 500
+
+
+def test_impulse_probes():
+    for c in CASES:
+        TH, TW = tile_shape(c)
+        groups = probe_passes(c)
+        pts = [p for g in groups for p in g]
+        assert len(set(p[:3] for p in pts)) == len(pts) and len(groups) <= 8
+        for g in groups:
+            for p, q in itertools.combinations(g, 2):
+                assert p[0] != q[0] or abs(p[1] - q[1]) > 2 or abs(p[2] - q[2]) > 2
+        pix = {p[:3] for p in pts}
+        assert {(0, 0, 0), (0, 0, c.W - 1), (0, c.H - 1, 0), (0, c.H - 1, c.W - 1), (c.B - 1, c.H - 1, c.W - 1)} <= pix
+        for xb in range(TW, c.W, TW):
+            assert {(0, c.H // 2, xb - 1), (0, c.H // 2, xb)} <= pix
+        for yb in range(TH, c.H, TH):
+            assert {(c.B - 1, yb - 1, c.W // 2), (c.B - 1, yb, c.W // 2)} <= pix
+        la, lb, _, _ = logical_of(c)
+        ks = {p[3] for p in pts}
+        assert all(k < la or c.CA <= k < c.CA + lb for k in ks)
+        if len(pts) >= 6:
+            assert {0, la - 1} <= ks and (not c.CB or {c.CA, c.CA + lb - 1} & ks)
+
+
+@pytest.mark.timeout(600)
+def test_exact_runs_stay_exact():
+    """impulse: every term of the statistics is a multiple of 1/64 (1/64^2) and the sums stay below 2^24 units.  lattice:
+    2 K < 2^24, so every partial sum of the K products (multiples of 1/2, at most 1 each) is exact in fp32 in any order, and
+    the reference's own sum |z| and sum z^2 stay below 2^24 lattice units on every case that takes statistics."""
+    from conv_reference import impulse_expected, make_problem, stats_are_exact
+    for c in CASES + LONG_CASES:
+        assert 2 * 9 * (c.CA + c.CB) + 4 < 2 ** 24
+    for c in CASES:
+        if c.stats:
+            for probes in probe_passes(c):
+                z, _ = impulse_expected(make_problem(c, "impulse", probes), probes)
+                assert stats_are_exact(z, 1.0 / 64), c
+    for c in CASES + LONG_CASES:
+        if c.stats:
+            prob = make_problem(c, "lattice")
+            z = prob.fast_reference()
+            assert stats_are_exact(z, 0.5), c
+            assert float(z.abs().max()) >= 1.0, c
+            act = prob.activation()
+            assert 0.01 < float((act != 0).float().mean()) < 0.7, c

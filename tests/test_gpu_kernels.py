@@ -210,7 +210,8 @@ def test_conv3x3_bf16_register_stationary(ops):
 @pytest.mark.parametrize("C", [64, 128])
 def test_conv3x3_bf16_prologue_side_output(ops, C):
     """segk_conv3x3_act (second conv of a block): conv(relu(z*scale+shift)) plus the hidden activation itself as a
-    side output, on an image with partial tiles; C = 64 runs the weight-stationary, 128 the producer/consumer kernel"""
+    side output, on an image with partial tiles; C = 64 at W = 72 runs conv_rs_kernel<2,true> (segk_conv_use_rs: the
+    weight-stationary kernel keeps W <= 16), C = 128 the producer/consumer kernel"""
     from image_segmentation_amd import _lib
     dtype = torch.bfloat16
     B, H, W = 2, 40, 72
