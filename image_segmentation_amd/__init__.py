@@ -14,3 +14,4 @@ from .augment import (Augmenter, AugPlan, AugmentedBatches, merge_pairs, class_w
                       cubic_table, contrast_lut, laplace_table, rotation_plan, merge_plan, ALL_OPS, TARGET_REMAP)
 from .robustness import (PERTURBATIONS, DEFAULT_LEVELS, PerturbPlan, gauss_table, value_lut, perturb_plan, perturb,      # noqa: F401
                          robustness_sweep, cell_seed, image_seed)
+from .components import components, Components, Clean, mask_finish                                          # noqa: F401

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops, prompts
+from .components import Components, as_clean, components as _components
 from . import utils as U
 
 # app.py:187-208 -- the demo's palette and the two class-name tables
@@ -50,6 +51,8 @@ class Prediction:
     counts: torch.Tensor                    # int64 [C] pixels per predicted class
     confusion: Optional[torch.Tensor]       # int64 [C,C], [pred][label]; None without labels
     meta: dict                              # the resize / padding record of process_batch_forward
+    raw_mask: Optional[torch.Tensor] = None         # with clean=: the argmax before cleaning (mask is the cleaned one)
+    components: Optional[Components] = None    # with clean=: the components of raw_mask (components.py)
 
 
 def _num_classes(model):
@@ -132,10 +135,15 @@ class Segmenter:
               (the 8-bit Gaussian of the training data, sigma as given to the constructor; several clicks: the maximum of
               theirs) is made on the device by segk_prompt_heatmap and takes the route of a float heat-map
     labels    optional integer [H,W] / [1,H,W] maps at the images' own sizes: the confusion counts come from the same pass
-              (labels outside [0,C) are skipped, as the eval loops skip 255 / ignore)"""
+              (labels outside [0,C) are skipped, as the eval loops skip 255 / ignore)
+
+    clean=    None (every output as without it), or a components.Clean / a dict of its keywords (connectivity, classes,
+              min_area, keep_largest, max_components): the mask is cleaned on the device; Prediction.mask,
+              color, counts and confusion describe the cleaned mask, raw_mask is the argmax and components its components"""
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
-                 sigma=3.0):
+                 sigma=3.0, clean=None):
+        self.clean = as_clean(clean)
         if not float(sigma) > 0:
             raise ValueError(f"sigma must be positive, got {sigma}")
         self.sigma = float(sigma)
@@ -243,12 +251,22 @@ class Segmenter:
                 if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
                     raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
                 lab = lab.to(dev, non_blocking=True).long().contiguous()
-            _lib.call("segk_predict_mask", y[k].data_ptr(), mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(),
-                      ops._p(lab), ops._p(None if M is None else M[k]), C, T, pt, pl, nh, nw, oh, ow, mode, s)
-            preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
+            if self.clean is None:
+                _lib.call("segk_predict_mask", y[k].data_ptr(), mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(),
+                          ops._p(lab), ops._p(None if M is None else M[k]), C, T, pt, pl, nh, nw, oh, ow, mode, s)
+                preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
+                continue
+            # the argmax alone, its components and the cleaned mask, then the other outputs from the cleaned mask
+            _lib.call("segk_predict_mask", y[k].data_ptr(), mask.data_ptr(), None, None, None, None, None, C, T, pt, pl, nh, nw,
+                      oh, ow, mode, s)
+            cl = self.clean
+            comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
+            _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
+                      ops._p(None if M is None else M[k]), C, oh, ow, s)
+            preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
         return preds
 
 
 def predict(model, images, heatmaps=None, labels=None, points=None, **kw):
-    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels, points)."""
+    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels, points); clean= is a Segmenter keyword."""
     return Segmenter(model, **kw)(images, heatmaps=heatmaps, labels=labels, points=points)

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 315
-#define SEGK_ENTRY_COUNT 85
+#define SEGK_ABI_VERSION 316
+#define SEGK_ENTRY_COUNT 88
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -268,6 +268,39 @@ int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W
 int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts,
                       const int64_t* labels, uint64_t* M, int C, int T, int pad_top, int pad_left, int nh, int nw, int oh,
                       int ow, int mode, segk_stream_t s);
+
+/* ---- mask clean-up: connected components, boxes, blob removal (the reference has no such code: this
+ * replaces a mask.cpu() + scipy.ndimage.label post-process).  Integer arithmetic only: results are unique and bit-stable.
+ * No launch waits for another workgroup; several launches per call, in stream order.
+ *
+ * Workspace: ws holds SEGK_CC_WS_INTS(H, W) 32-bit words, 16-byte aligned, uninitialised; segk_cc_label fills it and
+ * segk_cc_clean reads it (and uses its vote words), so it must stay untouched between the two.  Layout, in words:
+ * best[8] as uint64 (16) | votes [H*W][8] | parent [H*W] | area [H*W] | id [H*W] | row counts [H] | row bases [H]. */
+#define SEGK_CC_TILE_W 64
+#define SEGK_CC_TILE_H 32
+#define SEGK_CC_MAX_PIXELS (1L << 28)
+#define SEGK_CC_WS_INTS(H, W) (16L + 11L * (long)(H) * (long)(W) + 2L * (long)(H))
+/* DESIGN.md 3.3 "components and ids", "what is recorded": mask [H,W] uint8 -> labels [H,W] int32 (0: unlabelled, else the
+ * id 1..K in ascending order of the component's first pixel), num[1] = K, and for the ids 1..min(K, max_components) the rows
+ * cls / area / first [max_components] and box [max_components][4] = (y0, x0, y1, x1), y1 and x1 exclusive; the rows past
+ * K are zeroed.  A pixel is labelled if its value is < 8 and bit `value` of class_mask is set.  connectivity 4 or 8.
+ * box and ws 16-byte aligned; H*W <= SEGK_CC_MAX_PIXELS.  The mask is only read. */
+int segk_cc_label(const uint8_t* mask, int32_t* labels, int32_t* num, int32_t* cls, int32_t* area, int32_t* box,
+                  int32_t* first, int32_t* ws, int H, int W, int connectivity, int class_mask, int max_components,
+                  segk_stream_t s);
+/* DESIGN.md 3.3 "removal", "new class of a removed component": after segk_cc_label on the same mask and ws.  A component
+ * is removed if area < min_area, or if bit `class` of keep_mask is set and it is not the largest of its class (tie: lowest
+ * id); its pixels take the class most of its standing 4-neighbours have (lowest class on a tie, its own with no votes).
+ * out [H,W] uint8 (not the mask itself) = the cleaned mask; kept / new_cls [max_components] for the reported ids, zero past
+ * K.  May be called again with other min_area / keep_mask on the same ws. */
+int segk_cc_clean(const uint8_t* mask, uint8_t* out, int32_t* ws, int32_t* kept, int32_t* new_cls, int H, int W,
+                  int min_area, int keep_mask, int max_components, segk_stream_t s);
+/* DESIGN.md 3.3 "finish from a mask": the optional outputs of segk_predict_mask, with its pointer rules, from a finished
+ * mask [H,W] uint8: color [H,W,3] = palette[mask], counts[8] += pixels per class, M[mask*8 + label] += 1 for labels inside
+ * [0,C) (the caller zeroes counts and M).  A mask value >= C is coloured black and counted nowhere.  1 <= C <= 8; mask and
+ * color 4-byte aligned; at least one output. */
+int segk_mask_finish(const uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels,
+                     uint64_t* M, int C, int H, int W, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -531,7 +531,90 @@ def perturb():
     print(f"perturb clock probe: median {clk['median_ghz']} GHz; written to {path}")
 
 
+def components():
+    """Mask clean-up through the C ABI (csrc/components.hip): segk_cc_label, segk_cc_clean (min_area 20, keep_largest of
+    classes 1 and 2) and segk_mask_finish on a 375 x 500 and a 1024 x 1024 mask -- smooth blobs with 2 % speckle (the
+    realistic case) and uniform 4-class noise (the worst case: a component every few pixels), connectivity 4 and 8.  Beside
+    them, on the same box: segk_predict_mask to the same size from a 224 x 224 slot, and the U-Net forward per image (3 -> 4
+    classes, B = 32, 224 x 224, the compute dtype in force).  Device-event times, warmed, 100 repetitions per round, seven
+    rounds: median and min..max.  Also written to profiles/kbench_components.json (or the file given with --out)."""
+    import json
+    import image_segmentation_amd as seg
+    from image_segmentation_amd.components import ws_ints
+    from image_segmentation_amd.utils import _geometry
+    st = ops._stream()
+    T, cap = 224, 1024
+
+    def rounds(fn, iters=100):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return {"median": t[3], "min": t[0], "max": t[-1]}
+
+    def blobs(H, W, g):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        m = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+        for c, (cy, cx, ry, rx) in ((1, (0.35, 0.3, 0.25, 0.2)), (2, (0.65, 0.7, 0.22, 0.25))):
+            d = ((yy - cy * H) / (ry * H)) ** 2 + ((xx - cx * W) / (rx * W)) ** 2
+            m[d <= 1.0] = c
+            m[(d > 1.0) & (d <= 1.25)] = 3
+        hit = torch.rand((H, W), generator=g, device="cuda") < 0.02
+        return torch.where(hit, torch.randint(0, 4, (H, W), generator=g, device="cuda", dtype=torch.uint8), m)
+
+    model = seg.unet(3, 4).cuda().eval()
+    X = torch.randn((32, 3, T, T), device="cuda")
+    with torch.no_grad():
+        model(X)
+        tfwd = rounds(lambda: model(X), 10)
+    fwd_us = tfwd["median"] / 32
+    print(f"components: U-Net forward B=32 {T}x{T} {tfwd['median']:9.1f} us [{tfwd['min']:.1f}..{tfwd['max']:.1f}] = {fwd_us:7.1f} us per image")
+    rows = []
+    g = torch.Generator(device="cuda").manual_seed(0)
+    pal = torch.tensor([(0, 0, 0), (255, 0, 0), (0, 255, 0), (0, 0, 255)], dtype=torch.uint8, device="cuda")
+    for H, W in ((375, 500), (1024, 1024)):
+        nh, nw, pt, pl, _ = _geometry(H, W, T)
+        slot = torch.randn((4, T, T), device="cuda")
+        pm, color = torch.empty((H, W), dtype=torch.uint8, device="cuda"), torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
+        counts = torch.zeros(8, dtype=torch.int64, device="cuda")
+        tp = rounds(lambda: _lib.call("segk_predict_mask", slot.data_ptr(), pm.data_ptr(), color.data_ptr(), pal.data_ptr(),
+                                      counts.data_ptr(), None, None, 4, T, pt, pl, nh, nw, H, W, 0, st))
+        print(f"components {H}x{W}: segk_predict_mask {tp['median']:8.1f} us [{tp['min']:.1f}..{tp['max']:.1f}]")
+        for kind in ("blobs", "noise4"):
+            m = blobs(H, W, g) if kind == "blobs" else torch.randint(0, 4, (H, W), generator=g, device="cuda", dtype=torch.uint8)
+            i32 = dict(dtype=torch.int32, device="cuda")
+            labels, num, ws = torch.empty((H, W), **i32), torch.empty(1, **i32), torch.empty(ws_ints(H, W), **i32)
+            r, box, out = torch.empty((5, cap), **i32), torch.empty((cap, 4), **i32), torch.empty_like(m)
+            for conn in (4, 8):
+                f_l = lambda: _lib.call("segk_cc_label", m.data_ptr(), labels.data_ptr(), num.data_ptr(), r[0].data_ptr(), r[1].data_ptr(),
+                                        box.data_ptr(), r[2].data_ptr(), ws.data_ptr(), H, W, conn, 255, cap, st)
+                f_c = lambda: _lib.call("segk_cc_clean", m.data_ptr(), out.data_ptr(), ws.data_ptr(), r[3].data_ptr(), r[4].data_ptr(), H, W,
+                                        20, 0b110, cap, st)
+                f_f = lambda: _lib.call("segk_mask_finish", out.data_ptr(), color.data_ptr(), pal.data_ptr(), counts.data_ptr(), None, None,
+                                        4, H, W, st)
+                f_l(); f_c(); f_f()
+                K, changed = int(num.item()), int((out != m).sum())
+                tl, tc, tf = rounds(f_l), rounds(f_c), rounds(f_f)
+                total = tl["median"] + tc["median"] + tf["median"]
+                rows.append({"size": [H, W], "mask": kind, "connectivity": conn, "components": K, "pixels_changed": changed,
+                             "label_us": tl, "clean_us": tc, "mask_finish_us": tf, "predict_mask_us": tp,
+                             "forward_us_per_image": fwd_us, "label_clean_finish_over_forward": total / fwd_us})
+                print(f"components {H}x{W} {kind:6s} c{conn} K={K:7d} changed={changed:7d}  label {tl['median']:8.1f} us "
+                      f"[{tl['min']:.1f}..{tl['max']:.1f}]   clean {tc['median']:8.1f} us [{tc['min']:.1f}..{tc['max']:.1f}]   "
+                      f"finish {tf['median']:7.1f} us [{tf['min']:.1f}..{tf['max']:.1f}]   sum = {total / fwd_us:5.2f} x forward per image")
+    clk = ops.clock_probe()
+    res = {"rows": rows, "forward_B32_us": tfwd, "compute_dtype": str(seg.get_compute_dtype()), "clock_probe_ghz": clk["median_ghz"],
+           "build_id": _lib.build_id(), "T": T, "max_components": cap}
+    path = os.path.join(ROOT, "profiles", "kbench_components.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(f"components clock probe: median {clk['median_ghz']} GHz; written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "components":
+        components()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "perturb":
         perturb()
         sys.exit(0)

@@ -5,7 +5,10 @@ DIR/<name>_mask.png (8-bit class indices) and, while the palette covers the clas
 Usage: python tools/predict.py --model {unet,autoencoder,prompt} --checkpoint F --classes 4 --size 224 --out DIR IMG...
 --model prompt is the prompt model (a ViT-B/16 ClipUNet built from its configuration, no hub access: every weight comes
 from the checkpoint of the whole PromptModel) and needs --point Y,X (repeatable; the clicks apply to every image).  A ClipUNet
-alone is driven from the library: Segmenter(model)."""
+alone is driven from the library: Segmenter(model).
+--min-area N / --keep-largest [CLASSES] / --connectivity {4,8} clean every mask on the device first (small and
+non-largest components take their neighbours' class); --boxes FILE.json writes, per image, the class, area and box
+(y0, x0, y1, x1; exclusive ends) of the components that stayed."""
 import argparse
 import os
 import sys
@@ -27,6 +30,12 @@ def main():
     ap.add_argument("--interpolation", choices=["bilinear", "nearest"], default="bilinear")
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--min-area", type=int, default=0, metavar="N", help="remove components of fewer than N pixels")
+    ap.add_argument("--keep-largest", nargs="?", const="all", default=None, metavar="CLASSES",
+                    help="keep only the largest component of each class (or of the comma-separated CLASSES)")
+    ap.add_argument("--connectivity", type=int, choices=[4, 8], default=4)
+    ap.add_argument("--max-components", type=int, default=1024, help="components reported per image in --boxes")
+    ap.add_argument("--boxes", metavar="FILE.json", help="write the kept components' class, area and box per image")
     ap.add_argument("images", nargs="+", metavar="IMG")
     args = ap.parse_args()
     try:
@@ -38,6 +47,17 @@ def main():
     if (args.model == "prompt") != bool(clicks):
         ap.error("--model prompt needs --point Y,X, and --point needs --model prompt")
 
+    keep = False
+    if args.keep_largest is not None:
+        try:
+            keep = True if args.keep_largest == "all" else tuple(int(c) for c in args.keep_largest.split(","))
+        except ValueError:
+            ap.error("--keep-largest takes comma-separated class numbers")
+    clean = None
+    if args.min_area > 0 or keep is not False or args.boxes:
+        clean = dict(connectivity=args.connectivity, min_area=args.min_area, keep_largest=keep, max_components=args.max_components)
+
+    import json
     import numpy as np
     from PIL import Image
     import image_segmentation_amd as seg
@@ -53,7 +73,8 @@ def main():
     model = seg.load_checkpoint(model, args.checkpoint).cuda()
     palette = seg.COLOR_MAP if args.classes <= len(seg.COLOR_MAP) else None
     segmenter = seg.Segmenter(model, target_size=args.size, interpolation=args.interpolation, palette=palette,
-                              batch_size=args.batch_size, sigma=args.sigma)
+                              batch_size=args.batch_size, sigma=args.sigma, clean=clean)
+    boxes = {}
     os.makedirs(args.out, exist_ok=True)
     names = seg.CLASS_NAMES["prompt_model" if clicks else "standard"]
     for i in range(0, len(args.images), args.batch_size):
@@ -67,6 +88,15 @@ def main():
                 Image.fromarray(pred.color.cpu().numpy(), "RGB").save(stem + "_color.png")
             counts = pred.counts.tolist()
             print(p, " ".join(f"{names.get(k, k)}={c}" for k, c in enumerate(counts)))
+            if args.boxes:
+                c = pred.components
+                k = min(c.n, args.max_components)
+                rows = zip(c.kept[:k].tolist(), c.cls[:k].tolist(), c.area[:k].tolist(), c.box[:k].tolist())
+                boxes[p] = {"components": c.n, "reported": k,
+                            "kept": [{"class": cl, "name": names.get(cl, str(cl)), "area": a, "box": b} for kp, cl, a, b in rows if kp]}
+    if args.boxes:
+        with open(args.boxes, "w") as f:
+            json.dump(boxes, f, indent=1)
 
 
 if __name__ == "__main__":
