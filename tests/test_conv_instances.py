@@ -20,8 +20,8 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def parse_instance(mangled):
-    """Mangled kernel name -> the spelling instance_of() uses; None for a 1x1 / ConvTranspose (GEO == 1) instance and for
-    anything that is not a convolution kernel.  (The mangled name is parsed because c++filt garbles __bf16, DF16b.)"""
+    """Mangled kernel name -> the spelling instance_of() uses; None for a 1x1 / ConvTranspose (GEO == 1) instance (those belong
+    to tests/test_gemm_instances.py) and for anything that is not a convolution kernel.  (The mangled name is parsed because c++filt garbles __bf16, DF16b.)"""
     b = lambda v: "true" if v == "1" else "false"
     m = re.search(r"14conv_rs_kernelILi(\d)ELb([01])EE", mangled)
     if m:
@@ -55,7 +55,7 @@ def compiled_instances():
         assert all("conv" in r["name"] for r in rows), [r["name"] for r in rows]
         names += [n for n in (parse_instance(r["name"]) for r in rows) if n is not None]
         geo1 = [r["name"] for r in rows if parse_instance(r["name"]) is None]
-        assert all(re.search(r"17conv_igemm_kernelI(DF16b|f)Li1E", n) for n in geo1), geo1      # only GEO == 1 is ignored
+        assert all(re.search(r"17conv_igemm_kernelI(DF16b|f)Li1E", n) for n in geo1), geo1      # only GEO == 1 is ignored here: tests/test_gemm_instances.py accounts for it
     assert len(set(names)) == len(names)
     return set(names)
 
