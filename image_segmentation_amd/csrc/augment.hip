@@ -338,7 +338,8 @@ static int check_batch(const char* what, const void* descs, int n, int T) {
   return 0;
 }
 
-int segk_aug_prefilter_impl(const segk_aug_desc* descs, int n, int max_tiles, hipStream_t st) {
+extern "C" int segk_aug_prefilter(const segk_aug_desc* descs, int n, int max_tiles, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   if (int rc = check_batch("aug_prefilter", descs, n, 1)) return rc;
   // a rotated 8192 x 8192 image has sides of at most 11586: 725^2 tiles of 16 x 16
   SEGK_REQUIRE(max_tiles >= 1 && max_tiles <= 725 * 725, "aug_prefilter: max_tiles=%d (1..%d)", max_tiles, 725 * 725);
@@ -347,9 +348,10 @@ int segk_aug_prefilter_impl(const segk_aug_desc* descs, int n, int max_tiles, hi
   return 0;
 }
 
-int segk_aug_resample_impl(const segk_aug_desc* descs, int n, int T, const int32_t* cub_idx, const int16_t* cub_coef, int n_cub,
-                           const uint8_t* contrast, int n_contrast, const int16_t* laplace, int n_laplace,
-                           const uint8_t* label_lut, float* X, uint8_t* X8, long long* y, hipStream_t st) {
+extern "C" int segk_aug_resample(const segk_aug_desc* descs, int n, int T, const int32_t* cub_idx, const int16_t* cub_coef,
+                                 int n_cub, const uint8_t* contrast, int n_contrast, const int16_t* laplace, int n_laplace,
+                                 const uint8_t* label_lut, float* X, uint8_t* X8, int64_t* y, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   if (int rc = check_batch("aug_resample", descs, n, T)) return rc;
   SEGK_REQUIRE(cub_idx && cub_coef && n_cub >= 1 && n_cub <= 65535, "aug_resample: cubic tables (NULL, or %d rows: 1..65535)", n_cub);
   SEGK_REQUIRE(n_contrast >= 0 && n_contrast <= 65535 && (n_contrast == 0 || contrast),
@@ -360,24 +362,26 @@ int segk_aug_resample_impl(const segk_aug_desc* descs, int n, int T, const int32
   SEGK_REQUIRE(((uintptr_t)cub_idx & 3) == 0 && ((uintptr_t)cub_coef & 7) == 0 && ((uintptr_t)laplace & 3) == 0 &&
                ((uintptr_t)X & 3) == 0 && ((uintptr_t)y & 7) == 0, "aug_resample: misaligned buffer");
   hipLaunchKernelGGL(aug_resample_kernel, dim3(cdiv(T * T, 256), n), dim3(256), 0, st, descs, T, cub_idx, cub_coef, n_cub,
-                     contrast, n_contrast, laplace, n_laplace, label_lut, X, X8, y);
+                     contrast, n_contrast, laplace, n_laplace, label_lut, X, X8, (long long*)y);
   SEGK_CHECK_LAUNCH("aug_resample");
   return 0;
 }
 
-int segk_aug_merge_impl(const segk_merge_desc* descs, const int32_t* tables, int n, int T, const uint8_t* label_lut, float* X,
-                        uint8_t* X8, long long* y, hipStream_t st) {
+extern "C" int segk_aug_merge(const segk_merge_desc* descs, const int32_t* tables, int n, int T, const uint8_t* label_lut,
+                              float* X, uint8_t* X8, int64_t* y, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   if (int rc = check_batch("aug_merge", descs, n, T)) return rc;
   SEGK_REQUIRE(tables && ((uintptr_t)tables & 3) == 0, "aug_merge: NULL or misaligned index tables");
   SEGK_REQUIRE(X || X8, "aug_merge: no image output (X and X8 are NULL)");
   SEGK_REQUIRE(((uintptr_t)X & 3) == 0 && ((uintptr_t)y & 7) == 0, "aug_merge: misaligned buffer");
-  hipLaunchKernelGGL(aug_merge_kernel, dim3(cdiv(T * T, 256), n), dim3(256), 0, st, descs, tables, T, label_lut, X, X8, y);
+  hipLaunchKernelGGL(aug_merge_kernel, dim3(cdiv(T * T, 256), n), dim3(256), 0, st, descs, tables, T, label_lut, X, X8, (long long*)y);
   SEGK_CHECK_LAUNCH("aug_merge");
   return 0;
 }
 
-int segk_label_hist_impl(const void* labels, long n, int elem_bytes, int num_classes, int has_ignore, long ignore_index,
-                         unsigned long long* counts, hipStream_t st) {
+extern "C" int segk_label_hist(const void* labels, long n, int elem_bytes, int num_classes, int has_ignore, long ignore_index,
+                               uint64_t* counts, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(labels && counts, "label_hist: NULL pointer");
   SEGK_REQUIRE(n >= 1 && n <= (1L << 40), "label_hist: n=%ld (1..2^40)", n);
   SEGK_REQUIRE(elem_bytes == 1 || elem_bytes == 8, "label_hist: labels of %d bytes (uint8: 1, int64: 8)", elem_bytes);
@@ -388,15 +392,16 @@ int segk_label_hist_impl(const void* labels, long n, int elem_bytes, int num_cla
   const int blocks = (int)(want < 1024 ? want : 1024);
   if (elem_bytes == 1)
     hipLaunchKernelGGL(label_hist_kernel<uint8_t>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)labels, (long long)n,
-                       num_classes, has_ignore, (long long)ignore_index, counts);
+                       num_classes, has_ignore, (long long)ignore_index, (unsigned long long*)counts);
   else
     hipLaunchKernelGGL(label_hist_kernel<long long>, dim3(blocks), dim3(256), 0, st, (const long long*)labels, (long long)n,
-                       num_classes, has_ignore, (long long)ignore_index, counts);
+                       num_classes, has_ignore, (long long)ignore_index, (unsigned long long*)counts);
   SEGK_CHECK_LAUNCH("label_hist");
   return 0;
 }
 
-int segk_rgb_label_to_classes_impl(const uint8_t* rgb, uint8_t* out, long n, hipStream_t st) {
+extern "C" int segk_rgb_label_to_classes(const uint8_t* rgb, uint8_t* out, long n, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(rgb && out, "rgb_label_to_classes: NULL pointer");
   SEGK_REQUIRE(n >= 1 && n <= (1L << 38), "rgb_label_to_classes: n=%ld pixels (1..2^38)", n);
   hipLaunchKernelGGL(rgb_label_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rgb, out, (long long)n);

@@ -691,7 +691,8 @@ unsigned* segk_ticket_slot(int groups, hipStream_t st) {
 // diagnostics / tests: overwrite every ticket counter of the current device with the low 32 bits of `pattern` (what an
 // aborted launch, or a stray store, would leave behind); every launch that draws a ticket afterwards must still elect
 // exactly one finisher
-int segk_debug_poison_tickets_impl(unsigned long long pattern, hipStream_t st) {
+extern "C" int segk_debug_poison_tickets(uint64_t pattern, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   unsigned* base = nullptr;
   SEGK_REQUIRE(hipGetSymbolAddress((void**)&base, HIP_SYMBOL(g_tickets)) == hipSuccess, "poison_tickets: no ticket array");
   static unsigned host[TICKET_SLOTS * TICKET_GROUPS];
@@ -701,9 +702,10 @@ int segk_debug_poison_tickets_impl(unsigned long long pattern, hipStream_t st) {
   return 0;
 }
 
-int segk_bn_finalize_impl(const float* part, int MT, int C, int C_real, double count, const float* conv_bias,
-                          const float* gamma, const float* beta, float* rmean, float* rvar, float momentum, float eps,
-                          int training, float* scale, float* shift, float* mean, float* rstd, hipStream_t st) {
+extern "C" int segk_bn_finalize(const float* part, int MT, int C, int C_real, double count, const float* conv_bias,
+                                const float* gamma, const float* beta, float* rmean, float* rvar, float momentum, float eps,
+                                int training, float* scale, float* shift, float* mean, float* rstd, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_finalize: bad channels C=%d real=%d", C, C_real);
   SEGK_REQUIRE(gamma && beta && scale && shift, "bn_finalize: null pointer");
   if (training) SEGK_REQUIRE(part && MT > 0 && count > 0 && mean && rstd, "bn_finalize: training needs partials");
@@ -747,15 +749,19 @@ static int bn_relu_apply_t(const void* z, void* y, const float* scale, const flo
   SEGK_CHECK_LAUNCH("bn_relu_apply");
   return 0;
 }
-int segk_bn_relu_apply_impl(const void* z, void* y, const float* scale, const float* shift, long P, int C, int dtype,
-                            hipStream_t st) {
+extern "C" int segk_bn_relu_apply(const void* z, void* y, const float* scale, const float* shift, long P, int C, int dtype,
+                                  segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("bn_relu_apply", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(z && y && scale && shift && P > 0 && C > 0 && C % 32 == 0, "bn_relu_apply: bad arguments");
   return dtype == SEGK_DT_BF16 ? bn_relu_apply_t<bf16_t>(z, y, scale, shift, P, C, st)
                                : bn_relu_apply_t<float>(z, y, scale, shift, P, C, st);
 }
 
-int segk_bn_relu_apply_pool_impl(const void* z, void* y, void* pooled, const float* scale, const float* shift, int B, int H,
-                                  int W, int C, int dtype, hipStream_t st) {
+extern "C" int segk_bn_relu_apply_pool(const void* z, void* y, void* pooled, const float* scale, const float* shift, int B,
+                                       int H, int W, int C, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("bn_relu_apply_pool", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(z && y && pooled && scale && shift && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 32 == 0,
                "bn_relu_apply_pool: bad arguments");
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
@@ -823,9 +829,11 @@ static int bn_bwd_from_part_t(const void* dy, const void* z, void* dz, const flo
   SEGK_CHECK_LAUNCH("bn_bwd_apply");
   return 0;
 }
-int segk_bn_bwd_from_part_impl(const void* dy, const void* z, void* dz, const float* scale, const float* shift,
-                               const float* mean, const float* rstd, long P, int C, int C_real, const float* part, int nb,
-                               float* dgamma, float* dbeta, float* coef, int dtype, hipStream_t st) {
+extern "C" int segk_bn_relu_bwd_from_part(const void* dy, const void* z, void* dz, const float* scale, const float* shift,
+                                          const float* mean, const float* rstd, long P, int C, int C_real, const float* part,
+                                          int nb, float* dgamma, float* dbeta, float* coef, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("bn_relu_bwd_from_part", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(dy && z && dz && scale && shift && mean && rstd && part && dgamma && dbeta && coef && nb > 0,
                "bn_bwd_from_part: bad arguments");
   SEGK_REQUIRE(P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_bwd_from_part: bad shape");
@@ -834,9 +842,11 @@ int segk_bn_bwd_from_part_impl(const void* dy, const void* z, void* dz, const fl
              : bn_bwd_from_part_t<float>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, nb, dgamma, dbeta, coef, st);
 }
 
-int segk_bn_bwd_impl(const void* dy, const void* z, void* dz, const float* scale, const float* shift, const float* mean,
-                     const float* rstd, long P, int C, int C_real, float* part, float* dgamma, float* dbeta, float* coef,
-                     int dtype, hipStream_t st) {
+extern "C" int segk_bn_relu_bwd(const void* dy, const void* z, void* dz, const float* scale, const float* shift,
+                                const float* mean, const float* rstd, long P, int C, int C_real, float* part, float* dgamma,
+                                float* dbeta, float* coef, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("bn_relu_bwd", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(dy && z && dz && scale && shift && mean && rstd && part && dgamma && dbeta && coef,
                "bn_bwd: null pointer");
   SEGK_REQUIRE(P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_bwd: bad shape");
@@ -845,7 +855,9 @@ int segk_bn_bwd_impl(const void* dy, const void* z, void* dz, const float* scale
              : bn_bwd_t<float>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st);
 }
 
-int segk_maxpool_fwd_impl(const void* x, void* y, int B, int H, int W, int C, int dtype, hipStream_t st) {
+extern "C" int segk_maxpool2x2_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("maxpool2x2_fwd", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && y && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 32 == 0, "maxpool_fwd: bad arguments");
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
   long total = (long)B * (H / 2) * (W / 2) * (C / vec);
@@ -860,8 +872,10 @@ int segk_maxpool_fwd_impl(const void* x, void* y, int B, int H, int W, int C, in
   return 0;
 }
 
-int segk_maxpool_bwd_impl(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate, int dtype,
-                          hipStream_t st) {
+extern "C" int segk_maxpool2x2_bwd(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate,
+                                   int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("maxpool2x2_bwd", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && dy && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 32 == 0, "maxpool_bwd: bad arguments");
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
   long total = (long)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / vec);
@@ -890,9 +904,11 @@ int segk_maxpool_bwd_stat_blocks(int B, int H, int W, int C, int dtype) {
   return (int)(g > 1024 ? 1024 : g);
 }
 
-int segk_maxpool_bwd_bnstat_impl(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate,
-                                 const float* scale, const float* shift, const float* mean, const float* rstd, float* part,
-                                 const void* z, int dtype, hipStream_t st) {
+extern "C" int segk_maxpool2x2_bwd_bnstat(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate,
+                                          const float* scale, const float* shift, const float* mean, const float* rstd,
+                                          float* part, const void* z, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("maxpool2x2_bwd_bnstat", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && dy && dx && scale && shift && mean && rstd && part, "maxpool_bwd_bnstat: null pointer");
   const int g = segk_maxpool_bwd_stat_blocks(B, H, W, C, dtype);
   SEGK_REQUIRE(g > 0, "maxpool_bwd_bnstat: shape not served (channel vectors must be a power of two)");
@@ -906,7 +922,9 @@ int segk_maxpool_bwd_bnstat_impl(const void* x, const void* dy, void* dx, int B,
   return 0;
 }
 
-int segk_channel_sum_impl(const void* x, long P, int C, int C_real, float* part, float* out, int dtype, hipStream_t st) {
+extern "C" int segk_channel_sum(const void* x, long P, int C, int C_real, float* part, float* out, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("channel_sum", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && part && out && P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "channel_sum: bad arguments");
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
   int cvb, rows, gy;

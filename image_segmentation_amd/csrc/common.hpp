@@ -26,6 +26,8 @@ extern thread_local char g_segk_err[512];
   do {                                                         \
     if (!(cond)) SEGK_FAIL(-2, __VA_ARGS__);                   \
   } while (0)
+#define SEGK_REQUIRE_DTYPE(name, dtype) \
+  SEGK_REQUIRE((dtype) == SEGK_DT_F32 || (dtype) == SEGK_DT_BF16, name ": bad dtype %d", dtype)
 #define SEGK_CHECK_LAUNCH(name)                                                        \
   do {                                                                                 \
     hipError_t e_ = hipGetLastError();                                                 \

@@ -28,26 +28,66 @@
 #include "common.hpp"
 #include "segk_internal.h"
 
-// pixel-tile geometry shared by the launcher and the BN-statistics sizing query (api.hip)
+// ---- the dispatch, stated once: which kernel form serves a call, with which tile (segk_internal.h: ConvPlan)
 // weight-stationary kernel: at most two 64-byte input chunks and N a multiple of 64 (but not a 128-wide layer
 // with a long K, which the MFMA-bound streaming kernel serves better)
-int segk_conv_use_ws(int cin_p, int n_p, int dtype) {
+static bool use_ws(int cin_p, int n_p, int dtype) {
   return dtype == SEGK_DT_BF16 && cin_p <= 64 && n_p % 64 == 0;   // bf16 performance mode only
 }
 // producer/consumer kernel (bf16 3x3, at least two 64-byte input chunks, not a weight-stationary layer): returns
 // its channel tile, 128 (256-pixel tiles) or 64 (512-pixel tiles, Cin >= 128: with K = 576 the unit boundary
 // dominates and the weight-stationary kernel wins), or 0
-int segk_conv_use_pipe(int cin_p, int n_p, int dtype) {
-  if (dtype != SEGK_DT_BF16 || segk_conv_use_ws(cin_p, n_p, dtype) || cin_p < 64) return 0;
+static int use_pipe(int cin_p, int n_p, int dtype) {
+  if (dtype != SEGK_DT_BF16 || use_ws(cin_p, n_p, dtype) || cin_p < 64) return 0;
   if (n_p % 128 == 0) return 128;
   if (n_p % 64 == 0 && cin_p >= 128) return 64;
   return 0;
 }
-int segk_conv_writes_act(int cin_p, int n_p, int dtype) {   // (conv_rs layers are a subset of these shapes)
-  return segk_conv_use_ws(cin_p, n_p, dtype) || segk_conv_use_pipe(cin_p, n_p, dtype) != 0;
+// Tile of the generic kernel for a layer whose N is a multiple of `unit` (128 | 64 | 32, the largest that divides it), on an
+// image wider than 16 pixels or not: BM = wm * mf * 32 pixels by BN = wn * nf * 32 channels (BN must divide N; with the
+// pixel-shuffle store a tile may span taps: each thread derives its own tap).  constexpr: the plan reads it at run time and
+// launch_geo takes its template arguments from it, so no shape is compiled that the plan cannot name.  wm == 0: no generic
+// kernel -- a bf16 3x3 layer with N % 128 == 0 is weight-stationary (Cin <= 64) or producer/consumer (Cin >= 96).
+struct GenericTile { int twl, wm, wn, mf, nf, pbuf; };
+static constexpr GenericTile generic_tile(int geo, bool bf16, int unit, bool wide) {
+  const int twl = wide ? 5 : 4;                    // 8x32 tiles unless the image is at most 16 wide
+  // bf16 1x1 / ConvTranspose GEMMs have a short K (Cin) and are bound by their output epilogue: 128-pixel tiles on
+  // 4-wave workgroups, two per CU, so one workgroup's epilogue overlaps the other's loads and MFMAs
+  if (geo == 1 && bf16 && unit >= 64) return {4, 2, 2, 2, unit == 128 ? 2 : 1, 2};
+  if (unit == 128) return geo == 0 && bf16 ? GenericTile{0, 0, 0, 0, 0, 0} : GenericTile{twl, 4, 2, 2, 2, 2};   // 256 px x 128 ch, 8 waves
+  if (geo == 0) return unit == 64 ? GenericTile{4, 2, 2, 2, 1, 1}           // 128 px x 64 ch, 4 waves
+                                  : GenericTile{4, 4, 1, 1, 1, 1};          // 128 px x 32 ch, 4 waves
+  return unit == 64 ? GenericTile{twl, 4, 2, 2, 1, 2} : GenericTile{twl, 8, 1, 1, 1, 2};
 }
-int segk_conv_bm(int geo, int unit) { return (unit % 128 == 0 || geo != 0) ? 256 : 128; }
-int segk_conv_twl(int bm, int W) { return bm == 128 ? 4 : (W > 16 ? 5 : 4); }   // 8x16 | 8x32 | 16x16 tiles
+
+ConvPlan segk_conv_plan(int geo, int dtype, int cin_p, int n_p, int W, bool has_bias, bool gemm_dma) {
+  ConvPlan p{};
+  p.wide = W > 16;
+  p.twl = p.wide ? 5 : 4;                            // 8x32 | 16x16 (16x32 | 32x16 at 512 pixels) tiles
+  p.bm = 256;
+  if (geo == 0 && segk_conv_use_rs(cin_p, n_p, dtype, W) && !has_bias) {
+    // narrow high-resolution layers, images wider than 16 pixels: register-stationary streaming kernel (conv_rs.hip); it
+    // carries no bias, a biased layer goes on to the weight-stationary kernel
+    p.form = CONV_RS; p.bn = 64; p.rs_rows = true;
+  } else if (geo == 0 && use_ws(cin_p, n_p, dtype)) {      // narrow high-resolution layers (64-channel tiles)
+    p.form = CONV_WS; p.bn = 64;
+  } else if (geo == 0 && use_pipe(cin_p, n_p, dtype)) {    // MFMA-bound bf16 layers
+    p.form = CONV_PIPE; p.bn = use_pipe(cin_p, n_p, dtype); p.bm = 32768 / p.bn;
+  } else if (gemm_dma) {                            // long-K GEMMs (ViT projections, ConvTranspose up-sampling and its data gradient)
+    p.form = CONV_GEMM_DMA; p.bn = 128; p.twl = 0;  // rows, not pixel tiles: gemm.hip picks 256 or 320 of them
+  } else {
+    p.form = CONV_GENERIC;
+    p.unit = n_p % 128 == 0 ? 128 : n_p % 64 == 0 ? 64 : 32;
+    const GenericTile g = generic_tile(geo, dtype == SEGK_DT_BF16, p.unit, p.wide);
+    p.twl = g.twl; p.wm = g.wm; p.wn = g.wn; p.mf = g.mf; p.nf = g.nf; p.pbuf = g.pbuf;
+    p.bm = g.wm * g.mf * 32; p.bn = g.wn * g.nf * 32;
+  }
+  return p;
+}
+// conv_rs, conv_ws and the producer/consumer kernel can; the width only chooses between the first two
+int segk_conv_writes_act(int cin_p, int n_p, int dtype) {
+  return segk_conv_plan(0, dtype, cin_p, n_p, /*W=*/17, false, false).form != CONV_GENERIC;
+}
 
 namespace {
 
@@ -71,8 +111,6 @@ template <> struct Mma<float> {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
   }
 };
-
-static int num_cus() { return segk_num_cus(); }
 
 // Tile: BM = WM*MF*32 output pixels (TH x TW, TW = 1 << TWL) by BN = WN*NF*32 output channels, WM*WN waves.
 // PBUF: patch buffers (2 = next chunk staged under the current chunk's MFMAs; 1 = smaller LDS footprint so
@@ -1440,8 +1478,12 @@ __global__ __launch_bounds__(512, 2) void conv_ws_kernel(const ConvArgs a) {
   }
 }
 
+// every launcher: the tile it was instantiated for is the plan's, which sized the caller's statistics buffer
+#define SEGK_REQUIRE_PLAN_TILE(name, p, BM, TWL) \
+  SEGK_REQUIRE((p).bm == (BM) && (p).twl == (TWL), name ": instantiated for a %d-pixel tile (twl %d), the plan says %d (twl %d)", BM, TWL, (p).bm, (p).twl)
+
 template <typename T, int TWL, bool PRO>
-int launch_ws(ConvArgs a, hipStream_t st) {
+int launch_ws(ConvArgs a, const ConvPlan& p, hipStream_t st) {
   using E = ET<T>;
   constexpr int BM = 256, BN = 64, NTHR = 512;
   constexpr int TW = 1 << TWL, TH = BM >> TWL, PW = TW + 2, PH = TH + 2;
@@ -1449,32 +1491,18 @@ int launch_ws(ConvArgs a, hipStream_t st) {
   constexpr size_t lds = 2 * (size_t)PH * ROWP + 2 * 9 * (size_t)BN * PIXB + NTHR * 16;
   static_assert(lds <= 160 * 1024, "conv_ws: LDS exceeds 160 KiB");
   static_assert(BM * (BN * E::ES + 16) + 4 * BN * 8 <= 2 * PH * ROWP, "output staging tile fits in the patch region");
+  SEGK_REQUIRE_PLAN_TILE("conv_ws", p, BM, TWL);
   a.twl = TWL;
   a.tiles_x = cdiv(a.W, TW);
   a.tiles_y = cdiv(a.H, TH);
-  const int NT = a.Ntot / BN;
-  const int MT = a.B * a.tiles_x * a.tiles_y;
-  int gw = num_cus() / 8;                                  // one workgroup per CU
-  gw -= gw % NT;
-  const int need = ((MT + 7) / 8) * NT;
-  if (gw > need) gw = need;
-  if (gw < NT) gw = NT;
+  int gw, GW;                                              // one workgroup per CU
+  segk_conv_rs_grid(a.B * a.tiles_x * a.tiles_y, a.Ntot / BN, &gw, &GW);
   a.persistent = 1;
-  auto kern = conv_ws_kernel<T, TWL, PRO>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};     // per device: the attribute is device state
-  const int dev = segk_device_index();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "conv_ws: cannot raise dynamic LDS limit");
-    attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(8 * gw), dim3(NTHR), lds, st, a);
-  SEGK_CHECK_LAUNCH("conv_ws");
-  return 0;
+  return segk_launch_lds<conv_ws_kernel<T, TWL, PRO>>("conv_ws", 160 * 1024, dim3(8 * gw), dim3(NTHR), lds, st, a);
 }
 
 template <int TWL, bool PRO, int BN, bool DMA>
-int launch_pipe_m(ConvArgs a, hipStream_t st) {
+int launch_pipe_m(ConvArgs a, const ConvPlan& p, hipStream_t st) {
   constexpr int BM = 32768 / BN, NTHR = 512;
   constexpr int TW = 1 << TWL, TH = BM >> TWL, PW = TW + 2, PH = TH + 2;
   constexpr int PPIX = DMA ? 64 : 96, WPIX = 64;
@@ -1483,29 +1511,20 @@ int launch_pipe_m(ConvArgs a, hipStream_t st) {
   // + a trash KiB and the statistics exchange (4 waves x 64 channels x 2 floats, 4 flags) / the producers' trash slots
   constexpr size_t lds = DMA ? ring + 1024 + 4 * 64 * 8 + 64 : ring + (NTHR / 2) * 16;
   static_assert(lds <= 160 * 1024, "conv3x3_pipe: LDS exceeds 160 KiB");
+  SEGK_REQUIRE_PLAN_TILE("conv3x3_pipe", p, BM, TWL);
   a.twl = TWL;
   a.tiles_x = cdiv(a.W, TW);
   a.tiles_y = cdiv(a.H, TH);
   const int units = a.B * a.tiles_x * a.tiles_y * (a.Ntot / BN);
   const int per_xcd = (units + 7) / 8;
-  int gw = num_cus() / 8;                                  // one 8-wave workgroup per CU
+  int gw = segk_num_cus() / 8;                             // one 8-wave workgroup per CU
   if (gw > per_xcd) gw = per_xcd;
   a.persistent = 1;
-  auto kern = conv3x3_pipe_kernel<TWL, PRO, BN, DMA>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};
-  const int dev = segk_device_index();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "conv3x3_pipe: cannot raise dynamic LDS limit");
-    attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(8 * gw), dim3(NTHR), lds, st, a);
-  SEGK_CHECK_LAUNCH("conv3x3_pipe");
-  return 0;
+  return segk_launch_lds<conv3x3_pipe_kernel<TWL, PRO, BN, DMA>>("conv3x3_pipe", 160 * 1024, dim3(8 * gw), dim3(NTHR), lds, st, a);
 }
 
 template <int TWL, bool PRO, int BN>
-int launch_pipe(ConvArgs a, hipStream_t st) {
+int launch_pipe(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
   if constexpr (!PRO) {
     // LDS-DMA producers (round 4): layers without a BatchNorm prologue and without a bias (the register epilogue carries none)
     // whose chunk count is even (the patch ring's parity across the unit boundary) and whose sources stay below 4 GiB (32-bit
@@ -1515,13 +1534,13 @@ int launch_pipe(ConvArgs a, hipStream_t st) {
     int cmax = a.CA > a.CB ? a.CA : a.CB;
     cmax = cmax > a.CO1 ? cmax : a.CO1;
     cmax = cmax > a.CO2 ? cmax : a.CO2;
-    if (nchunks % 2 == 0 && px * cmax * 2 < 4294967296LL && a.bias == nullptr) return launch_pipe_m<TWL, PRO, BN, true>(a, st);
+    if (nchunks % 2 == 0 && px * cmax * 2 < 4294967296LL && a.bias == nullptr) return launch_pipe_m<TWL, PRO, BN, true>(a, p, st);
   }
-  return launch_pipe_m<TWL, PRO, BN, false>(a, st);
+  return launch_pipe_m<TWL, PRO, BN, false>(a, p, st);
 }
 
 template <typename T, int GEO, int TWL, int WM, int WN, int MF, int NF, int PBUF, bool PRO>
-int launch_pro(ConvArgs a, hipStream_t st) {
+int launch_pro(ConvArgs a, const ConvPlan& p, hipStream_t st) {
   using E = ET<T>;
   constexpr int BM = WM * MF * 32, BN = WN * NF * 32, NTHR = WM * WN * 64;
   constexpr int HALO = (GEO == 0) ? 1 : 0;
@@ -1529,6 +1548,7 @@ int launch_pro(ConvArgs a, hipStream_t st) {
   constexpr int TW = 1 << TWL, TH = BM >> TWL;
   constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO;
   constexpr int ROWP = (PW * PIXB + 255) & ~255;
+  SEGK_REQUIRE_PLAN_TILE("conv_igemm", p, BM, TWL);
   a.twl = TWL;
   a.tiles_x = cdiv(a.W, TW);
   a.tiles_y = cdiv(a.H, TH);
@@ -1542,91 +1562,83 @@ int launch_pro(ConvArgs a, hipStream_t st) {
   int wg_per_cu = (int)((160 * 1024) / lds);
   const int wg_cap = (NTHR == 512) ? 1 : 2;
   if (wg_per_cu > wg_cap) wg_per_cu = wg_cap;
-  int gw = (num_cus() / 8) * wg_per_cu;
+  int gw = (segk_num_cus() / 8) * wg_per_cu;
   if (gw > per_xcd) gw = per_xcd;
   a.persistent = 1;
-  auto kern = conv_igemm_kernel<T, GEO, TWL, WM, WN, MF, NF, PBUF, PRO>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};  // idempotent; racing setters write the same value
-  const int dev = segk_device_index();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "conv_igemm: cannot raise dynamic LDS limit");
-    attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(8 * gw), dim3(NTHR), lds, st, a);
-  SEGK_CHECK_LAUNCH("conv_igemm");
-  return 0;
-}
-
-template <typename T, int GEO, int TWL, int WM, int WN, int MF, int NF, int PBUF>
-int launch_cfg(const ConvArgs& a, hipStream_t st) {
-  if constexpr (GEO == 0) {
-    if (a.scale) return launch_pro<T, GEO, TWL, WM, WN, MF, NF, PBUF, true>(a, st);
-  }
-  return launch_pro<T, GEO, TWL, WM, WN, MF, NF, PBUF, false>(a, st);
+  return segk_launch_lds<conv_igemm_kernel<T, GEO, TWL, WM, WN, MF, NF, PBUF, PRO>>("conv_igemm", 160 * 1024, dim3(8 * gw),
+                                                                                     dim3(NTHR), lds, st, a);
 }
 
 template <typename T, int GEO>
 int launch_geo(const ConvArgs& a, hipStream_t st) {
-  // BN must divide N (with the pixel-shuffle store a tile may span taps: each thread derives its own tap)
-  const int unit = a.Ntot;
-  const bool wide = a.W > 16;                      // 8x32 tiles unless the image is at most 16 wide
-  if constexpr (GEO == 0 && sizeof(T) == 2) {
-    // narrow high-resolution layers, images wider than 16 pixels: register-stationary streaming kernel (conv_rs.hip)
-    if (segk_conv_use_rs(a.CA + a.CB, a.Ntot, SEGK_DT_BF16, a.W)) {
-      if (!a.bias) return segk_conv_rs_launch(a, st);
-      // a biased layer falls through to the weight-stationary kernel, whose statistics rows are per tile while
-      // segk_conv_tiles() sized the buffer for conv_rs: the combination is refused instead of overrunning it
-      SEGK_REQUIRE(!a.stats, "conv3x3: bias together with BatchNorm statistics is not served for this layer shape");
+  constexpr bool BF = sizeof(T) == 2;
+  const int dtype = BF ? SEGK_DT_BF16 : SEGK_DT_F32, cin = a.CA + a.CB;
+  GemmArgs g{};
+  const int mode = a.shuffle ? 1 : (a.unshuf ? 2 : 0);
+  bool gemm_dma = false;
+  if constexpr (GEO == 1 && BF) {
+    g.A = a.srcA; g.w = (const char*)a.w; g.bias = a.bias; g.out = a.out;
+    g.M = (long)a.B * a.H * a.W; g.N = a.Ntot; g.nchA = a.CA / 32; g.nchunks = a.unshuf ? 4 * g.nchA : g.nchA; g.lda = a.CA;
+    g.H = a.H; g.W = a.W; g.Cout = a.CO1; g.act = a.act;
+    gemm_dma = !a.srcB && !a.out2 && !a.stats && segk_gemm_dma_ok(g.M, g.nchunks, g.nchA, g.N, g.Cout, g.lda, mode);
+  }
+  const ConvPlan p = segk_conv_plan(GEO, dtype, cin, a.Ntot, a.W, a.bias != nullptr, gemm_dma);
+  // segk_conv_tiles() does not know the bias.  A biased conv_rs shape is served by the weight-stationary kernel, whose
+  // statistics rows are per tile while the query sized the buffer for conv_rs: the combination is refused instead of
+  // overrunning it
+  SEGK_REQUIRE(!a.stats || p.rs_rows == segk_conv_plan(GEO, dtype, cin, a.Ntot, a.W, false, gemm_dma).rs_rows,
+               "conv3x3: bias together with BatchNorm statistics is not served for this layer shape");
+  // run-time fields of the plan (and the prologue flag of the call) -> template arguments
+  auto by_twl = [&](auto f) { return p.twl == 5 ? f(std::integral_constant<int, 5>{}) : f(std::integral_constant<int, 4>{}); };
+  auto by_wide = [&](auto f) { return p.wide ? f(std::true_type{}) : f(std::false_type{}); };
+  auto by_pro = [&](auto f) {
+    if constexpr (GEO == 0) {                     // the BatchNorm prologue is a 3x3 feature
+      if (a.scale) return f(std::true_type{});
+    }
+    return f(std::false_type{});
+  };
+  switch (p.form) {
+    case CONV_RS:
+      if constexpr (GEO == 0 && BF) return segk_conv_rs_launch(a, p, st);
+      break;
+    case CONV_WS:
+      if constexpr (GEO == 0 && BF)
+        return by_twl([&](auto TWLc) {
+          return by_pro([&](auto PROc) { return launch_ws<T, decltype(TWLc)::value, decltype(PROc)::value>(a, p, st); });
+        });
+      break;
+    case CONV_PIPE:
+      if constexpr (GEO == 0 && BF)
+        return by_twl([&](auto TWLc) {
+          return by_pro([&](auto PROc) {
+            constexpr int TWL = decltype(TWLc)::value;
+            constexpr bool PRO = decltype(PROc)::value;
+            return p.bn == 128 ? launch_pipe<TWL, PRO, 128>(a, p, st) : launch_pipe<TWL, PRO, 64>(a, p, st);
+          });
+        });
+      break;
+    case CONV_GEMM_DMA:
+      if constexpr (GEO == 1 && BF) return segk_gemm_dma_launch(g, mode, st);
+      break;
+    case CONV_GENERIC: {
+      // the template arguments are generic_tile's at the plan's (unit, wide), evaluated at compile time
+      auto by_unit = [&](auto UNITc) {
+        return by_wide([&](auto WIDEc) {
+          return by_pro([&](auto PROc) {
+            constexpr GenericTile G = generic_tile(GEO, BF, decltype(UNITc)::value, decltype(WIDEc)::value);
+            if constexpr (G.wm != 0)
+              return launch_pro<T, GEO, G.twl, G.wm, G.wn, G.mf, G.nf, G.pbuf, decltype(PROc)::value>(a, p, st);
+            else
+              SEGK_FAIL(-2, "conv_igemm: no generic kernel for a bf16 3x3 layer with N %% 128 == 0");
+          });
+        });
+      };
+      return p.unit == 128 ? by_unit(std::integral_constant<int, 128>{})
+           : p.unit == 64 ? by_unit(std::integral_constant<int, 64>{})
+                          : by_unit(std::integral_constant<int, 32>{});
     }
   }
-  if constexpr (GEO == 0 && sizeof(T) == 2) {
-    // narrow high-resolution layers: weight-stationary streaming kernel (64-channel tiles)
-    if (segk_conv_use_ws(a.CA + a.CB, a.Ntot, sizeof(T) == 2 ? SEGK_DT_BF16 : SEGK_DT_F32)) {
-      if (a.scale) return wide ? launch_ws<T, 5, true>(a, st) : launch_ws<T, 4, true>(a, st);
-      return wide ? launch_ws<T, 5, false>(a, st) : launch_ws<T, 4, false>(a, st);
-    }
-  }
-  if constexpr (GEO == 0 && sizeof(T) == 2) {
-    const int pk = segk_conv_use_pipe(a.CA + a.CB, a.Ntot, SEGK_DT_BF16);   // MFMA-bound bf16 layers: producer/consumer kernel
-    if (pk == 128) {
-      if (a.scale) return wide ? launch_pipe<5, true, 128>(a, st) : launch_pipe<4, true, 128>(a, st);
-      return wide ? launch_pipe<5, false, 128>(a, st) : launch_pipe<4, false, 128>(a, st);
-    }
-    if (pk == 64) {
-      if (a.scale) return wide ? launch_pipe<5, true, 64>(a, st) : launch_pipe<4, true, 64>(a, st);
-      return wide ? launch_pipe<5, false, 64>(a, st) : launch_pipe<4, false, 64>(a, st);
-    }
-  }
-  if constexpr (GEO == 1 && sizeof(T) == 2) {
-    // long-K GEMMs (ViT projections, ConvTranspose up-sampling and its data gradient): producer/consumer kernel
-    const int mode = a.shuffle ? 1 : (a.unshuf ? 2 : 0);
-    const int nchA = a.CA / 32, nchunks = a.unshuf ? 4 * nchA : nchA;
-    const long M = (long)a.B * a.H * a.W;
-    if (!a.srcB && !a.out2 && !a.stats && segk_gemm_dma_ok(M, nchunks, nchA, a.Ntot, a.CO1, a.CA, mode)) {
-      GemmArgs g{};
-      g.A = a.srcA; g.w = (const char*)a.w; g.bias = a.bias; g.out = a.out;
-      g.M = M; g.N = a.Ntot; g.nchunks = nchunks; g.nchA = nchA; g.lda = a.CA; g.H = a.H; g.W = a.W; g.Cout = a.CO1;
-      g.act = a.act;
-      return segk_gemm_dma_launch(g, mode, st);
-    }
-  }
-  if constexpr (GEO == 1 && sizeof(T) == 2) {
-    // 1x1 / ConvTranspose GEMMs have a short K (Cin) and are bound by their output epilogue: 128-pixel tiles on
-    // 4-wave workgroups, two per CU, so one workgroup's epilogue overlaps the other's loads and MFMAs
-    if (unit % 128 == 0) return launch_cfg<T, GEO, 4, 2, 2, 2, 2, 2>(a, st);
-    if (unit % 64 == 0) return launch_cfg<T, GEO, 4, 2, 2, 2, 1, 2>(a, st);
-  }
-  if (unit % 128 == 0)                             // 256 px x 128 ch, 8 waves
-    return wide ? launch_cfg<T, GEO, 5, 4, 2, 2, 2, 2>(a, st) : launch_cfg<T, GEO, 4, 4, 2, 2, 2, 2>(a, st);
-  if constexpr (GEO == 0) {
-    if (unit % 64 == 0) return launch_cfg<T, GEO, 4, 2, 2, 2, 1, 1>(a, st);        // 128 px x 64 ch, 4 waves
-    return launch_cfg<T, GEO, 4, 4, 1, 1, 1, 1>(a, st);                            // 128 px x 32 ch, 4 waves
-  } else {
-    if (unit % 64 == 0)
-      return wide ? launch_cfg<T, GEO, 5, 4, 2, 2, 1, 2>(a, st) : launch_cfg<T, GEO, 4, 4, 2, 2, 1, 2>(a, st);
-    return wide ? launch_cfg<T, GEO, 5, 8, 1, 1, 1, 2>(a, st) : launch_cfg<T, GEO, 4, 8, 1, 1, 1, 2>(a, st);
-  }
+  SEGK_FAIL(-2, "conv_igemm: the plan names a kernel form (%d) that this geometry and dtype do not compile", (int)p.form);
 }
 
 }  // namespace
@@ -1635,7 +1647,7 @@ int segk_conv_igemm_launch(const ConvArgs& a, int geo, int dtype, hipStream_t st
   using F = ET<float>;
   using H = ET<bf16_t>;
   const int CH = (dtype == SEGK_DT_BF16) ? H::CH : F::CH;
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "conv_igemm: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("conv_igemm", dtype);
   SEGK_REQUIRE(geo == 0 || geo == 1, "conv_igemm: bad geometry %d", geo);
   SEGK_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0, "conv_igemm: bad shape B=%d H=%d W=%d", a.B, a.H, a.W);
   SEGK_REQUIRE(a.srcA && a.w && a.out, "conv_igemm: null pointer");

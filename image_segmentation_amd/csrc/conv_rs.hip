@@ -503,33 +503,23 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
 }
 
 template <int NCH, bool PRO>
-int launch_rs(ConvArgs a, hipStream_t st) {
+int launch_rs(ConvArgs a, const ConvPlan& p, hipStream_t st) {
   constexpr size_t lds = 3 * (size_t)NCH * RS_CHB + NCH * 256;
   static_assert(lds <= 160 * 1024, "conv_rs: LDS exceeds 160 KiB");
+  SEGK_REQUIRE(p.bm == 256 && p.twl == 5, "conv_rs: written for 8 x 32 tiles, the plan says %d pixels (twl %d)", p.bm, p.twl);
   a.tiles_x = cdiv(a.W, 32);
   a.tiles_y = cdiv(a.H, 8);
-  const int NT = a.Ntot / 64;
   int gw, GW;
-  segk_conv_rs_grid(a.B, a.H, a.W, NT, &gw, &GW);
+  segk_conv_rs_grid(a.B * a.tiles_x * a.tiles_y, a.Ntot / 64, &gw, &GW);
   a.persistent = 1;
-  auto kern = conv_rs_kernel<NCH, PRO>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};
-  const int dev = segk_device_index();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "conv_rs: cannot raise dynamic LDS limit");
-    attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(8 * gw), dim3(512), lds, st, a);
-  SEGK_CHECK_LAUNCH("conv_rs");
-  return 0;
+  return segk_launch_lds<conv_rs_kernel<NCH, PRO>>("conv_rs", 160 * 1024, dim3(8 * gw), dim3(512), lds, st, a);
 }
 
 }  // namespace
 
-// workgroups per XCD (gw, a multiple of the NT channel tiles) and per channel tile (GW); one workgroup per CU at most
-void segk_conv_rs_grid(int B, int H, int W, int NT, int* gw_out, int* GW_out) {
-  const int MT = B * cdiv(W, 32) * cdiv(H, 8);
+// workgroups per XCD (gw, a multiple of the NT channel tiles) and per channel tile (GW) for MT pixel tiles; one workgroup per
+// CU at most.  Shared with the weight-stationary kernel (conv_igemm.hip: launch_ws)
+void segk_conv_rs_grid(int MT, int NT, int* gw_out, int* GW_out) {
   int gw = segk_num_cus() / 8;
   gw -= gw % NT;
   const int need = ((MT + 7) / 8) * NT;
@@ -542,7 +532,7 @@ void segk_conv_rs_grid(int B, int H, int W, int NT, int* gw_out, int* GW_out) {
 // rows of BatchNorm partial sums the kernel writes: one per wave slab and workgroup of a channel tile
 int segk_conv_rs_rows(int B, int H, int W, int n_p) {
   int gw, GW;
-  segk_conv_rs_grid(B, H, W, n_p / 64, &gw, &GW);
+  segk_conv_rs_grid(B * cdiv(W, 32) * cdiv(H, 8), n_p / 64, &gw, &GW);
   return 8 * GW * 4;
 }
 
@@ -551,10 +541,10 @@ int segk_conv_use_rs(int cin_p, int n_p, int dtype, int W) {
   return dtype == SEGK_DT_BF16 && (cin_p == 32 || cin_p == 64) && n_p % 64 == 0 && W > 16;
 }
 
-int segk_conv_rs_launch(const ConvArgs& a, hipStream_t st) {
+int segk_conv_rs_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
   const int nch = (a.CA + a.CB) / 32;
   SEGK_REQUIRE(nch == 1 || nch == 2, "conv_rs: Cin=%d not served", a.CA + a.CB);
   SEGK_REQUIRE(a.Ntot % 64 == 0 && a.CO1 % 32 == 0 && !a.bias, "conv_rs: bad output configuration");
-  if (a.scale) return nch == 2 ? launch_rs<2, true>(a, st) : launch_rs<1, true>(a, st);
-  return nch == 2 ? launch_rs<2, false>(a, st) : launch_rs<1, false>(a, st);
+  if (a.scale) return nch == 2 ? launch_rs<2, true>(a, p, st) : launch_rs<1, true>(a, p, st);
+  return nch == 2 ? launch_rs<2, false>(a, p, st) : launch_rs<1, false>(a, p, st);
 }

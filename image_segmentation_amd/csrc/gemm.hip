@@ -268,32 +268,20 @@ __global__ __launch_bounds__(512, 2) void gemm_dma_kernel(const GemmArgs g) {
   }
 }
 
-static int g_num_cus() { return segk_num_cus(); }
-
 template <int MODE, int BM>
 int launch_dma(const GemmArgs& g, hipStream_t st) {
-  auto kern = gemm_dma_kernel<MODE, BM>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};     // per device: the attribute is device state
-  const int dev_ = segk_device_index();
-  if (!attr_set[dev_]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "gemm_dma: cannot raise dynamic LDS limit");
-    attr_set[dev_] = true;
-  }
   const long U = ((g.M + BM - 1) / BM) * (g.N / G_BN) * (g.ksplit > 1 ? g.ksplit : 1);
   const int per_xcd = (int)((U + 7) / 8);
-  int gw = g_num_cus() / 8;
+  int gw = segk_num_cus() / 8;
   if (gw > per_xcd) gw = per_xcd;
   constexpr int SLOT = (BM + 128) * 64, NSLOT = (6 * SLOT <= 160 * 1024) ? 6 : 5;
-  hipLaunchKernelGGL(kern, dim3(8 * gw), dim3(512), NSLOT * SLOT, st, g);
-  SEGK_CHECK_LAUNCH("gemm_dma");
-  return 0;
+  return segk_launch_lds<gemm_dma_kernel<MODE, BM>>("gemm_dma", 160 * 1024, dim3(8 * gw), dim3(512), NSLOT * SLOT, st, g);
 }
 
 // rounds of `units` work units on the chip's CUs, in units of one 256-row tile's time
 static double gemm_rounds(long M, int N, int ks, int bm) {
   const long units = ((M + bm - 1) / bm) * (long)(N / 128) * ks;
-  const long cus = g_num_cus();
+  const long cus = segk_num_cus();
   return (double)((units + cus - 1) / cus) * bm / 256.0;
 }
 

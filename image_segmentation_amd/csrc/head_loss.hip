@@ -610,9 +610,6 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
 }  // namespace
 
 template <typename T> static size_t head_lds() { return (size_t)HT * (HCH * ET<T>::ES + 16); }
-static bool raise_lds(const void* f) {
-  return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
-}
 
 // ------------------------------------------------------------------------------------------------
 #ifndef SEGK_HEAD_BLOCKS_CAP
@@ -629,11 +626,12 @@ int segk_head_part_floats(long P, int Cp) {
   return n > 0x7fffffffLL ? 0 : (int)n;
 }
 
-int segk_head_fwd_impl(const void* y, const float* w, const float* bias, float* logits, int B, int H, int W, int Cp,
-                       int C, int ncls, const float* zsc, const float* zsh, int dtype, hipStream_t st) {
+// zsc, zsh: BatchNorm scale / shift applied (with the ReLU) to a pre-activation input, or null for an activation
+static int head_fwd(const void* y, const float* w, const float* bias, float* logits, int B, int H, int W, int Cp, int C, int ncls,
+                    const float* zsc, const float* zsh, int dtype, hipStream_t st) {
   SEGK_REQUIRE(y && w && bias && logits && B > 0 && H > 0 && W > 0, "head_fwd: bad arguments");
   SEGK_REQUIRE((zsc == nullptr) == (zsh == nullptr), "head_fwd: scale and shift come together");
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "head_fwd: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("head_fwd", dtype);
   SEGK_REQUIRE(ncls >= 1 && ncls <= MAXC, "head_fwd: 1..%d classes supported, got %d", MAXC, ncls);
   SEGK_REQUIRE(Cp % 32 == 0 && C > 0 && C <= Cp, "head_fwd: bad channels");
   const long P = (long)B * H * W, HW = (long)H * W;
@@ -644,11 +642,8 @@ int segk_head_fwd_impl(const void* y, const float* w, const float* bias, float* 
   auto launch = [&](auto Tc, auto NCc) {
     using T = decltype(Tc);
     constexpr int NC = decltype(NCc)::value;
-    auto kern = head_fwd_kernel<T, NC>;
-    if (!raise_lds((const void*)kern)) return false;
-    hipLaunchKernelGGL(kern, dim3((int)g), dim3(256), head_lds<T>(), st, (const T*)y, w, bias, logits, P, HW, Cp, C, ncls, zsc,
-                       zsh);
-    return true;
+    return segk_launch_lds<head_fwd_kernel<T, NC>>("head_fwd", 96 * 1024, dim3((int)g), dim3(256), head_lds<T>(), st, (const T*)y, w,
+                                                   bias, logits, P, HW, Cp, C, ncls, zsc, zsh);
   };
   auto by_nc = [&](auto Tc) {
     if (ncls <= 2) return launch(Tc, std::integral_constant<int, 2>{});
@@ -656,10 +651,17 @@ int segk_head_fwd_impl(const void* y, const float* w, const float* bias, float* 
     if (ncls == 4) return launch(Tc, std::integral_constant<int, 4>{});
     return launch(Tc, std::integral_constant<int, MAXC>{});
   };
-  const bool ok = dtype == SEGK_DT_BF16 ? by_nc(bf16_t{}) : by_nc(float{});
-  SEGK_REQUIRE(ok, "head_fwd: cannot raise dynamic LDS limit");
-  SEGK_CHECK_LAUNCH("head_fwd");
-  return 0;
+  return dtype == SEGK_DT_BF16 ? by_nc(bf16_t{}) : by_nc(float{});
+}
+extern "C" int segk_head_fwd(const void* y, const float* w, const float* bias, float* logits, int B, int H, int W, int Cp, int C,
+                             int ncls, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("head_fwd", dtype);
+  return head_fwd(y, w, bias, logits, B, H, W, Cp, C, ncls, nullptr, nullptr, dtype, (hipStream_t)s);
+}
+extern "C" int segk_head_fwd_bn(const void* z, const float* scale, const float* shift, const float* w, const float* bias,
+                                float* logits, int B, int H, int W, int Cp, int C, int ncls, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE(scale && shift, "head_fwd_bn: null scale/shift");
+  return head_fwd(z, w, bias, logits, B, H, W, Cp, C, ncls, scale, shift, dtype, (hipStream_t)s);
 }
 
 template <typename T>
@@ -676,30 +678,28 @@ static int head_bwd_t(const float* dlog, const void* y, const float* w, void* dy
   // block's pixels and writes its own columns of the partial rows (tests/test_gpu_kernels.py at 288 and 512 channels)
   auto launch_z = [&](auto NCc, auto ZINc) {
     constexpr int NC = decltype(NCc)::value;
-    auto kern = head_bwd_kernel<T, NC, decltype(ZINc)::value>;
-    if (!raise_lds((const void*)kern)) return false;
-    hipLaunchKernelGGL(kern, dim3(nb, gy), dim3(256), lds, st, dlog, (const T*)y, w, (T*)dy, part, P, HW, Cp, C, ncls, cvb, rows,
-                       bn ? bn[0] : nullptr, bn ? bn[1] : nullptr, bn ? bn[2] : nullptr, bn ? bn[3] : nullptr, bnpart);
-    return true;
+    return segk_launch_lds<head_bwd_kernel<T, NC, decltype(ZINc)::value>>(
+        "head_bwd", 96 * 1024, dim3(nb, gy), dim3(256), lds, st, dlog, (const T*)y, w, (T*)dy, part, P, HW, Cp, C, ncls, cvb, rows,
+        bn ? bn[0] : nullptr, bn ? bn[1] : nullptr, bn ? bn[2] : nullptr, bn ? bn[3] : nullptr, bnpart);
   };
   auto launch = [&](auto NCc) { return zin ? launch_z(NCc, std::true_type{}) : launch_z(NCc, std::false_type{}); };
-  const bool ok = ncls <= 2 ? launch(std::integral_constant<int, 2>{})
-                : ncls == 3 ? launch(std::integral_constant<int, 3>{})
-                : ncls == 4 ? launch(std::integral_constant<int, 4>{})
-                            : launch(std::integral_constant<int, MAXC>{});
-  SEGK_REQUIRE(ok, "head_bwd: cannot raise dynamic LDS limit");
-  SEGK_CHECK_LAUNCH("head_bwd");
+  const int rc = ncls <= 2 ? launch(std::integral_constant<int, 2>{})
+               : ncls == 3 ? launch(std::integral_constant<int, 3>{})
+               : ncls == 4 ? launch(std::integral_constant<int, 4>{})
+                           : launch(std::integral_constant<int, MAXC>{});
+  if (rc) return rc;
   hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(cdiv(ncls * (C + 1), 4)), dim3(256), 0, st, part, nb, Cp, C, ncls, dw, db);
   SEGK_CHECK_LAUNCH("head_bwd_finalize");
   return 0;
 }
 
-int segk_head_bwd_impl(const float* dlog, const void* y, const float* w, void* dy, float* part, float* dw, float* db,
-                       int B, int H, int W, int Cp, int C, int ncls, const float* bn_scale, const float* bn_shift,
-                       const float* bn_mean, const float* bn_rstd, float* bnpart, int zin, int dtype, hipStream_t st) {
+// bnpart: also reduce the BatchNorm backward partials of the layer in front; zin: y is that layer's pre-activation
+static int head_bwd(const float* dlog, const void* y, const float* w, void* dy, float* part, float* dw, float* db, int B, int H,
+                    int W, int Cp, int C, int ncls, const float* bn_scale, const float* bn_shift, const float* bn_mean,
+                    const float* bn_rstd, float* bnpart, int zin, int dtype, hipStream_t st) {
   SEGK_REQUIRE(dlog && y && w && dy && part && dw && db && B > 0 && H > 0 && W > 0, "head_bwd: bad arguments");
   SEGK_REQUIRE(ncls >= 1 && ncls <= MAXC && Cp % 32 == 0 && C > 0 && C <= Cp, "head_bwd: bad channels/classes");
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "head_bwd: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("head_bwd", dtype);
   SEGK_REQUIRE(!(bnpart || zin) || (bn_scale && bn_shift && bn_mean && bn_rstd),
                "head_bwd: BatchNorm reductions / a pre-activation input need scale, shift, mean and rstd");
   const long P = (long)B * H * W, HW = (long)H * W;
@@ -709,7 +709,29 @@ int segk_head_bwd_impl(const float* dlog, const void* y, const float* w, void* d
   return dtype == SEGK_DT_BF16 ? head_bwd_t<bf16_t>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, st)
                                : head_bwd_t<float>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, st);
 }
-int segk_head_blocks_q(long P) { return segk_head_blocks(P); }
+extern "C" int segk_head_bwd(const float* dlogits, const void* y, const float* w, void* dy, float* part, float* dw, float* db,
+                             int B, int H, int W, int Cp, int C, int ncls, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("head_bwd", dtype);
+  return head_bwd(dlogits, y, w, dy, part, dw, db, B, H, W, Cp, C, ncls, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dtype,
+                  (hipStream_t)s);
+}
+extern "C" int segk_head_bwd_blocks(long P) { return segk_head_blocks(P); }
+extern "C" int segk_head_bwd_bnstat(const float* dlogits, const void* y, const float* w, void* dy, float* part, float* dw,
+                                    float* db, int B, int H, int W, int Cp, int C, int ncls, const float* scale,
+                                    const float* shift, const float* mean, const float* rstd, float* bnpart, int dtype,
+                                    segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("head_bwd_bnstat", dtype);
+  SEGK_REQUIRE(bnpart, "head_bwd_bnstat: null partials");
+  return head_bwd(dlogits, y, w, dy, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 0, dtype,
+                  (hipStream_t)s);
+}
+extern "C" int segk_head_bwd_bn(const float* dlogits, const void* z, const float* w, void* dy, float* part, float* dw, float* db,
+                                int B, int H, int W, int Cp, int C, int ncls, const float* scale, const float* shift,
+                                const float* mean, const float* rstd, float* bnpart, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE(scale && shift && mean && rstd, "head_bwd_bn: null BatchNorm vectors");
+  return head_bwd(dlogits, z, w, dy, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 1, dtype,
+                  (hipStream_t)s);
+}
 
 // ---- prompt model remix (prompt_based/prompt.py:33-56), 4 CLIP classes x 1 mask channel, fp32 NCHW ----
 //   p = softmax(clip_logits), m = sigmoid(mask_logit)
@@ -756,7 +778,8 @@ __global__ __launch_bounds__(256) void prompt_mix_bwd_kernel(const float* __rest
   }
 }
 
-int segk_prompt_mix_impl(const float* clip, const float* mask, const float* dout, float* out, int N, long HW, hipStream_t st) {
+// dout null: forward, out = final probabilities; else backward, out = gradient of the mask logit
+static int prompt_mix(const float* clip, const float* mask, const float* dout, float* out, int N, long HW, hipStream_t st) {
   SEGK_REQUIRE(clip && mask && out && N > 0 && HW > 0, "prompt_mix: bad arguments");
   const long P = (long)N * HW;
   SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
@@ -767,6 +790,15 @@ int segk_prompt_mix_impl(const float* clip, const float* mask, const float* dout
   SEGK_CHECK_LAUNCH("prompt_mix");
   return 0;
 }
+extern "C" int segk_prompt_mix_fwd(const float* clip_logits, const float* mask_logit, float* final_probs, int N, long HW,
+                                   segk_stream_t s) {
+  return prompt_mix(clip_logits, mask_logit, nullptr, final_probs, N, HW, (hipStream_t)s);
+}
+extern "C" int segk_prompt_mix_bwd(const float* clip_logits, const float* mask_logit, const float* dfinal, float* dmask_logit,
+                                   int N, long HW, segk_stream_t s) {
+  SEGK_REQUIRE(dfinal, "prompt_mix_bwd: null gradient");
+  return prompt_mix(clip_logits, mask_logit, dfinal, dmask_logit, N, HW, (hipStream_t)s);
+}
 
 int segk_loss_blocks(long P) {
   if (P <= 0) return 0;
@@ -776,9 +808,12 @@ int segk_loss_blocks(long P) {
 int segk_loss_part_floats(long P) { return segk_loss_blocks(P) * LP; }
 int segk_loss_state_floats(void) { return LS; }
 
-int segk_loss_fwd_impl(const float* logits, const long long* labels, const float* cw, int N, int C, long HW,
-                       int ignore_index, float smooth, float dice_weight, float ce_weight, float* part, float* state,
-                       float* loss_out, int prob, int nll_log, float eps, hipStream_t st) {
+// prob: the input holds probabilities (NLL with or without the logarithm, nll_log / eps), not logits (cross-entropy)
+static int loss_fwd(const float* logits, const int64_t* labels64, const float* cw, int N, int C, long HW, int ignore_index,
+                    float smooth, float dice_weight, float ce_weight, float* part, float* state, float* loss_out, int prob,
+                    int nll_log, float eps, segk_stream_t s) {
+  const long long* labels = (const long long*)labels64;
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(logits && labels && part && state && N > 0 && HW > 0, "loss_fwd: bad arguments");
   SEGK_REQUIRE(C >= 1 && C <= MAXC, "loss_fwd: 1..%d classes supported, got %d", MAXC, C);
   const long P = (long)N * HW;
@@ -802,10 +837,23 @@ int segk_loss_fwd_impl(const float* logits, const long long* labels, const float
   SEGK_CHECK_LAUNCH("loss_fwd");
   return 0;
 }
+extern "C" int segk_loss_fwd(const float* logits, const int64_t* labels, const float* cw, int N, int C, long HW, int ignore_index,
+                             float smooth, float dice_weight, float ce_weight, float* part, float* state, float* loss_out,
+                             segk_stream_t s) {
+  return loss_fwd(logits, labels, cw, N, C, HW, ignore_index, smooth, dice_weight, ce_weight, part, state, loss_out, 0, 0, 0.f, s);
+}
+extern "C" int segk_prob_loss_fwd(const float* probs, const int64_t* labels, const float* cw, int N, int C, long HW,
+                                  int ignore_index, float smooth, float dice_weight, float nll_weight, int nll_log, float eps,
+                                  float* part, float* state, float* loss_out, segk_stream_t s) {
+  return loss_fwd(probs, labels, cw, N, C, HW, ignore_index, smooth, dice_weight, nll_weight, part, state, loss_out, 1, nll_log,
+                  eps, s);
+}
 
-int segk_loss_bwd_impl(const float* logits, const long long* labels, const float* cw, const float* state,
-                       const float* gout, int N, int C, long HW, int ignore_index, float dice_weight, float ce_weight,
-                       float* dlogits, int prob, int nll_log, float eps, hipStream_t st) {
+static int loss_bwd(const float* logits, const int64_t* labels64, const float* cw, const float* state, const float* gout, int N,
+                    int C, long HW, int ignore_index, float dice_weight, float ce_weight, float* dlogits, int prob, int nll_log,
+                    float eps, segk_stream_t s) {
+  const long long* labels = (const long long*)labels64;
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(logits && labels && state && gout && dlogits && N > 0 && HW > 0 && C >= 1 && C <= MAXC, "loss_bwd: bad arguments");
   const long P = (long)N * HW;
   SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
@@ -827,15 +875,25 @@ int segk_loss_bwd_impl(const float* logits, const long long* labels, const float
   SEGK_CHECK_LAUNCH("loss_bwd");
   return 0;
 }
+extern "C" int segk_loss_bwd(const float* logits, const int64_t* labels, const float* cw, const float* state, const float* gout,
+                             int N, int C, long HW, int ignore_index, float dice_weight, float ce_weight, float* dlogits,
+                             segk_stream_t s) {
+  return loss_bwd(logits, labels, cw, state, gout, N, C, HW, ignore_index, dice_weight, ce_weight, dlogits, 0, 0, 0.f, s);
+}
+extern "C" int segk_prob_loss_bwd(const float* probs, const int64_t* labels, const float* cw, const float* state,
+                                  const float* gout, int N, int C, long HW, int ignore_index, float dice_weight,
+                                  float nll_weight, int nll_log, float eps, float* dprobs, segk_stream_t s) {
+  return loss_bwd(probs, labels, cw, state, gout, N, C, HW, ignore_index, dice_weight, nll_weight, dprobs, 1, nll_log, eps, s);
+}
 
-int segk_confusion_impl(const float* logits, const long long* labels, int N, int C, long HW, unsigned long long* M,
-                        hipStream_t st) {
+extern "C" int segk_confusion(const float* logits, const int64_t* labels, int N, int C, long HW, uint64_t* M, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(logits && labels && M && N > 0 && HW > 0 && C >= 1 && C <= MAXC, "confusion: bad arguments");
   const long P = (long)N * HW;
   SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
   long g = (P + 255) / 256;
   if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(confusion_kernel, dim3((int)g), dim3(256), 0, st, logits, labels, P, HW, C, M);
+  hipLaunchKernelGGL(confusion_kernel, dim3((int)g), dim3(256), 0, st, logits, (const long long*)labels, P, HW, C, (unsigned long long*)M);
   SEGK_CHECK_LAUNCH("confusion");
   return 0;
 }

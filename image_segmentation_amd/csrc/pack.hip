@@ -371,7 +371,9 @@ static int grid_for(long total) {
 
 }  // namespace
 
-int segk_nchw_to_nhwc_impl(const float* src, void* dst, int B, int C, int H, int W, int Cp, int dtype, hipStream_t st) {
+extern "C" int segk_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int Cp, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("nchw_to_nhwc", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0 && Cp >= C && Cp % 32 == 0, "nchw_to_nhwc: bad arguments");
   const long total = (long)B * H * W * (Cp / (dtype == SEGK_DT_BF16 ? 8 : 4));
   if (dtype == SEGK_DT_BF16)
@@ -382,7 +384,9 @@ int segk_nchw_to_nhwc_impl(const float* src, void* dst, int B, int C, int H, int
   return 0;
 }
 
-int segk_nhwc_to_nchw_impl(const void* src, float* dst, int B, int C, int H, int W, int Cp, int dtype, hipStream_t st) {
+extern "C" int segk_nhwc_to_nchw(const void* src, float* dst, int B, int C, int H, int W, int Cp, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("nhwc_to_nchw", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0 && Cp >= C, "nhwc_to_nchw: bad arguments");
   const long total = (long)B * H * W * C;
   if (dtype == SEGK_DT_BF16)
@@ -393,8 +397,10 @@ int segk_nhwc_to_nchw_impl(const void* src, float* dst, int B, int C, int H, int
   return 0;
 }
 
-int segk_pack_conv_weight_impl(const float* w, void* dst, int Cout, int CA, int CB, int Coutp, int CAp, int CBp,
-                               int taps, int mode, int dtype, hipStream_t st) {
+extern "C" int segk_pack_conv_weight(const float* w, void* dst, int Cout, int CA, int CB, int Coutp, int CAp, int CBp, int taps,
+                                     int mode, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("pack_conv_weight", dtype);
+  hipStream_t st = (hipStream_t)s;
   const int CH = dtype == SEGK_DT_BF16 ? 32 : 16;
   SEGK_REQUIRE(w && dst && Cout > 0 && CA > 0 && CB >= 0 && (taps == 9 || taps == 1) && (mode == 0 || mode == 1),
                "pack_conv_weight: bad arguments");
@@ -412,8 +418,10 @@ int segk_pack_conv_weight_impl(const float* w, void* dst, int Cout, int CA, int 
   return 0;
 }
 
-int segk_pack_conv3x3_both_impl(const float* w, void* dst_fwd, void* dst_dgrad, int Cout, int CA, int CB, int Coutp, int CAp,
-                                 int CBp, int dtype, hipStream_t st) {
+extern "C" int segk_pack_conv3x3_both(const float* w, void* dst_fwd, void* dst_dgrad, int Cout, int CA, int CB, int Coutp,
+                                      int CAp, int CBp, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("pack_conv3x3_both", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(w && dst_fwd && Cout > 0 && CA > 0 && CB >= 0, "pack_conv3x3_both: bad arguments");
   SEGK_REQUIRE(Coutp >= Cout && CAp >= CA && CBp >= CB && Coutp % 32 == 0 && CAp % 32 == 0 && CBp % 32 == 0 &&
                    (CBp == 0) == (CB == 0),
@@ -429,9 +437,10 @@ int segk_pack_conv3x3_both_impl(const float* w, void* dst_fwd, void* dst_dgrad, 
   return 0;
 }
 
-int segk_pack_multi_impl(const void* table, int n, int total_blocks, int dtype, hipStream_t st) {
+extern "C" int segk_pack_multi(const void* table, int n, int total_blocks, int dtype, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(table && n > 0 && n <= 64 && total_blocks > 0, "pack_multi: bad arguments");
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "pack_multi: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("pack_multi", dtype);
   if (dtype == SEGK_DT_BF16)
     hipLaunchKernelGGL(pack_multi_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, st, (const SegkPackEntry*)table, n);
   else
@@ -439,10 +448,12 @@ int segk_pack_multi_impl(const void* table, int n, int total_blocks, int dtype, 
   SEGK_CHECK_LAUNCH("pack_multi");
   return 0;
 }
-int segk_pack_convt_chunk_impl() { return PACK_CONVT_CHUNK; }
+extern "C" int segk_pack_convt_chunk(void) { return PACK_CONVT_CHUNK; }
 
-int segk_pack_convt_weight_impl(const float* w, void* dst, int Cin, int Cout, int Cinp, int Coutp, int mode, int dtype,
-                                hipStream_t st) {
+extern "C" int segk_pack_convt_weight(const float* w, void* dst, int Cin, int Cout, int Cinp, int Coutp, int mode, int dtype,
+                                      segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("pack_convt_weight", dtype);
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(w && dst && Cin > 0 && Cout > 0 && Cinp >= Cin && Coutp >= Cout && Cinp % 32 == 0 && Coutp % 32 == 0 &&
                    (mode == 0 || mode == 1),
                "pack_convt_weight: bad arguments");
@@ -458,7 +469,8 @@ int segk_pack_convt_weight_impl(const float* w, void* dst, int Cin, int Cout, in
 }
 
 // jobs: host array of n <= 4 segk_reduce_job (include/segk.h); see wgrad_reduce_multi_kernel
-int segk_wgrad_reduce_multi_impl(const segk_reduce_job* jobs, int n, hipStream_t st) {
+extern "C" int segk_wgrad_reduce_multi(const segk_reduce_job* jobs, int n, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(jobs && n >= 1 && n <= 4, "wgrad_reduce_multi: 1..4 jobs");
   ReduceJobs p{};
   p.n = n;
@@ -493,23 +505,16 @@ int segk_wgrad_reduce_multi_impl(const segk_reduce_job* jobs, int n, hipStream_t
       SEGK_FAIL(-2, "wgrad_reduce_multi: job %d: bad kind %d", i, q.kind);
     }
   }
-  if (lds > 48 * 1024) {
-    static bool attr_set[SEGK_MAX_DEVICES] = {};
-    const int dev = segk_device_index();
-    if (!attr_set[dev]) {
-      if (hipFuncSetAttribute((const void*)wgrad_reduce_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
-          hipSuccess)
-        SEGK_FAIL(-3, "wgrad_reduce_multi: cannot raise dynamic LDS limit");
-      attr_set[dev] = true;
-    }
-  }
+  if (lds > 48 * 1024)
+    if (const int rc = segk_raise_lds<wgrad_reduce_multi_kernel>("wgrad_reduce_multi", 64 * 1024)) return rc;
   hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), lds, st, p);
   SEGK_CHECK_LAUNCH("wgrad_reduce_multi");
   return 0;
 }
 
-int segk_wgrad_reduce_impl(const float* slabs, int S, float* grad, int N, int CA, int CB, int Np, int CAp, int CBp,
-                           int taps, hipStream_t st) {
+extern "C" int segk_wgrad_reduce(const float* slabs, int S, float* grad, int N, int CA, int CB, int Np, int CAp, int CBp,
+                                 int taps, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(slabs && grad && S > 0 && N > 0 && CA > 0 && CB >= 0 && Np >= N && CAp >= CA && CBp >= CB && taps > 0,
                "wgrad_reduce: bad arguments");
   if (S > 16) {      // many thin slabs (narrow layers): slab-parallel reduction, one launch

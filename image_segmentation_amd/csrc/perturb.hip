@@ -232,8 +232,9 @@ static int check_table(const char* what, const void* descs, int n, int total_til
   return 0;
 }
 
-int segk_perturb_point_impl(const segk_perturb_desc* descs, int n, int total_tiles, int kind, const void* table,
-                            hipStream_t st) {
+extern "C" int segk_perturb_point(const segk_perturb_desc* descs, int n, int total_tiles, int kind, const void* table,
+                                  segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   if (int rc = check_table("perturb_point", descs, n, total_tiles)) return rc;
   SEGK_REQUIRE(kind == K_LUT || kind == K_GAUSS || kind == K_SP || kind == K_OCC, "perturb_point: unknown kind %d (0..3)", kind);
   const bool needs = kind == K_LUT || kind == K_GAUSS;
@@ -249,7 +250,8 @@ int segk_perturb_point_impl(const segk_perturb_desc* descs, int n, int total_til
   return 0;
 }
 
-int segk_perturb_blur_impl(const segk_perturb_desc* descs, int n, int total_tiles, int k, hipStream_t st) {
+extern "C" int segk_perturb_blur(const segk_perturb_desc* descs, int n, int total_tiles, int k, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   if (int rc = check_table("perturb_blur", descs, n, total_tiles)) return rc;
   SEGK_REQUIRE(k >= 0 && k <= BK, "perturb_blur: %d passes (0..%d: the halo one tile holds)", k, BK);
   if (total_tiles == 0) return 0;

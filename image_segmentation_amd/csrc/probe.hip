@@ -82,10 +82,11 @@ __global__ __launch_bounds__(256) void clock_probe_kernel(unsigned long long* __
 }
 }  // namespace
 
-int segk_clock_probe_impl(unsigned long long* out, int blocks, int iters, int shape, hipStream_t st) {
+extern "C" int segk_clock_probe(uint64_t* out, int blocks, int iters, int shape, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(out && blocks > 0 && blocks <= 4096 && iters > 0 && (shape == 0 || shape == 1), "clock_probe: bad arguments");
-  if (shape == 1) hipLaunchKernelGGL(clock_probe_kernel<true>, dim3(blocks), dim3(256), 0, st, out, iters);
-  else hipLaunchKernelGGL(clock_probe_kernel<false>, dim3(blocks), dim3(256), 0, st, out, iters);
+  if (shape == 1) hipLaunchKernelGGL(clock_probe_kernel<true>, dim3(blocks), dim3(256), 0, st, (unsigned long long*)out, iters);
+  else hipLaunchKernelGGL(clock_probe_kernel<false>, dim3(blocks), dim3(256), 0, st, (unsigned long long*)out, iters);
   SEGK_CHECK_LAUNCH("clock_probe");
   return 0;
 }

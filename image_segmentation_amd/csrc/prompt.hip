@@ -279,23 +279,25 @@ static int check_image(const char* what, int H, int W) {
   return 0;
 }
 
-int segk_prompt_scores_impl(const long long* labels, const uint8_t* lut, const int* centers, const double* w, int nw, int R,
-                            double* scores, int* cls, int B, int K, int H, int W, hipStream_t st) {
+extern "C" int segk_prompt_scores(const int64_t* labels, const uint8_t* lut, const int* centers, const double* w, int nw, int R,
+                                  double* scores, int* cls, int B, int K, int H, int W, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(labels && centers && w && scores && cls, "prompt_scores: NULL pointer");
   SEGK_REQUIRE(B > 0 && B < 65536 && K > 0 && K <= (1 << 20), "prompt_scores: B=%d (1..65535), K=%d (1..2^20)", B, K);
   if (int rc = check_image("prompt_scores", H, W)) return rc;
   SEGK_REQUIRE(R >= 0 && R <= 4096 && nw > 0, "prompt_scores: R=%d (0..4096), nw=%d (> 0)", R, nw);
   SEGK_REQUIRE(((uintptr_t)labels & 7) == 0 && ((uintptr_t)centers & 7) == 0 && ((uintptr_t)w & 7) == 0 &&
                ((uintptr_t)scores & 15) == 0 && ((uintptr_t)cls & 3) == 0, "prompt_scores: misaligned buffer");
-  hipLaunchKernelGGL(prompt_scores_kernel, dim3(cdiv(K, 4), B), dim3(256), 0, st, labels, lut, (const int2*)centers, w, nw, R,
+  hipLaunchKernelGGL(prompt_scores_kernel, dim3(cdiv(K, 4), B), dim3(256), 0, st, (const long long*)labels, lut, (const int2*)centers, w, nw, R,
                      scores, cls, K, H, W);
   SEGK_CHECK_LAUNCH("prompt_scores");
   return 0;
 }
 
-int segk_prompt_make_impl(const long long* labels, const uint8_t* lut, const int* centers, const int* cls, const uint8_t* q,
-                          int nq, float* heat, long long* target, int* classes, int* out_centers, uint8_t* valid, int B, int K,
-                          int per_image, int H, int W, hipStream_t st) {
+extern "C" int segk_prompt_make(const int64_t* labels, const uint8_t* lut, const int* centers, const int* cls, const uint8_t* q,
+                                int nq, float* heat, int64_t* target, int* classes, int* out_centers, uint8_t* valid, int B,
+                                int K, int per_image, int H, int W, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(labels && centers && cls && q && heat && target && classes && out_centers && valid, "prompt_make: NULL pointer");
   SEGK_REQUIRE(B > 0 && B < 65536 && K > 0 && K <= (1 << 20), "prompt_make: B=%d (1..65535), K=%d (1..2^20)", B, K);
   SEGK_REQUIRE(per_image >= 1 && per_image <= MAXPI, "prompt_make: per_image=%d (1..%d)", per_image, MAXPI);
@@ -308,16 +310,18 @@ int segk_prompt_make_impl(const long long* labels, const uint8_t* lut, const int
                ((uintptr_t)cls & 3) == 0 && ((uintptr_t)classes & 3) == 0, "prompt_make: misaligned buffer");
   const dim3 grid((HW / (vec ? 4 : 1) + 255) / 256, B);
   if (vec)
-    hipLaunchKernelGGL(prompt_make_kernel<true>, grid, dim3(256), 0, st, labels, lut, (const int2*)centers, cls, q, nq, heat,
-                       target, classes, (int2*)out_centers, valid, K, per_image, H, W, HW);
+    hipLaunchKernelGGL(prompt_make_kernel<true>, grid, dim3(256), 0, st, (const long long*)labels, lut, (const int2*)centers, cls, q, nq, heat,
+                       (long long*)target, classes, (int2*)out_centers, valid, K, per_image, H, W, HW);
   else
-    hipLaunchKernelGGL(prompt_make_kernel<false>, grid, dim3(256), 0, st, labels, lut, (const int2*)centers, cls, q, nq, heat,
-                       target, classes, (int2*)out_centers, valid, K, per_image, H, W, HW);
+    hipLaunchKernelGGL(prompt_make_kernel<false>, grid, dim3(256), 0, st, (const long long*)labels, lut, (const int2*)centers, cls, q, nq, heat,
+                       (long long*)target, classes, (int2*)out_centers, valid, K, per_image, H, W, HW);
   SEGK_CHECK_LAUNCH("prompt_make");
   return 0;
 }
 
-int segk_prompt_heatmap_impl(const int* points, int P, const uint8_t* q, int nq, float* heat, int H, int W, hipStream_t st) {
+extern "C" int segk_prompt_heatmap(const int* points, int P, const uint8_t* q, int nq, float* heat, int H, int W,
+                                   segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(points && q && heat, "prompt_heatmap: NULL pointer");
   SEGK_REQUIRE(P >= 1 && P <= MAXPTS, "prompt_heatmap: %d points (1..%d)", P, MAXPTS);
   if (int rc = check_image("prompt_heatmap", H, W)) return rc;

@@ -242,9 +242,10 @@ int segk_mse_blocks(long n) {
   return (int)(g < 1 ? 1 : (g > MSE_MAX_BLOCKS ? MSE_MAX_BLOCKS : g));
 }
 
-int segk_recon_head_fwd_impl(const void* x, const float* w, const float* bias, float* rec, int B, int H, int W, int Cp,
-                             int Cin, int Cout, int dtype, hipStream_t st) {
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "recon_head_fwd: bad dtype %d", dtype);
+extern "C" int segk_recon_head_fwd(const void* x, const float* w, const float* bias, float* rec, int B, int H, int W, int Cp,
+                                   int Cin, int Cout, int dtype, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  SEGK_REQUIRE_DTYPE("recon_head_fwd", dtype);
   SEGK_REQUIRE(x && w && rec && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "recon_head_fwd: bad arguments");
   SEGK_REQUIRE(Cp % 32 == 0 && Cin <= Cp, "recon_head_fwd: Cp=%d must be a multiple of 32 holding Cin=%d", Cp, Cin);
   SEGK_REQUIRE(((uintptr_t)x & 15) == 0, "recon_head_fwd: the act tensor must be 16-byte aligned");
@@ -264,9 +265,10 @@ int segk_recon_head_fwd_impl(const void* x, const float* w, const float* bias, f
   return 0;
 }
 
-int segk_recon_sigmoid_bwd_impl(const float* drec, const float* rec, void* dz, int B, int H, int W, int C, int Cp, int dtype,
-                                hipStream_t st) {
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "recon_sigmoid_bwd: bad dtype %d", dtype);
+extern "C" int segk_recon_sigmoid_bwd(const float* drec, const float* rec, void* dz, int B, int H, int W, int C, int Cp,
+                                      int dtype, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  SEGK_REQUIRE_DTYPE("recon_sigmoid_bwd", dtype);
   SEGK_REQUIRE(drec && rec && dz && B > 0 && H > 0 && W > 0 && C > 0, "recon_sigmoid_bwd: bad arguments");
   SEGK_REQUIRE(Cp % 32 == 0 && C <= Cp, "recon_sigmoid_bwd: Cp=%d must be a multiple of 32 holding C=%d", Cp, C);
   SEGK_REQUIRE(((uintptr_t)dz & 15) == 0, "recon_sigmoid_bwd: dz must be 16-byte aligned");
@@ -283,8 +285,9 @@ int segk_recon_sigmoid_bwd_impl(const float* drec, const float* rec, void* dz, i
   return 0;
 }
 
-int segk_mse_fwd_impl(const float* a, const float* b, float* part, int part_floats, float* out, long n, int mean,
-                      hipStream_t st) {
+extern "C" int segk_mse_fwd(const float* a, const float* b, float* part, int part_floats, float* out, long n, int mean,
+                            segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(a && b && part && out && n > 0 && part_floats > 0, "mse_fwd: bad arguments");
   SEGK_REQUIRE(mean == 0 || mean == 1, "mse_fwd: mean must be 0 (sum) or 1 (mean), got %d", mean);
   SEGK_REQUIRE(((uintptr_t)part & 7) == 0, "mse_fwd: part must be 8-byte aligned (it holds fp64 partials)");
@@ -297,8 +300,9 @@ int segk_mse_fwd_impl(const float* a, const float* b, float* part, int part_floa
   return 0;
 }
 
-int segk_mse_bwd_impl(const float* a, const float* b, const float* gout, float* da, float* db, long n, int mean,
-                      hipStream_t st) {
+extern "C" int segk_mse_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long n, int mean,
+                            segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(a && b && gout && da && n > 0, "mse_bwd: bad arguments");
   SEGK_REQUIRE(mean == 0 || mean == 1, "mse_bwd: mean must be 0 (sum) or 1 (mean), got %d", mean);
   const float norm = mean ? (float)(2.0 / (double)n) : 2.0f;      // aten mse_loss_backward: 2/numel (mean) or 2 (sum)

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_y_kernel(const float* __rest
 extern "C" int segk_bilinear_fwd(const void* x, void* y, int B, int IH, int IW, int OH, int OW, int Cp, int dtype,
                                  segk_stream_t s) {
   SEGK_REQUIRE(x && y && B > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && Cp > 0 && Cp % 32 == 0, "bilinear_fwd: bad arguments");
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "bilinear_fwd: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("bilinear_fwd", dtype);
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
   long g = ((long)B * OH * OW * (Cp / vec) + 255) / 256;
   if (g > 8192) g = 8192;
@@ -181,7 +181,7 @@ extern "C" int segk_bilinear_fwd(const void* x, void* y, int B, int IH, int IW, 
 extern "C" int segk_bilinear_bwd(const void* dy, void* dx, float* scratch, int B, int IH, int IW, int OH, int OW, int Cp,
                                  int dtype, segk_stream_t s) {
   SEGK_REQUIRE(dy && dx && B > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && Cp > 0 && Cp % 32 == 0, "bilinear_bwd: bad arguments");
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "bilinear_bwd: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("bilinear_bwd", dtype);
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
   if (scratch) {   // separable two-pass form: scratch holds B*OH*IW*Cp floats
     hipStream_t st2 = (hipStream_t)s;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "common.hpp"
 
 struct ConvArgs {
   const void* srcA;     // NHWC [B,H,W,CA]  (un-shuffle gather: [B,2H,2W,CA])
@@ -33,8 +34,9 @@ int segk_num_cus();                       // multiprocessor count of the current
 // register-stationary kernel for the narrow high-resolution bf16 layers (conv_rs.hip)
 int segk_conv_use_rs(int cin_p, int n_p, int dtype, int W);
 int segk_conv_rs_rows(int B, int H, int W, int n_p);          // rows of BatchNorm partials it writes
-void segk_conv_rs_grid(int B, int H, int W, int NT, int* gw_out, int* GW_out);
-int segk_conv_rs_launch(const ConvArgs& a, hipStream_t st);
+void segk_conv_rs_grid(int MT, int NT, int* gw_out, int* GW_out);   // MT pixel tiles, NT channel tiles (conv_ws too)
+struct ConvPlan;
+int segk_conv_rs_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
 // the U-Net stem on the NCHW fp32 input (stem.hip)
 int segk_stem_rows(int B, int H, int W, int Cin, int Cout, int dtype);
 int segk_stem_launch(const float* x, const float* w, void* z, void* xn, float* stats, int B, int H, int W, int Cin, int Cout,
@@ -49,11 +51,52 @@ int segk_convt_stream_launch(const void* x, const void* wp, const float* bias4, 
 int segk_convt_stream_dgrad_ok(int B, int H, int W, int Cin, int Cout, int dtype);
 int segk_convt_stream_dgrad_launch(const void* dout, const void* wd, void* din, int B, int H, int W, int Cin, int Cout,
                                    hipStream_t st);
-int segk_conv_use_ws(int cin_p, int n_p, int dtype);   // weight-stationary variant applies
-int segk_conv_use_pipe(int cin_p, int n_p, int dtype); // producer/consumer variant: its channel tile (128 | 64) or 0
 int segk_conv_writes_act(int cin_p, int n_p, int dtype); // the layer's kernel can emit ConvArgs::act_out
-int segk_conv_bm(int geo, int unit);      // pixels per tile for a layer with N = unit output channels
-int segk_conv_twl(int bm, int W);         // log2 tile width
+
+// The conv / 1x1 dispatch, stated once (segk_conv_plan, conv_igemm.hip): launch_geo instantiates the kernel the plan names, and
+// the sizing queries (segk_conv_tiles, segk_conv_writes_act) read the same plan, so a launcher's tile and the rows of the
+// BatchNorm statistics buffer the host allocates cannot drift apart.
+enum ConvForm {
+  CONV_RS,        // register-stationary (conv_rs.hip)
+  CONV_WS,        // weight-stationary
+  CONV_PIPE,      // producer/consumer, channel tile bn (its LDS-DMA producers are chosen per call: launch_pipe)
+  CONV_GEMM_DMA,  // LDS-DMA GEMM of the 1x1 geometry (gemm.hip)
+  CONV_GENERIC,   // conv_igemm_kernel<T, GEO, twl, wm, wn, mf, nf, pbuf>
+};
+struct ConvPlan {
+  ConvForm form;
+  bool wide;                  // image wider than 16 pixels
+  int bm, twl;                // pixel tile: bm pixels, 1 << twl wide
+  int bn;                     // channel tile
+  int wm, wn, mf, nf, pbuf;   // CONV_GENERIC: wave layout, fragments per wave, patch buffers
+  int unit;                   // CONV_GENERIC: the largest of 128, 64, 32 that divides N
+  bool rs_rows;               // rows of BatchNorm partials: conv_rs's 8 * GW * 4 (segk_conv_rs_rows), else one per pixel tile
+};
+// cin_p, n_p: padded CA + CB and N of the call.  gemm_dma: the call is one segk_gemm_dma_ok accepts (it also depends on the
+// row count and the shuffle mode, so the launcher asks it; the queries, which are about the 3x3 geometry, pass false).
+ConvPlan segk_conv_plan(int geo, int dtype, int cin_p, int n_p, int W, bool has_bias, bool gemm_dma);
+
+// Raise a kernel's dynamic-LDS limit to `limit` bytes, once per (kernel instance, device): the attribute is device state, and
+// racing first calls set the same value.
+template <auto Kern>
+int segk_raise_lds(const char* name, int limit) {
+  static bool attr_set[SEGK_MAX_DEVICES] = {};
+  const int dev = segk_device_index();
+  if (!attr_set[dev]) {
+    if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, limit) != hipSuccess)
+      SEGK_FAIL(-3, "%s: cannot raise dynamic LDS limit", name);
+    attr_set[dev] = true;
+  }
+  return 0;
+}
+// ... and launch it with `lds` bytes
+template <auto Kern, typename... Args>
+int segk_launch_lds(const char* name, int limit, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  if (const int rc = segk_raise_lds<Kern>(name, limit)) return rc;
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  SEGK_CHECK_LAUNCH(name);
+  return 0;
+}
 
 // one tensor of segk_pack_multi's device table (64 bytes; the host builds it as 8 int64 words)
 //   kind 0: Conv2d 3x3 weight OIHW -> forward + data-gradient layouts   (blocks: (CAp+CBp)/32 * Coutp/32)

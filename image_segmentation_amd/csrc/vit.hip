@@ -20,6 +20,7 @@
 // The residual stream stays fp32 in both compute modes (it is 2.4 MB per image batch of 16); GEMM operands are
 // the compute dtype.
 #include "common.hpp"
+#include "segk_internal.h"
 #include "../../include/segk.h"
 
 namespace {
@@ -425,12 +426,7 @@ int launch_attention_mfma(const void* qkv, void* ctx, int B, int Tn, int heads, 
   const int Tp = (Tn + 31) & ~31;
   const size_t lds = (size_t)Tp * 144 + (size_t)64 * (Tp * 2 + 16);
   SEGK_REQUIRE(lds <= 160 * 1024, "attention: %d tokens do not fit the 160 KiB LDS (%zu bytes)", Tn, lds);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)attention_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "attention: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
+  if (const int rc = segk_raise_lds<attention_mfma_kernel>("attention", 160 * 1024)) return rc;
   hipLaunchKernelGGL(attention_mfma_kernel, dim3(cdiv(Tn, 128), B * heads), dim3(256), lds, st, (const bf16_t*)qkv, (bf16_t*)ctx,
                      Tn, heads, ldq, ldo, scale);
   SEGK_CHECK_LAUNCH("attention_mfma");
@@ -444,17 +440,8 @@ int launch_attention(const void* qkv, void* ctx, int B, int Tn, int heads, int l
   const size_t comb = (size_t)4 * (HD + 2) * 64 * 4;
   if (lds < comb) lds = comb;
   SEGK_REQUIRE(lds <= 160 * 1024, "attention: %d tokens x %d head dims do not fit the 160 KiB LDS (%zu bytes)", Tn, HD, lds);
-  auto kern = attention_kernel<T, HD>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "attention: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(cdiv(Tn, 64), B * heads), dim3(256), lds, st, (const T*)qkv, (T*)ctx, Tn, heads, ldq, ldo,
-                     scale);
-  SEGK_CHECK_LAUNCH("attention");
-  return 0;
+  return segk_launch_lds<attention_kernel<T, HD>>("attention", 160 * 1024, dim3(cdiv(Tn, 64), B * heads), dim3(256), lds, st,
+                                                  (const T*)qkv, (T*)ctx, Tn, heads, ldq, ldo, scale);
 }
 
 }  // namespace

@@ -590,20 +590,12 @@ int launch_dma(const WgradArgs& a, hipStream_t st) {
   constexpr size_t lds = 2 * ((size_t)WU * 128 * 64 + (size_t)WV * 192 * 64);
   static_assert(lds <= 160 * 1024, "wgrad_dma: LDS exceeds 160 KiB");
   const int NCT = (a.CD / (32 * WC)) * ((a.CA + a.CB) / (32 * WI));
-  auto kern = wgrad_dma_kernel<WC, WI, PRO, RAG>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};     // per device: the attribute is device state
-  const int dev_ = segk_device_index();
-  if (!attr_set[dev_]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "wgrad_dma: cannot raise dynamic LDS limit");
-    attr_set[dev_] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.S * NCT), dim3((WC * WI > 4 ? WC * WI : 4) * 64), lds, st, a);
+  const int rc = segk_launch_lds<wgrad_dma_kernel<WC, WI, PRO, RAG>>("wgrad_dma", 160 * 1024, dim3(a.S * NCT),
+                                                                     dim3((WC * WI > 4 ? WC * WI : 4) * 64), lds, st, a);
 #ifdef SEGK_WGRAD_STAMPS
   { void* sp = nullptr; if (hipGetSymbolAddress(&sp, HIP_SYMBOL(g_wstamps)) == hipSuccess) (void)hipMemcpyAsync(a.slabs, sp, sizeof(unsigned long long) * 256 * 8 * 8, hipMemcpyDeviceToDevice, st); }
 #endif
-  SEGK_CHECK_LAUNCH("wgrad_dma");
-  return 0;
+  return rc;
 }
 
 template <int WC, int WI>
@@ -618,20 +610,12 @@ int launch_cfg(const WgradArgs& a, hipStream_t st) {
   using G = WG<T, GEO, WC>;
   const size_t lds = (size_t)WC * G::NDZ * G::BLKP + (size_t)WI * G::NPP * G::BLKP;
   const int NCT = (a.CD / (32 * WC)) * ((a.CA + a.CB) / (32 * WI));
-  auto kern = wgrad_kernel<T, GEO, WC, WI>;
-  static bool attr_set[SEGK_MAX_DEVICES] = {};     // per device: the attribute is device state
-  const int dev_ = segk_device_index();
-  if (!attr_set[dev_]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      SEGK_FAIL(-3, "wgrad: cannot raise dynamic LDS limit");
-    attr_set[dev_] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.S * NCT), dim3((WC * WI > 4 ? WC * WI : 4) * 64), lds, st, a);
+  const int rc = segk_launch_lds<wgrad_kernel<T, GEO, WC, WI>>("wgrad", 160 * 1024, dim3(a.S * NCT),
+                                                               dim3((WC * WI > 4 ? WC * WI : 4) * 64), lds, st, a);
 #ifdef SEGK_WGRAD_STAMPS
   { void* sp = nullptr; if (hipGetSymbolAddress(&sp, HIP_SYMBOL(g_wstamps)) == hipSuccess) (void)hipMemcpyAsync(a.slabs, sp, sizeof(unsigned long long) * 256 * 8 * 8, hipMemcpyDeviceToDevice, st); }
 #endif
-  SEGK_CHECK_LAUNCH("wgrad");
-  return 0;
+  return rc;
 }
 
 template <typename T, int GEO>
@@ -695,7 +679,7 @@ int segk_wgrad_tiles(int B, int H, int W, int geo, int dtype) {
 }
 
 int segk_wgrad_launch(const WgradArgs& a, int geo, int dtype, hipStream_t st) {
-  SEGK_REQUIRE(dtype == SEGK_DT_F32 || dtype == SEGK_DT_BF16, "wgrad: bad dtype %d", dtype);
+  SEGK_REQUIRE_DTYPE("wgrad", dtype);
   SEGK_REQUIRE(geo >= 0 && geo <= 2, "wgrad: bad geometry %d", geo);
   SEGK_REQUIRE(a.dz && a.srcA && a.slabs, "wgrad: null pointer");
   SEGK_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0, "wgrad: bad shape");

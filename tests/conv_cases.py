@@ -21,7 +21,7 @@ def cdiv(a, b):
     return -(-a // b)
 
 
-# ---- the dispatch: segk_conv_use_rs / _ws / _pipe, segk_conv_bm, segk_conv_twl, launch_geo, launch_pipe ----------------------
+# ---- the dispatch: segk_conv_plan (segk_conv_use_rs, use_ws, use_pipe, generic_tile), launch_geo, launch_pipe ----------------
 def use_rs(cin, n, dtype, W):
     return dtype == "bf16" and cin in (32, 64) and n % 64 == 0 and W > 16
 
@@ -281,16 +281,6 @@ LONG_CASES = [
     Case("bf16", 38, 18, 34, 96, 0, 64, 128, False, False, False, True, 0),       # generic bf16, two 4-wave workgroups per CU
     Case("fp32", 29, 18, 34, 32, 0, 384, 0, False, False, False, True, 0),        # generic fp32, 8 waves
 ]
-
-# Compiled 3x3 instances no valid call can select, each with the reason in the dispatch (tests/test_conv_instances.py proves
-# every entry by sweeping the mirror).  A later clean-up can delete their instantiations.
-UNREACHABLE = {
-    f"conv_igemm_kernel<bf16,0,{twl},4,2,2,2,2,{pro}>":
-        "launch_geo takes this 256 x 128 form for N % 128 == 0, but in bf16 every such layer is served earlier: Cin <= 64 by "
-        "conv_ws / conv_rs (N % 64 == 0), Cin >= 96 by the producer/consumer kernel (segk_conv_use_pipe returns 128)"
-    for twl in (5, 4) for pro in ("true", "false")
-}
-
 
 # ---- inputs of the impulse and the lattice run -----------------------------------------------------------------------------------------------
 def lattice_density(c):

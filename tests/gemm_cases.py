@@ -362,11 +362,3 @@ LONG_CASES = [
 
 PERSISTENT_FAMILIES = ("dma-0-256", "dma-0-320", "dma-1-256", "dma-1-320", "dma-2-256", "dma-2-320", "generic-bf16", "generic-fp32",
                        "stream-0", "stream-1")
-
-# Compiled instances no valid call can select (tests/test_gemm_instances.py proves every entry by sweeping the mirror).
-UNREACHABLE = {
-    f"conv_igemm_kernel<bf16,1,{twl},4,2,2,{nf},2,false>":
-        f"launch_geo<bf16, 1> serves N % {64 * nf} == 0 earlier, by the LDS-DMA GEMM or the 128-pixel form "
-        f"conv_igemm_kernel<bf16,1,4,2,2,2,{nf},2,false>; the 256-pixel form behind them is reached in fp32 only"
-    for twl in (5, 4) for nf in (2, 1)
-}

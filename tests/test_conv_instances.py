@@ -1,5 +1,5 @@
 """CPU: the case table of the 3x3 convolution matrix (tests/conv_cases.py) reaches every 3x3 kernel instance that
-csrc/conv_igemm.hip and csrc/conv_rs.hip compile to, except the ones listed -- and proved -- unreachable, and nothing else.
+csrc/conv_igemm.hip and csrc/conv_rs.hip compile to, without exception, and nothing else.
 The units are compiled device-only exactly as tools/spill_report.py does and the kernel names of the resource-usage remarks
 are parsed: a new instance without a case, or a dispatch change that strands a case, fails here on any machine.  Also the
 table's own conditions: image kinds per instance, the W = 16 / 17 pairs, the spread of the features, the cases with three or
@@ -11,7 +11,7 @@ import sys
 
 import pytest
 
-from conv_cases import (CASES, LONG_CASES, PERSISTENT_FAMILIES, REF_MADD_CAP, UNREACHABLE, Case, case_id, family_of, image_kind,
+from conv_cases import (CASES, LONG_CASES, PERSISTENT_FAMILIES, REF_MADD_CAP, Case, case_id, family_of, image_kind,
                         instance_of, is_valid, logical_of, probe_passes, ref_madds, select, spell, tile_shape, tiles_of,
                         units_per_workgroup, writes_act)
 
@@ -74,16 +74,13 @@ def test_parse_instance():
 
 
 @pytest.mark.timeout(900)
-def test_table_and_unreachable_list_account_for_every_compiled_instance(compiled_instances):
+def test_table_accounts_for_every_compiled_instance(compiled_instances):
     table = {instance_of(c) for c in CASES}
-    unreachable = set(UNREACHABLE)
-    assert not table & unreachable, sorted(table & unreachable)
-    print(f"{len(compiled_instances & (table | unreachable))} of {len(compiled_instances)} compiled 3x3 instances accounted for: "
-          f"{len(table)} reached by the table, {len(unreachable)} listed unreachable")
-    missing, stranded = compiled_instances - table - unreachable, (table | unreachable) - compiled_instances
+    print(f"{len(compiled_instances & table)} of {len(compiled_instances)} compiled 3x3 instances reached by the table")
+    missing, stranded = compiled_instances - table, table - compiled_instances
     assert not missing, f"compiled instances without a case: {sorted(missing)}"
-    assert not stranded, f"cases or UNREACHABLE entries whose instance is not compiled (dispatch changed?): {sorted(stranded)}"
-    assert len(compiled_instances) == 36
+    assert not stranded, f"cases whose instance is not compiled (dispatch changed?): {sorted(stranded)}"
+    assert len(compiled_instances) == 32
     assert {instance_of(c) for c in LONG_CASES} <= table
 
 
@@ -98,17 +95,34 @@ def test_every_case_is_a_valid_call_and_distinct():
     assert len({case_id(c) for c in CASES + LONG_CASES}) == len(CASES) + len(LONG_CASES)
 
 
-def test_unreachable_instances_are_selected_by_no_valid_call():
+def test_sweep_of_the_mirror_selects_exactly_the_tables_instances():
     """The mirror over every padded (Cin, N) in 32..512 step 32 x W x bias x prologue x dtype (odd and even chunk counts, the
-    LDS-DMA condition, among them) selects none of the UNREACHABLE instances -- and does select every other one."""
+    LDS-DMA condition, among them) selects the instances of the table and no other."""
     seen = set()
     for dtype, cin, n, W, bias, pro in itertools.product(("bf16", "fp32"), range(32, 513, 32), range(32, 513, 32), (8, 16, 17, 64),
                                                          (False, True), (False, True)):
         seen.add(spell(*select(dtype, cin, n, W, bias, pro)))
-    assert not seen & set(UNREACHABLE), sorted(seen & set(UNREACHABLE))
     assert seen == {instance_of(c) for c in CASES}
-    for name, reason in UNREACHABLE.items():
-        assert name.startswith("conv_igemm_kernel<bf16,0,") and len(reason) > 40
+
+
+def test_library_queries_agree_with_the_mirror_over_the_whole_sweep():
+    """segk_conv_tiles and segk_conv_writes_act_q of the built library against tiles_of / writes_act, over every dtype x padded
+    (Cin, N) in 32..512 step 32 x W x two (B, H): 4096 points.  The queries are pure host code and need no device (without one
+    the library assumes 256 compute units, the mirror's NUM_CUS): the host sizes every statistics buffer from them."""
+    from image_segmentation_amd import build, _lib
+    stamp = os.path.join(os.path.dirname(_lib.LIB_PATH), ".build_id")
+    built = open(stamp).read().strip() if os.path.exists(stamp) else ""
+    if not os.path.exists(_lib.LIB_PATH) or built != build.source_hash():
+        build.build(verbose=False)
+    n_points = 0
+    for dtype, cin, n, W, (B, H) in itertools.product(("bf16", "fp32"), range(32, 513, 32), range(32, 513, 32), (8, 16, 17, 64),
+                                                       ((2, 40), (64, 9))):
+        sdt = 1 if dtype == "bf16" else 0
+        c = Case(dtype, B, H, W, cin, 0, n, 0, False, False, False, False, 0)
+        assert _lib.query("segk_conv_tiles", B, H, W, cin, n, sdt) == tiles_of(c), c
+        assert bool(_lib.query("segk_conv_writes_act_q", cin, n, sdt)) == bool(writes_act(cin, n, dtype)), c
+        n_points += 1
+    assert n_points == 4096
 
 
 def test_instance_of_follows_the_dispatch_rules():

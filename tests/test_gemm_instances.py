@@ -1,6 +1,6 @@
 """CPU: the case table of the 1x1-geometry matrix (tests/gemm_cases.py) reaches every instance of gemm_dma_kernel
 (csrc/gemm.hip), of convt_stream_kernel (csrc/convt_stream.hip) and every GEO == 1 instance of conv_igemm_kernel
-(csrc/conv_igemm.hip) the units compile to, except the ones listed -- and proved -- unreachable, and nothing else.  The units
+(csrc/conv_igemm.hip) the units compile to, without exception, and nothing else.  The units
 are compiled device-only exactly as tools/spill_report.py does and the kernel names of the resource-usage remarks are parsed
 (names and register counts only): a new instance without a case, or a dispatch change that strands a case, fails here on any
 machine.  Also the table's own conditions: image kinds per instance, the W = 16 / 17 pairs, the pixel-shuffle cases whose tap
@@ -14,7 +14,7 @@ import sys
 
 import pytest
 
-from gemm_cases import (CASES, LONG_CASES, NUM_CUS, PERSISTENT_FAMILIES, UNREACHABLE, blocks_per_stream, case_id, convt_stream_ok,
+from gemm_cases import (CASES, LONG_CASES, NUM_CUS, PERSISTENT_FAMILIES, blocks_per_stream, case_id, convt_stream_ok,
                         dma_bm, family_of, gemm_dma_ok, gemm_view, image_kind, instance_of, is_valid, kernel_of, lin, min_chunks, mk,
                         nchunks_of, rows_of, select, spell, splitk_ok, stream_grid, tile_shape, unit_walk, units_per_workgroup)
 
@@ -72,16 +72,13 @@ def test_parse_instance():
 
 
 @pytest.mark.timeout(900)
-def test_table_and_unreachable_list_account_for_every_compiled_instance(compiled_instances):
+def test_table_accounts_for_every_compiled_instance(compiled_instances):
     table = {kernel_of(c) for c in CASES}
-    unreachable = set(UNREACHABLE)
-    assert not table & unreachable, sorted(table & unreachable)
-    print(f"{len(compiled_instances & (table | unreachable))} of {len(compiled_instances)} compiled 1x1-geometry instances accounted "
-          f"for: {len(table)} reached by the table, {len(unreachable)} listed unreachable")
-    missing, stranded = compiled_instances - table - unreachable, (table | unreachable) - compiled_instances
+    print(f"{len(compiled_instances & table)} of {len(compiled_instances)} compiled 1x1-geometry instances reached by the table")
+    missing, stranded = compiled_instances - table, table - compiled_instances
     assert not missing, f"compiled instances without a case: {sorted(missing)}"
-    assert not stranded, f"cases or UNREACHABLE entries whose instance is not compiled (dispatch changed?): {sorted(stranded)}"
-    assert len(compiled_instances) == 23          # 6 gemm_dma + 3 convt_stream + 14 conv_igemm<*, 1, ...>
+    assert not stranded, f"cases whose instance is not compiled (dispatch changed?): {sorted(stranded)}"
+    assert len(compiled_instances) == 19          # 6 gemm_dma + 3 convt_stream + 10 conv_igemm<*, 1, ...>
     assert {kernel_of(c) for c in LONG_CASES} <= table
 
 
@@ -117,13 +114,8 @@ def _sweep():
     return seen
 
 
-def test_unreachable_instances_are_selected_by_no_valid_call():
-    seen = _sweep()
-    assert not seen & set(UNREACHABLE), sorted(seen & set(UNREACHABLE))
-    assert seen == {kernel_of(c) for c in CASES}
-    for name, reason in UNREACHABLE.items():
-        assert name.startswith("conv_igemm_kernel<bf16,1,") and len(reason) > 40
-    assert len(UNREACHABLE) == 4
+def test_sweep_of_the_mirror_selects_exactly_the_tables_instances():
+    assert _sweep() == {kernel_of(c) for c in CASES}
 
 
 def test_instance_of_follows_the_dispatch_rules():
