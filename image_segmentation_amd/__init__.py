@@ -14,4 +14,5 @@ from .augment import (Augmenter, AugPlan, AugmentedBatches, merge_pairs, class_w
                       cubic_table, contrast_lut, laplace_table, rotation_plan, merge_plan, ALL_OPS, TARGET_REMAP)
 from .robustness import (PERTURBATIONS, DEFAULT_LEVELS, PerturbPlan, gauss_table, value_lut, perturb_plan, perturb,      # noqa: F401
                          robustness_sweep, cell_seed, image_seed)
+from .tta import TTA, view_table, view_order, VIEW_DESC                                                      # noqa: F401
 from .components import components, Components, Clean, mask_finish                                          # noqa: F401

@@ -300,9 +300,10 @@ __device__ __forceinline__ void resize_sample(L ld, int oy, int ox, float sh, fl
 
 template <typename V>
 __global__ __launch_bounds__(256) void resize_pad_kernel(const V* __restrict__ img, V* __restrict__ out, int C, int H, int W,
-                                                         int nh, int nw, int T, int pt, int pl, int mode) {
+                                                         int nh, int nw, int T, int pt, int pl, int mode, int flip) {
   const long total = (long)C * T * T;
   const float sh = (float)H / (float)nh, sw = (float)W / (float)nw;
+  const bool fh = flip & 1, fv = flip & 2;   // the flipped image's pixel (y, x) is the image's (H-1-y, W-1-x)
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int tx = (int)(i % T);
     const int ty = (int)((i / T) % T);
@@ -311,11 +312,12 @@ __global__ __launch_bounds__(256) void resize_pad_kernel(const V* __restrict__ i
     V v = (V)0;
     if (oy >= 0 && oy < nh && ox >= 0 && ox < nw) {
       const V* src = img + (size_t)c * H * W;
+      auto at = [&](int y, int x) { return src[(size_t)(fv ? H - 1 - y : y) * W + (fh ? W - 1 - x : x)]; };
       if (mode == 1) {
-        v = src[(size_t)nearest_index(oy, sh, H) * W + nearest_index(ox, sw, W)];
+        v = at(nearest_index(oy, sh, H), nearest_index(ox, sw, W));
       } else {
         float r[1];
-        resize_sample<1>([&](int y, int x, float (&t)[1]) { t[0] = (float)src[(size_t)y * W + x]; }, oy, ox, sh, sw, H, W, mode, r);
+        resize_sample<1>([&](int y, int x, float (&t)[1]) { t[0] = (float)at(y, x); }, oy, ox, sh, sw, H, W, mode, r);
         v = (V)r[0];
       }
     }
@@ -329,12 +331,13 @@ __global__ __launch_bounds__(256) void resize_pad_kernel(const V* __restrict__ i
 // dword-or-less and are fetched together.  Reads H*W*CIN bytes at most, writes 4*CO*T*T.
 template <int CIN, int MODE>
 __global__ __launch_bounds__(256) void resize_pad_u8_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H, int W,
-                                                            int nh, int nw, int T, int pt, int pl) {
+                                                            int nh, int nw, int T, int pt, int pl, int flip) {
   constexpr int CO = CIN < 3 ? CIN : 3;
   const int total = T * T;
   const float sh = (float)H / (float)nh, sw = (float)W / (float)nw;
+  const bool fh = flip & 1, fv = flip & 2;   // the flipped image's pixel (y, x) is the image's (H-1-y, W-1-x)
   auto ld = [&](int y, int x, float (&t)[CO]) {
-    const uint8_t* q = img + ((size_t)y * W + x) * CIN;
+    const uint8_t* q = img + ((size_t)(fv ? H - 1 - y : y) * W + (fh ? W - 1 - x : x)) * CIN;
     if constexpr (CIN == 4) {   // one aligned dword; the alpha byte is dropped (process_batch_forward does the same)
       const uint32_t w = *(const uint32_t*)q;
       t[0] = (float)(w & 255u) / 255.0f;
@@ -514,8 +517,8 @@ __global__ __launch_bounds__(256) void predict_mask_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int segk_resize_pad(const void* img, void* out, int C, int H, int W, int nh, int nw, int T, int pad_top,
-                               int pad_left, int mode, int elem, segk_stream_t s) {
+static int resize_pad_launch(const void* img, void* out, int C, int H, int W, int nh, int nw, int T, int pad_top, int pad_left,
+                             int mode, int elem, int flip, segk_stream_t s) {
   SEGK_REQUIRE(img && out && C > 0 && H > 0 && W > 0 && nh > 0 && nw > 0 && T > 0, "resize_pad: bad shape");
   SEGK_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + nh <= T && pad_left + nw <= T, "resize_pad: window outside the target");
   SEGK_REQUIRE(mode >= 0 && mode <= 2 && (elem == 0 || elem == 1), "resize_pad: bad mode/element type");
@@ -525,12 +528,23 @@ extern "C" int segk_resize_pad(const void* img, void* out, int C, int H, int W, 
   hipStream_t st = (hipStream_t)s;
   if (elem == 1)
     hipLaunchKernelGGL(resize_pad_kernel<long long>, dim3((int)g), dim3(256), 0, st, (const long long*)img, (long long*)out, C, H, W,
-                       nh, nw, T, pad_top, pad_left, mode);
+                       nh, nw, T, pad_top, pad_left, mode, flip);
   else
     hipLaunchKernelGGL(resize_pad_kernel<float>, dim3((int)g), dim3(256), 0, st, (const float*)img, (float*)out, C, H, W, nh, nw, T,
-                       pad_top, pad_left, mode);
+                       pad_top, pad_left, mode, flip);
   SEGK_CHECK_LAUNCH("resize_pad");
   return 0;
+}
+
+extern "C" int segk_resize_pad(const void* img, void* out, int C, int H, int W, int nh, int nw, int T, int pad_top,
+                               int pad_left, int mode, int elem, segk_stream_t s) {
+  return resize_pad_launch(img, out, C, H, W, nh, nw, T, pad_top, pad_left, mode, elem, 0, s);
+}
+
+extern "C" int segk_resize_pad_flip(const void* img, void* out, int C, int H, int W, int nh, int nw, int T, int pad_top,
+                                    int pad_left, int mode, int elem, int flip, segk_stream_t s) {
+  SEGK_REQUIRE(flip >= 0 && flip <= 3, "resize_pad_flip: flip is 0..3 (bit 0: x, bit 1: y), got %d", flip);
+  return resize_pad_launch(img, out, C, H, W, nh, nw, T, pad_top, pad_left, mode, elem, flip, s);
 }
 
 extern "C" int segk_crop_resize(const float* slot, float* out, int C, int T, int pad_top, int pad_left, int nh, int nw, int oh,
@@ -546,8 +560,8 @@ extern "C" int segk_crop_resize(const float* slot, float* out, int C, int T, int
   return 0;
 }
 
-extern "C" int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T, int pad_top,
-                                  int pad_left, int mode, segk_stream_t s) {
+static int resize_pad_u8_launch(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T, int pad_top,
+                                int pad_left, int mode, int flip, segk_stream_t s) {
   SEGK_REQUIRE(img_hwc && out && H > 0 && W > 0 && nh > 0 && nw > 0 && T > 0 && T <= 16384, "resize_pad_u8: bad shape");
   SEGK_REQUIRE(Cin == 1 || Cin == 3 || Cin == 4, "resize_pad_u8: 1, 3 or 4 interleaved channels, got %d", Cin);
   SEGK_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + nh <= T && pad_left + nw <= T, "resize_pad_u8: window outside the target");
@@ -558,7 +572,7 @@ extern "C" int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, i
   hipStream_t st = (hipStream_t)s;
   auto launch = [&](auto cin, auto md) {
     hipLaunchKernelGGL((resize_pad_u8_kernel<decltype(cin)::value, decltype(md)::value>), dim3((int)g), dim3(256), 0, st, img_hwc, out,
-                       H, W, nh, nw, T, pad_top, pad_left);
+                       H, W, nh, nw, T, pad_top, pad_left, flip);
   };
   auto by_mode = [&](auto cin) {
     if (mode == 0) launch(cin, std::integral_constant<int, 0>{});
@@ -570,6 +584,17 @@ extern "C" int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, i
   else by_mode(std::integral_constant<int, 4>{});
   SEGK_CHECK_LAUNCH("resize_pad_u8");
   return 0;
+}
+
+extern "C" int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T, int pad_top,
+                                  int pad_left, int mode, segk_stream_t s) {
+  return resize_pad_u8_launch(img_hwc, out, Cin, H, W, nh, nw, T, pad_top, pad_left, mode, 0, s);
+}
+
+extern "C" int segk_resize_pad_u8_flip(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T,
+                                       int pad_top, int pad_left, int mode, int flip, segk_stream_t s) {
+  SEGK_REQUIRE(flip >= 0 && flip <= 3, "resize_pad_u8_flip: flip is 0..3 (bit 0: x, bit 1: y), got %d", flip);
+  return resize_pad_u8_launch(img_hwc, out, Cin, H, W, nh, nw, T, pad_top, pad_left, mode, flip, s);
 }
 
 extern "C" int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts,
@@ -611,5 +636,234 @@ extern "C" int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* colo
   else if (C == 4) by_mode(std::integral_constant<int, 4>{});
   else by_mode(std::integral_constant<int, SEGK_MAX_CLASSES>{});
   SEGK_CHECK_LAUNCH("predict_mask");
+  return 0;
+}
+
+// ---- multi-view prediction: V views of one image -> one mask ---------------------------------------------
+// predict_mask_kernel with an accumulator: a thread owns four consecutive flat pixels and walks the views in table order
+// over acc[4][NC]; per view it samples the view's window at the FLIPPED pixel with the arithmetic of crop_resize_kernel
+// (clamped indices, unconditional loads: the 4*NC taps of a pixel are in flight together), turns logits into probabilities
+// where the merge asks for it, and adds weight * s.  A view's descriptor is indexed by the loop counter alone, so it is
+// read with uniform loads into scalar registers, and its per-class window origins are scalar too.  The slots (V*C*T*T*4
+// bytes) stay in L2; 1 + 3 + 1 bytes leave per pixel.  Classes past C repeat class C-1, as in predict_mask_kernel: they
+// never win the strict comparison, and the sums over classes skip them.
+namespace {
+
+template <int NC>
+__device__ __forceinline__ void softmax_classes(float (&z)[NC], int C) {
+  // m = max z, e_k = expf(z_k - m), p_k = e_k / sum_k e_k, the sum in class order
+  float m = z[0];
+#pragma unroll
+  for (int k = 1; k < NC; ++k) m = z[k] > m ? z[k] : m;
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    z[k] = expf(z[k] - m);
+    sum = sum + ((NC <= 4 || k < C) ? z[k] : 0.f);
+  }
+#pragma unroll
+  for (int k = 0; k < NC; ++k) z[k] = z[k] / sum;
+}
+
+template <int NC, int MODE, bool LAB>
+__global__ __launch_bounds__(256) void predict_merge_kernel(const segk_view_desc* __restrict__ views, int V, int C, int merge,
+                                                            int oh, int ow, uint8_t* __restrict__ mask, uint8_t* __restrict__ color,
+                                                            const uint8_t* __restrict__ palette,
+                                                            unsigned long long* __restrict__ counts,
+                                                            const long long* __restrict__ labels, unsigned long long* __restrict__ M,
+                                                            uint8_t* __restrict__ conf, float* __restrict__ scores) {
+  constexpr int NB = SEGK_MAX_CLASSES * SEGK_MAX_CLASSES;
+  __shared__ unsigned int hist[NB + SEGK_MAX_CLASSES];            // confusion bins, then class counts
+  if (threadIdx.x < NB + SEGK_MAX_CLASSES) hist[threadIdx.x] = 0;
+  unsigned int pal[NC], cnt[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) { pal[k] = 0; cnt[k] = 0; }
+  if (color) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const uint8_t* q = palette + 3 * (k < C ? k : C - 1);
+      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
+    }
+  }
+  __syncthreads();
+  const int total = oh * ow;
+  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
+    const int p = (int)(q * 4);
+    long long lab[4];
+    if (LAB) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
+    }
+    // the thread's four pixels (one past the end repeats the last); a thread may straddle a row end
+    int oy[4], ox[4];
+    oy[0] = p / ow; ox[0] = p - oy[0] * ow;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      oy[j] = oy[j - 1]; ox[j] = ox[j - 1];
+      if (p + j < total && ++ox[j] == ow) { ox[j] = 0; ++oy[j]; }
+    }
+    float acc[4][NC];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc[j][k] = 0.f;
+    for (int v = 0; v < V; ++v) {                                  // fixed order: the order is part of the result
+      const segk_view_desc d = views[v];                           // uniform: scalar loads
+      const float sh = (float)d.nh / (float)oh, sw = (float)d.nw / (float)ow;
+      const char* wk[NC];
+#pragma unroll
+      for (int k = 0; k < NC; ++k)
+        wk[k] = (const char*)((const float*)d.slot + ((size_t)(k < C ? k : C - 1) * d.T + d.pad_top) * d.T + d.pad_left);
+      const unsigned pitch = 4u * (unsigned)d.T;
+      const bool soft = merge == SEGK_MERGE_PROB && d.kind == 0;
+      const float wt = d.weight;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int sy = (d.flip & 2) ? oh - 1 - oy[j] : oy[j], sx = (d.flip & 1) ? ow - 1 - ox[j] : ox[j];
+        float z[NC];
+        if (MODE == 1) {
+          const unsigned o = (unsigned)nearest_index(sy, sh, d.nh) * pitch + 4u * (unsigned)nearest_index(sx, sw, d.nw);
+#pragma unroll
+          for (int k = 0; k < NC; ++k) z[k] = tap(wk[k], o);
+        } else {
+          int y0, y1, x0, x1;
+          float ly, lx;
+          src_index(sy, sh, d.nh, y0, y1, ly);
+          src_index(sx, sw, d.nw, x0, x1, lx);
+          const unsigned r0 = (unsigned)y0 * pitch, r1 = (unsigned)y1 * pitch, c0 = 4u * (unsigned)x0, c1 = 4u * (unsigned)x1;
+          float a[NC], b[NC], e[NC], f[NC];
+#pragma unroll
+          for (int k = 0; k < NC; ++k) {
+            a[k] = tap(wk[k], r0 + c0); b[k] = tap(wk[k], r0 + c1); e[k] = tap(wk[k], r1 + c0); f[k] = tap(wk[k], r1 + c1);
+          }
+#pragma unroll
+          for (int k = 0; k < NC; ++k) z[k] = bilerp(a[k], b[k], e[k], f[k], ly, lx);
+        }
+        if (soft) softmax_classes<NC>(z, C);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) acc[j][k] = acc[j][k] + wt * z[k];
+      }
+    }
+    const bool full = p + 3 < total;
+    int best[4];
+    unsigned int c4[4], cf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int bi = 0;
+      float bv = acc[j][0];
+#pragma unroll
+      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
+        const bool take = (acc[j][k] > bv) | ((acc[j][k] != acc[j][k]) & (bv == bv));
+        bv = take ? acc[j][k] : bv;
+        bi = take ? k : bi;
+      }
+      best[j] = bi;
+      const unsigned live = p + j < total ? 1u : 0u;
+      c4[j] = 0; cf[j] = 0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        cnt[k] += bi == k ? live : 0u;
+        c4[j] = bi == k ? pal[k] : c4[j];
+      }
+      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[bi * SEGK_MAX_CLASSES + (int)lab[j]], 1u);
+      if (conf || scores) {                               // p = acc / sum acc (prob) or softmax(acc) (logit)
+        float pr[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) pr[k] = acc[j][k];
+        if (merge == SEGK_MERGE_PROB) {
+          float sum = 0.f;
+#pragma unroll
+          for (int k = 0; k < NC; ++k) sum = sum + ((NC <= 4 || k < C) ? pr[k] : 0.f);
+#pragma unroll
+          for (int k = 0; k < NC; ++k) pr[k] = pr[k] / sum;
+        } else {
+          softmax_classes<NC>(pr, C);
+        }
+        float pb = pr[0];
+#pragma unroll
+        for (int k = 1; k < NC; ++k) pb = bi == k ? pr[k] : pb;
+        const float c = 255.f * pb + 0.5f;
+        cf[j] = c >= 0.f ? (unsigned)(c > 255.f ? 255.f : c) : 0u;     // a NaN confidence is stored as 0
+        if (scores && live) {
+#pragma unroll
+          for (int k = 0; k < NC; ++k)
+            if (NC <= 4 || k < C) scores[(size_t)k * total + (unsigned)(p + j)] = pr[k];
+        }
+      }
+    }
+    if (full) {
+      *(uint32_t*)(mask + (unsigned)p) = (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
+      if (conf) *(uint32_t*)(conf + (unsigned)p) = cf[0] | (cf[1] << 8) | (cf[2] << 16) | (cf[3] << 24);
+      if (color)
+        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (p + j < total) {
+          mask[p + j] = (uint8_t)best[j];
+          if (conf) conf[p + j] = (uint8_t)cf[j];
+          if (color)
+            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
+        }
+    }
+  }
+  if (counts) {   // wave sums first: 64 lanes adding to one LDS word serialise
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      unsigned int c = cnt[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
+    }
+  }
+  __syncthreads();
+  // integer sums: one 64-bit atomic per non-zero bin per block, order-independent and bit-stable
+  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+  if (counts && threadIdx.x >= NB && threadIdx.x < NB + SEGK_MAX_CLASSES && hist[threadIdx.x])
+    atomicAdd(&counts[threadIdx.x - NB], (unsigned long long)hist[threadIdx.x]);
+}
+
+}  // namespace
+
+static_assert(sizeof(segk_view_desc) == 48, "segk_view_desc is 48 bytes (image_segmentation_amd/tta.py: VIEW_DESC)");
+
+extern "C" int segk_predict_merge(const void* views_dev, int V, int C, int merge, int mode, int oh, int ow, uint8_t* mask,
+                                  uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels, uint64_t* M,
+                                  uint8_t* conf, float* scores, segk_stream_t s) {
+  SEGK_REQUIRE(views_dev && mask && oh > 0 && ow > 0, "predict_merge: bad shape");
+  SEGK_REQUIRE(V >= 1 && V <= SEGK_MAX_VIEWS, "predict_merge: 1..%d views supported, got %d", SEGK_MAX_VIEWS, V);
+  SEGK_REQUIRE(C >= 1 && C <= SEGK_MAX_CLASSES, "predict_merge: 1..%d classes supported, got %d", SEGK_MAX_CLASSES, C);
+  SEGK_REQUIRE(merge == SEGK_MERGE_PROB || merge == SEGK_MERGE_LOGIT, "predict_merge: bad merge %d", merge);
+  SEGK_REQUIRE(mode == 0 || mode == 1, "predict_merge: bad mode %d", mode);
+  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "predict_merge: color and palette come together");
+  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "predict_merge: labels and M come together");
+  SEGK_REQUIRE((long)oh * ow < (1L << 31) - 4, "predict_merge: output too large for 32-bit offsets");
+  SEGK_REQUIRE(((uintptr_t)views_dev & 15) == 0, "predict_merge: the view table must be 16-byte aligned");
+  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)conf & 3) == 0 && ((uintptr_t)scores & 3) == 0,
+               "predict_merge: mask, color, conf and scores must be 4-byte aligned");
+  long g = (((long)oh * ow + 3) / 4 + 255) / 256;
+  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;      // as segk_predict_mask: few blocks end in atomics
+  if (g > cap) g = cap;
+  hipStream_t st = (hipStream_t)s;
+  auto launch = [&](auto nc, auto md, auto lab) {
+    hipLaunchKernelGGL((predict_merge_kernel<decltype(nc)::value, decltype(md)::value, decltype(lab)::value>), dim3((int)g), dim3(256), 0,
+                       st, (const segk_view_desc*)views_dev, V, C, merge, oh, ow, mask, color, palette, (unsigned long long*)counts,
+                       (const long long*)labels, (unsigned long long*)M, conf, scores);
+  };
+  auto by_lab = [&](auto nc, auto md) {
+    if (labels) launch(nc, md, std::true_type{});
+    else launch(nc, md, std::false_type{});
+  };
+  auto by_mode = [&](auto nc) {
+    if (mode == 0) by_lab(nc, std::integral_constant<int, 0>{});
+    else by_lab(nc, std::integral_constant<int, 1>{});
+  };
+  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
+  if (C == 1) by_mode(std::integral_constant<int, 1>{});
+  else if (C == 2) by_mode(std::integral_constant<int, 2>{});
+  else if (C == 3) by_mode(std::integral_constant<int, 3>{});
+  else if (C == 4) by_mode(std::integral_constant<int, 4>{});
+  else by_mode(std::integral_constant<int, SEGK_MAX_CLASSES>{});
+  SEGK_CHECK_LAUNCH("predict_merge");
   return 0;
 }

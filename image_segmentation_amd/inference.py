@@ -10,7 +10,11 @@ Both ends of the forward are HIP kernels of their own (csrc/resize.hip): segk_re
 interleaved image straight into the network batch, and segk_predict_mask goes from the network output to the uint8 class
 mask, the RGB image, the class counts and (with labels) the confusion counts in one pass, without storing the full-size
 logits that process_batch_reverse + argmax + a palette index would.  Nothing here synchronises with the host when the
-inputs are already on the device; there is no CPU path."""
+inputs are already on the device; there is no CPU path.
+
+Several views of an image -- flips and target sizes (tta=TTA(...)) and several models (a list: an ensemble) -- are merged
+by segk_predict_merge in one pass per image from the views' network outputs: the mask, colour, counts,
+confusion counts and a confidence map, again without full-size float images."""
 import inspect
 from dataclasses import dataclass
 from typing import Optional
@@ -18,7 +22,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib, ops, prompts
+from . import _lib, ops, prompts, tta as _tta
+from .augment import _upload
+from .clipunet import ClipUNet
 from .components import Components, as_clean, components as _components
 from . import utils as U
 
@@ -53,6 +59,9 @@ class Prediction:
     meta: dict                              # the resize / padding record of process_batch_forward
     raw_mask: Optional[torch.Tensor] = None         # with clean=: the argmax before cleaning (mask is the cleaned one)
     components: Optional[Components] = None    # with clean=: the components of raw_mask (components.py)
+    # set on merged views, None otherwise; attributes, not dataclass fields: the constructor stays as it was
+    confidence = None                          # uint8 [H,W], (uint8)(255 p_best + 0.5)
+    scores = None                              # Segmenter(return_scores=True): float32 [C,H,W], the merged probabilities
 
 
 def _num_classes(model):
@@ -91,9 +100,10 @@ def _as_tensor(a):
     return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
 
 
-def _into_slot(image, slot, T, interpolation, antialias, what):
+def _into_slot(image, slot, T, interpolation, antialias, what, flip=0):
     """One image or heat-map -> its slot [c,T,T]: uint8 [H,W,Cin] / [H,W] through segk_resize_pad_u8, float [C,H,W]
-    through segk_resize_pad.  Returns the metadata."""
+    through segk_resize_pad; with flip (bit 0: x, bit 1: y) the slot of the flipped image, through their _flip forms.
+    Returns the metadata."""
     if image.dtype == torch.uint8:
         if image.ndim == 2:
             image = image.unsqueeze(-1)
@@ -108,7 +118,11 @@ def _into_slot(image, slot, T, interpolation, antialias, what):
         src = image.contiguous()
         if cin == 4 and src.data_ptr() % 4:
             src = src.clone()
-        _lib.call("segk_resize_pad_u8", src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, mode, ops._stream())
+        if flip:
+            _lib.call("segk_resize_pad_u8_flip", src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, mode, flip,
+                      ops._stream())
+        else:
+            _lib.call("segk_resize_pad_u8", src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, mode, ops._stream())
         return meta
     if not torch.is_floating_point(image) or image.ndim != 3:
         raise ValueError(f"{what}: expected a float [C,H,W] tensor or a uint8 [H,W,C] image, got {image.dtype} {tuple(image.shape)}")
@@ -116,13 +130,39 @@ def _into_slot(image, slot, T, interpolation, antialias, what):
         image = image[:3]
     if image.shape[0] != slot.shape[0]:
         raise ValueError(f"{what}: {image.shape[0]} channels where the batch has {slot.shape[0]}")
-    return U._resize_pad_into(image, slot, T, interpolation, antialias)
+    if not flip:
+        return U._resize_pad_into(image, slot, T, interpolation, antialias)
+    C, H, W = image.shape
+    nh, nw, pt, pl, meta = U._geometry(H, W, T)
+    antialias = U.ANTIALIAS if antialias is None else antialias
+    mode = 1 if interpolation == U.NEAREST else (0 if antialias else 2)
+    src = image.float().contiguous()
+    _lib.call("segk_resize_pad_flip", src.data_ptr(), slot.data_ptr(), C, H, W, nh, nw, T, pt, pl, mode, 0,
+              flip, ops._stream())
+    return meta
 
 
 def _channels(image):
     if image.dtype == torch.uint8:
         return 1 if image.ndim == 2 else min(int(image.shape[-1]), 3)
     return min(int(image.shape[0]), 3)
+
+
+def _arity(model):
+    """True for a model whose forward takes (image, heatmap)"""
+    return len([p for p in inspect.signature(model.forward).parameters.values()
+                if p.default is p.empty and p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]) >= 2
+
+
+def _is_prompt_model(model):
+    return hasattr(model, "clip") and hasattr(model, "mask")
+
+
+def _fixed_input_size(model):
+    """The one input size a ClipUNet (alone or inside a PromptModel) accepts, None for the convolutional models."""
+    clip = model.clip if _is_prompt_model(model) else model
+    config = getattr(getattr(clip, "encoder", None), "config", None) if isinstance(clip, ClipUNet) else None
+    return None if config is None else int(config.image_size)
 
 
 class Segmenter:
@@ -139,10 +179,24 @@ class Segmenter:
 
     clean=    None (every output as without it), or a components.Clean / a dict of its keywords (connectivity, classes,
               min_area, keep_largest, max_components): the mask is cleaned on the device; Prediction.mask,
-              color, counts and confusion describe the cleaned mask, raw_mask is the argmax and components its components"""
+              color, counts and confusion describe the cleaned mask, raw_mask is the argmax and components its components
+
+    Merged views (without them every output and the code path are as above):
+    model     a list of models is an ensemble: same class count, same input arity, all on one device
+    tta=      a tta.TTA (or a dict of its keywords): the flips and target sizes each model sees and the merge ("prob" /
+              "logit"); view order is models-major, then sizes, then flips
+    model_weights=  one positive weight per model (equal by default); a view weighs model weight x TTA weight
+    outputs=  what a model returns, "logits" or "probs", one string or one per model; default "probs" for a PromptModel,
+              else "logits" ("logit" merging refuses probabilities)
+    return_scores=  Prediction.scores = the merged, normalised class scores, float32 [C,H,W]
+    Prediction.confidence (uint8 [H,W]) is set whenever views are merged; heat-maps and points are flipped with their image."""
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
-                 sigma=3.0, clean=None):
+                 sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False):
+        models = list(model) if isinstance(model, (list, tuple)) else [model]
+        if not models:
+            raise ValueError("an ensemble needs at least one model")
+        model = models[0]
         self.clean = as_clean(clean)
         if not float(sigma) > 0:
             raise ValueError(f"sigma must be positive, got {sigma}")
@@ -155,11 +209,42 @@ class Segmenter:
         self.batch_size, self.antialias = int(batch_size), antialias
         self._palette = _palette_tensor(palette)
         self._palette_dev = {}
-        self._two_input = len([p for p in inspect.signature(model.forward).parameters.values()
-                               if p.default is p.empty and p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]) >= 2
+        self._two_input = _arity(model)
         self.num_classes = _num_classes(model)
         if self.num_classes is not None:
             _check_classes(self.num_classes, self._palette)
+        self.models, self.return_scores = models, bool(return_scores)
+        self._merged = tta is not None or len(models) > 1 or self.return_scores
+        if not self._merged:
+            if model_weights is not None or outputs is not None:
+                raise ValueError("model_weights= and outputs= belong to merged views: pass tta= or several models")
+            return
+        if isinstance(tta, dict):
+            tta = _tta.TTA(**tta)
+        self.tta = _tta.TTA(flips=("",)) if tta is None else tta
+        if not isinstance(self.tta, _tta.TTA):
+            raise ValueError(f"tta: a TTA or a dict of its keywords, got {type(tta).__name__}")
+        for k, m in enumerate(models[1:], 1):
+            if _arity(m) != self._two_input:
+                raise ValueError(f"model {k} takes {'(image, heatmap)' if _arity(m) else 'the image alone'}, model 0 does not")
+            if None not in (_num_classes(m), self.num_classes) and _num_classes(m) != self.num_classes:
+                raise ValueError(f"model {k} has {_num_classes(m)} classes, model 0 has {self.num_classes}")
+        if outputs is None:
+            outputs = ["probs" if _is_prompt_model(m) else "logits" for m in models]
+        elif isinstance(outputs, str):
+            outputs = [outputs] * len(models)
+        outputs = list(outputs)
+        if len(outputs) != len(models) or any(o not in _tta.KINDS for o in outputs):
+            raise ValueError(f"outputs: one of {tuple(_tta.KINDS)} per model, got {outputs!r}")
+        if self.tta.merge == "logit" and "probs" in outputs:
+            raise ValueError('merge="logit" needs models that return logits; a model here returns probabilities')
+        self.outputs = outputs
+        self._views = _tta.view_order(len(models), self.tta, self.target_size, model_weights)
+        for k, m in enumerate(models):
+            fixed = _fixed_input_size(m)
+            if fixed is not None and any(T != fixed for _, T, _, _ in self._views):
+                raise ValueError(f"model {k} is a ClipUNet whose ViT takes {fixed} x {fixed} inputs only: "
+                                 f"target_size / TTA sizes must be {fixed}")
 
     def _palette_on(self, dev):
         if self._palette is None:
@@ -188,15 +273,19 @@ class Segmenter:
             raise ValueError(f"{len(heatmaps)} heatmaps for {n} images")
         if labels is not None and len(labels) != n:
             raise ValueError(f"{len(labels)} label maps for {n} images")
-        param = next(self.model.parameters(), None)
-        if param is None:
+        params = [next(m.parameters(), None) for m in self.models]
+        if any(p is None for p in params):
             raise ValueError("the model has no parameters")
-        ops._require_cuda(param, "Segmenter")
-        dev = param.device
-        modes = [(m, m.training) for m in self.model.modules()]
+        for param in params:
+            ops._require_cuda(param, "Segmenter")
+        dev = params[0].device
+        if any(p.device != dev for p in params):
+            raise ValueError("the models of an ensemble live on one device")
+        modes = [(m, m.training) for model in self.models for m in model.modules()]
         out = []
         try:
-            self.model.eval()
+            for model in self.models:
+                model.eval()
             with torch.no_grad(), torch.cuda.device(dev):
                 for i in range(0, n, self.batch_size):
                     j = min(i + self.batch_size, n)
@@ -204,7 +293,8 @@ class Segmenter:
                     if points is not None:      # click(s) -> heat-map on the device, at the image's own size
                         hm = [prompts._heatmap_on(torch.from_numpy(p).to(dev, non_blocking=True), *sizes[i + k], self.sigma, dev)
                               for k, p in enumerate(points[i:j])]
-                    out += self._chunk(dev, images[i:j], hm, None if labels is None else labels[i:j])
+                    chunk = self._chunk_merged if self._merged else self._chunk
+                    out += chunk(dev, images[i:j], hm, None if labels is None else labels[i:j])
         finally:
             for m, was in modes:
                 m.training = was
@@ -264,6 +354,95 @@ class Segmenter:
             _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
                       ops._p(None if M is None else M[k]), C, oh, ow, s)
             preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
+        return preds
+
+    def _chunk_merged(self, dev, images, heatmaps, labels):
+        """The merged-views form of _chunk: one forward per view over the whole chunk, one table upload for all its images,
+        one segk_predict_merge per image."""
+        n = len(images)
+        images = [im.to(dev, non_blocking=True) for im in images]
+        if heatmaps is not None:
+            heatmaps = [_as_tensor(hm).to(dev, non_blocking=True) for hm in heatmaps]
+        # the network batches, one per (size, flip), shared by the models
+        batches, metas = {}, {}
+        for _, T, f, _ in self._views:
+            if (T, f) in batches:
+                continue
+            flip = _tta.FLIPS[f]
+            X = torch.empty((n, _channels(images[0]), T, T), dtype=torch.float32, device=dev)
+            ms = [_into_slot(im, X[k], T, self.interpolation, self.antialias, "image", flip) for k, im in enumerate(images)]
+            Hm = None
+            if heatmaps is not None:
+                Hm = torch.empty((n, 1, T, T), dtype=torch.float32, device=dev)
+                for k, hm in enumerate(heatmaps):
+                    hmeta = _into_slot(hm, Hm[k], T, self.interpolation, self.antialias, "heatmap", flip)
+                    if hmeta["original_size"] != ms[k]["original_size"]:
+                        raise ValueError(f"heatmap {k} is {hmeta['original_size']}, its image {ms[k]['original_size']}")
+            batches[(T, f)], metas[T] = (X, Hm), ms
+        # one forward per view, in view order
+        ys, C = [], None
+        for m, T, f, _ in self._views:
+            X, Hm = batches[(T, f)]
+            y = self.models[m](X) if Hm is None else self.models[m](X, Hm)
+            ops._require_cuda(y, "Segmenter (model output)")
+            y = y.detach()
+            if y.ndim != 4 or y.shape[0] != n or y.shape[2] != T or y.shape[3] != T:
+                raise ValueError(f"model {m} returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
+            if y.dtype != torch.float32 or not y.is_contiguous():
+                y = y.float().contiguous()
+            if C is not None and int(y.shape[1]) != C:
+                raise ValueError(f"model {m} returned {int(y.shape[1])} classes, the views before it {C}")
+            C = int(y.shape[1])
+            ys.append(y)
+        pal = self._palette_on(dev)
+        _check_classes(C, pal)
+        V = len(self._views)
+        table = np.zeros((n, V), dtype=_tta.VIEW_DESC)
+        for k in range(n):
+            rows = []
+            for (m, T, f, w), y in zip(self._views, ys):
+                pl, pt, _, _ = metas[T][k]["pad"]
+                nh, nw = metas[T][k]["new_size"]
+                rows.append((y[k].data_ptr(), T, pt, pl, nh, nw, f, self.outputs[m], w))
+            table[k] = _tta.view_table(rows)
+        table_dev, (p_table,) = _upload([table], dev)
+        counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
+        M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
+        merge = _tta.MERGES[self.tta.merge]
+        mode = 1 if self.interpolation == U.NEAREST else 0
+        s = ops._stream()
+        preds = []
+        for k, meta in enumerate(metas[self._views[0][1]]):
+            oh, ow = meta["original_size"]
+            mask = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+            conf = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+            scores = torch.empty((C, oh, ow), dtype=torch.float32, device=dev) if self.return_scores else None
+            color = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev) if pal is not None else None
+            lab = None
+            if labels is not None:
+                lab = _as_tensor(labels[k])
+                if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
+                    raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
+                lab = lab.to(dev, non_blocking=True).long().contiguous()
+            views = p_table + k * V * _tta.VIEW_DESC.itemsize
+            Mk = None if M is None else M[k]
+            if self.clean is None:
+                _lib.call("segk_predict_merge", views, V, C, merge, mode, oh, ow, mask.data_ptr(), ops._p(color), ops._p(pal),
+                          counts[k].data_ptr(), ops._p(lab), ops._p(Mk), conf.data_ptr(), ops._p(scores), s)
+                preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
+                preds[-1].confidence, preds[-1].scores = conf, scores
+                continue
+            # the merged argmax alone, its components and the cleaned mask, then the other outputs from the cleaned mask
+            _lib.call("segk_predict_merge", views, V, C, merge, mode, oh, ow, mask.data_ptr(), None, None, None, None, None,
+                      conf.data_ptr(), ops._p(scores), s)
+            cl = self.clean
+            comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
+            _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
+                      ops._p(Mk), C, oh, ow, s)
+            preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
+            preds[-1].confidence, preds[-1].scores = conf, scores
+        # the slots and the table (table_dev) are read by launches still in flight: the caching allocator keeps them valid
+        # in stream order, as it does for the batch of the single-view path
         return preds
 
 

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 316
-#define SEGK_ENTRY_COUNT 88
+#define SEGK_ABI_VERSION 317
+#define SEGK_ENTRY_COUNT 91
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -268,6 +268,40 @@ int segk_resize_pad_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W
 int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts,
                       const int64_t* labels, uint64_t* M, int C, int T, int pad_top, int pad_left, int nh, int nw, int oh,
                       int ow, int mode, segk_stream_t s);
+
+/* segk_resize_pad / segk_resize_pad_u8 of the FLIPPED image (test-time augmentation): bit 0 of flip reverses
+ * x, bit 1 reverses y, in the image's own pixels; only the source fetch changes (it reads (H-1-y, W-1-x)), so the slot
+ * equals bit for bit what the entries above make of the flipped image, and flip 0 equals them.  0 <= flip <= 3. */
+int segk_resize_pad_flip(const void* img, void* out, int C, int H, int W, int nh, int nw, int T, int pad_top, int pad_left,
+                         int mode, int elem, int flip, segk_stream_t s);
+int segk_resize_pad_u8_flip(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int nh, int nw, int T, int pad_top,
+                            int pad_left, int mode, int flip, segk_stream_t s);
+
+/* ---- multi-view prediction: test-time augmentation and ensembling (the reference holds no code for it) ----
+ * One view of an (oh, ow) image: the network output for one model, one target size and one flip of the image. */
+#define SEGK_MAX_VIEWS 16
+#define SEGK_MERGE_PROB 0            /* acc += weight * (kind 0: softmax(z); kind 1: z) */
+#define SEGK_MERGE_LOGIT 1           /* acc += weight * z (kind is not read) */
+typedef struct segk_view_desc {      /* one view; 48 bytes, 16-byte aligned */
+  uint64_t slot;                     /* device address of the view's fp32 slot [C][T][T] */
+  int32_t T, pad_top, pad_left, nh, nw; /* the slot's side and the (nh, nw) window of the flipped image in it; T T < 2^30 */
+  int32_t flip;                      /* bit 0: the view saw the image reversed in x, bit 1: in y */
+  int32_t kind;                      /* 0: the slot holds logits, 1: probabilities */
+  float weight;                      /* w_v / sum of the weights, rounded once from float64 */
+  int32_t pad_[2];
+} segk_view_desc;
+/* views_dev: a DEVICE table of V descriptors (1 <= V <= SEGK_MAX_VIEWS), 16-byte aligned; the host never reads it, so its
+ * contents are the caller's to get right (image_segmentation_amd/tta.py: view_table checks them).  Per output pixel (oy, ox),
+ * for v = 0..V-1 in table order: z = the view sampled at (flip & 2 ? oh-1-oy : oy, flip & 1 ? ow-1-ox : ox) with the
+ * arithmetic of segk_crop_resize (mode 0 bilinear, 1 nearest), then the accumulation above in fp32.  mask = argmax of acc
+ * (first maximum, NaN maximal: segk_predict_mask's rule); color, palette, counts, labels and M as in segk_predict_mask.
+ * Optional: conf [oh,ow] uint8 = (uint8)(255 p_best + 0.5) and scores fp32 [C,oh,ow] = p, with p = acc / sum_k acc
+ * (merge 0) or softmax(acc) (merge 1); a NaN confidence is stored as 0.  No float atomics: bit-stable from run to run.
+ * 1 <= C <= 8; mask, color and conf 4-byte aligned; oh ow < 2^31 - 4.  Only the scalar arguments and the output pointers
+ * are validated (-2 before any launch). */
+int segk_predict_merge(const void* views_dev, int V, int C, int merge, int mode, int oh, int ow, uint8_t* mask,
+                       uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels, uint64_t* M,
+                       uint8_t* conf, float* scores, segk_stream_t s);
 
 /* ---- mask clean-up: connected components, boxes, blob removal (the reference has no such code: this
  * replaces a mask.cpu() + scipy.ndimage.label post-process).  Integer arithmetic only: results are unique and bit-stable.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -611,7 +611,88 @@ def components():
     print(f"components clock probe: median {clk['median_ghz']} GHz; written to {path}")
 
 
+def tta():
+    """Multi-view prediction through the C ABI (csrc/resize.hip): segk_predict_merge -- mask, colour, class
+    counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
+    weights, "prob" merge of logits) against the materialised route it replaces: per view segk_crop_resize to full-size fp32
+    logits, torch.flip, softmax and a running weighted sum, then argmax, the confidence and segk_mask_finish.  Beside the
+    V = 1 line: segk_predict_mask on the same slot.  Both routes run in this process, alternating, seven rounds each: median
+    and min..max.  Also written to profiles/kbench_tta.json (or the file given with --out)."""
+    import json
+    import numpy as np
+    from image_segmentation_amd import tta as T_
+    from image_segmentation_amd.utils import _geometry
+    T, C, oh, ow = 224, 4, 1200, 1600
+    st = ops._stream()
+    nh, nw, pt, pl, _ = _geometry(oh, ow, T)
+    pal = torch.tensor([(0, 0, 0), (255, 0, 0), (0, 255, 0), (0, 0, 255)], dtype=torch.uint8, device="cuda")
+    mask, conf = (torch.empty((oh, ow), dtype=torch.uint8, device="cuda") for _ in range(2))
+    color = torch.empty((oh, ow, 3), dtype=torch.uint8, device="cuda")
+    counts = torch.zeros(8, dtype=torch.int64, device="cuda")
+    full = torch.empty((C, oh, ow), device="cuda")
+    dims = {0: (), 1: (-1,), 2: (-2,), 3: (-2, -1)}
+
+    def rounds(fns, iters=50):
+        ts = [[] for _ in fns]
+        for _ in range(7):
+            for t, fn in zip(ts, fns):
+                t.append(timeit(fn, iters))
+        return [{"median": sorted(t)[3], "min": min(t), "max": max(t)} for t in ts]
+
+    rows = []
+    for V in (1, 2, 6):
+        slots = [torch.randn((C, T, T), device="cuda") for _ in range(V)]
+        table = T_.view_table([(s.data_ptr(), T, pt, pl, nh, nw, v % 4, 0, 1.0) for v, s in enumerate(slots)])
+        weights = [torch.tensor(w, device="cuda") for w in table["weight"]]
+        dev = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).cuda()
+
+        def fused():
+            _lib.call("segk_predict_merge", dev.data_ptr(), V, C, 0, 0, oh, ow, mask.data_ptr(), color.data_ptr(), pal.data_ptr(),
+                      counts.data_ptr(), None, None, conf.data_ptr(), None, st)
+
+        def old():
+            acc = None
+            for v, s in enumerate(slots):
+                _lib.call("segk_crop_resize", s.data_ptr(), full.data_ptr(), C, T, pt, pl, nh, nw, oh, ow, 0, st)
+                p = weights[v] * torch.softmax(torch.flip(full, dims[v % 4]) if v % 4 else full, 0)
+                acc = p if acc is None else acc + p
+            m = acc.argmax(0).to(torch.uint8)
+            cf = (255 * (acc.max(0).values / acc.sum(0)) + 0.5).to(torch.uint8)
+            _lib.call("segk_mask_finish", m.data_ptr(), color.data_ptr(), pal.data_ptr(), counts.data_ptr(), None, None, C, oh, ow, st)
+            return m, cf
+
+        def single():
+            _lib.call("segk_predict_mask", slots[0].data_ptr(), mask.data_ptr(), color.data_ptr(), pal.data_ptr(), counts.data_ptr(),
+                      None, None, C, T, pt, pl, nh, nw, oh, ow, 0, st)
+        m_old, cf_old = old()
+        fused()
+        differ = int((mask != m_old).sum())
+        conf_off = int((conf.int() - cf_old.int()).abs().max())
+        fns = [fused, old] + ([single] if V == 1 else [])
+        res = rounds(fns)
+        row = {"V": V, "size": [oh, ow], "C": C, "T": T, "predict_merge_us": res[0], "materialised_us": res[1],
+               "mask_pixels_differing": differ, "confidence_max_difference": conf_off}
+        line = (f"tta {oh}x{ow} C={C} V={V}  segk_predict_merge {res[0]['median']:8.1f} us [{res[0]['min']:.1f}..{res[0]['max']:.1f}]   "
+                f"materialised {res[1]['median']:9.1f} us [{res[1]['min']:.1f}..{res[1]['max']:.1f}]   "
+                f"{res[1]['median'] / res[0]['median']:5.1f}x   mask pixels differing {differ}, confidence off by <= {conf_off}")
+        if V == 1:
+            row["predict_mask_us"] = res[2]
+            line += f"   segk_predict_mask {res[2]['median']:8.1f} us [{res[2]['min']:.1f}..{res[2]['max']:.1f}]"
+        rows.append(row)
+        print(line)
+    clk = ops.clock_probe()
+    path = os.path.join(ROOT, "profiles", "kbench_tta.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump({"rows": rows, "clock_probe_ghz": clk["median_ghz"], "build_id": _lib.build_id()}, f, indent=1)
+    print(f"tta clock probe: median {clk['median_ghz']} GHz; written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "tta":
+        tta()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "components":
         components()
         sys.exit(0)
