@@ -15,4 +15,5 @@ from .augment import (Augmenter, AugPlan, AugmentedBatches, merge_pairs, class_w
 from .robustness import (PERTURBATIONS, DEFAULT_LEVELS, PerturbPlan, gauss_table, value_lut, perturb_plan, perturb,      # noqa: F401
                          robustness_sweep, cell_seed, image_seed)
 from .tta import TTA, view_table, view_order, VIEW_DESC                                                      # noqa: F401
+from .tiles import Tiles, tile_axis, tile_plan                                                                # noqa: F401
 from .components import components, Components, Clean, mask_finish                                          # noqa: F401

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 317          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 318          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
@@ -77,6 +77,9 @@ SIGNATURES = {
     "segk_resize_pad_flip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_resize_pad_u8_flip": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_predict_merge": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _vp]),
+    "segk_tile_gather_u8": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_tile_gather": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_predict_tiles": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _vp]),
     "segk_cc_label": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_cc_clean": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_mask_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

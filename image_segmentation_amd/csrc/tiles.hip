@@ -1,0 +1,465 @@
+// Tiled full-resolution prediction: tile gather and blend.  The reference holds no code for this.
+//   tile_gather(_u8)   image at its own resolution -> the T x T network inputs of tiles tile0 .. tile0 + ntiles - 1
+//   predict_tiles      the tiles' network outputs -> one mask (+ colour, counts, confusion, confidence, scores)
+// No resampling anywhere: a tile pixel IS an image pixel.  The tile plan is derived in the kernels from (L, T, overlap)
+// per axis (image_segmentation_amd/tiles.py: tile_axis is the same arithmetic): stride s = T - overlap;
+//   L <= T: one tile at -((T - L) / 2);   L > T: n = ceil((L - T) / s) + 1 tiles at min(i s, L - T).
+#include <type_traits>
+
+#include "../../include/segk.h"
+#include "segk_internal.h"
+
+namespace {
+
+// One axis of the plan.  last is the origin of tile n - 1: tiles 0 .. n - 2 ("regular") start at i s < L - T.
+struct Axis {
+  int L, s, n, last;
+};
+
+inline int tile_count(int L, int T, int s) { return L <= T ? 1 : (L - T + s - 1) / s + 1; }
+inline Axis make_axis(int L, int T, int overlap) {
+  Axis a;
+  a.L = L; a.s = T - overlap; a.n = tile_count(L, T, a.s);
+  a.last = L <= T ? -((T - L) / 2) : L - T;
+  return a;
+}
+
+__device__ __forceinline__ int tile_origin(const Axis& a, int i) { return i == a.n - 1 ? a.last : i * a.s; }
+
+// pad = reflect without the edge pixel, repeated as often as needed (L = 3 in T = 32)
+__device__ __forceinline__ int reflect_index(int g, int L) {
+  if (L == 1) return 0;
+  const int m = 2 * L - 2;
+  int j = g % m;
+  j = j < 0 ? j + m : j;
+  return j < L ? j : m - j;
+}
+
+// Source coordinate of tile pixel g on an axis of length L, and whether the value is kept (else 0).  Only a short axis
+// (L < T: `padded`, uniform over the launch) can leave the image; on a long axis g is the coordinate itself, so interior
+// tiles pay for no index arithmetic and every load is unconditional: the index is clamped or reflected, the value selected.
+__device__ __forceinline__ int src_coord(int g, int L, bool padded, int pad, bool& keep) {
+  keep = true;
+  if (!padded) return g;
+  if (pad == SEGK_TILE_PAD_REFLECT) return reflect_index(g, L);
+  keep = (unsigned)g < (unsigned)L;
+  return clampi(g, 0, L - 1);
+}
+
+// A thread owns four consecutive x of one slot row: CO channels of them for the 8-bit image (the CO bytes of a source
+// pixel sit together), one channel for the planar float image.  Adjacent threads read adjacent source pixels of one image
+// row and store adjacent 16-byte vectors (VEC: T % 4 == 0 and a 16-byte aligned `out`); otherwise scalar stores, and the
+// row's last thread repeats column T - 1 for the loads of the columns it does not store.
+template <int CIN, bool VEC>
+__global__ __launch_bounds__(256) void tile_gather_u8_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H, int W,
+                                                             int T, Axis ay, Axis ax, int pad, int tile0, int ntiles) {
+  constexpr int CO = CIN < 3 ? CIN : 3;
+  const int Q = (T + 3) >> 2;
+  const unsigned total = (unsigned)ntiles * T * Q;               // < 2^31: checked by the entry
+  const bool py = H < T, px = W < T;
+  const size_t TT = (size_t)T * T;
+  auto ld = [&](int y, int x, float (&t)[CO]) {
+    const uint8_t* q = img + ((size_t)y * W + x) * CIN;
+    if constexpr (CIN == 4) {   // one aligned dword; the alpha byte is dropped
+      const uint32_t w = *(const uint32_t*)q;
+      t[0] = (float)(w & 255u) / 255.0f;
+      t[1] = (float)((w >> 8) & 255u) / 255.0f;
+      t[2] = (float)((w >> 16) & 255u) / 255.0f;
+    } else {
+#pragma unroll
+      for (int k = 0; k < CO; ++k) t[k] = (float)q[k] / 255.0f;      // segk_resize_pad_u8's expression
+    }
+  };
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const unsigned r = i / Q;
+    const int q = (int)(i - r * Q), lt = (int)(r / T), ty = (int)(r - (unsigned)lt * T);
+    const int t = tile0 + lt, iy = t / ax.n, ix = t - iy * ax.n;
+    bool ky;
+    const int sy = src_coord(tile_origin(ay, iy) + ty, H, py, pad, ky);
+    const int x0 = tile_origin(ax, ix);
+    float v[4][CO];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int tx = 4 * q + j < T ? 4 * q + j : T - 1;
+      bool kx;
+      const int sx = src_coord(x0 + tx, W, px, pad, kx);
+      float u[CO];
+      ld(sy, sx, u);
+#pragma unroll
+      for (int k = 0; k < CO; ++k) v[j][k] = (ky & kx) ? u[k] : 0.f;
+    }
+    float* o = out + (size_t)lt * CO * TT + (size_t)ty * T + 4 * q;
+    if (VEC) {
+#pragma unroll
+      for (int k = 0; k < CO; ++k) *(float4*)(o + k * TT) = make_float4(v[0][k], v[1][k], v[2][k], v[3][k]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * q + j < T) {
+#pragma unroll
+          for (int k = 0; k < CO; ++k) o[k * TT + j] = v[j][k];
+        }
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void tile_gather_kernel(const float* __restrict__ img, float* __restrict__ out, int C, int H, int W,
+                                                          int T, Axis ay, Axis ax, int pad, int tile0, int ntiles) {
+  const int Q = (T + 3) >> 2;
+  const unsigned total = (unsigned)ntiles * C * T * Q;           // < 2^31: checked by the entry
+  const bool py = H < T, px = W < T;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const unsigned r = i / Q;                   // (lt * C + c) * T + ty: the slot row, which is the output row too
+    const unsigned lc = r / T;
+    const int q = (int)(i - r * Q), ty = (int)(r - lc * T), lt = (int)(lc / C), c = (int)(lc - (unsigned)lt * C);
+    const int t = tile0 + lt, iy = t / ax.n, ix = t - iy * ax.n;
+    bool ky;
+    const int sy = src_coord(tile_origin(ay, iy) + ty, H, py, pad, ky);
+    const int x0 = tile_origin(ax, ix);
+    const float* row = img + ((size_t)c * H + sy) * W;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int tx = 4 * q + j < T ? 4 * q + j : T - 1;
+      bool kx;
+      const int sx = src_coord(x0 + tx, W, px, pad, kx);
+      const float u = row[sx];
+      v[j] = (ky & kx) ? u : 0.f;
+    }
+    float* o = out + (size_t)r * T + 4 * q;
+    if (VEC) {
+      *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * q + j < T) o[j] = v[j];
+    }
+  }
+}
+
+// ---- blend ---------------------------------------------------------------------------------------------------------------
+// m = max z, e_k = expf(z_k - m), p_k = e_k / sum_k e_k, the sum in class order: the source expression of resize.hip's
+// softmax_classes, so one input gives one bit pattern in both kernels
+template <int NC>
+__device__ __forceinline__ void softmax_classes(float (&z)[NC], int C) {
+  float m = z[0];
+#pragma unroll
+  for (int k = 1; k < NC; ++k) m = z[k] > m ? z[k] : m;
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    z[k] = expf(z[k] - m);
+    sum = sum + ((NC <= 4 || k < C) ? z[k] : 0.f);
+  }
+#pragma unroll
+  for (int k = 0; k < NC; ++k) z[k] = z[k] / sum;
+}
+
+// The regular tiles (0 .. n - 2, origin i s) that cover coordinate g are ilo .. ihi, at most two because T <= 2 s: with
+// q = g / s tile q covers g (q s <= g < q s + s <= q s + T), tile q - 1 does when (q - 1) s + T - 1 >= g, and tile q - 2
+// never ((q - 2) s + T - 1 >= g would need T > 2 s).  None when ihi < ilo (n == 1, or g beyond the regular tiles).
+__device__ __forceinline__ void regular_range(int g, int T, const Axis& a, int& ilo, int& ihi) {
+  const int q = g / a.s;
+  ilo = (q >= 1 && (q - 1) * a.s + T - 1 >= g) ? q - 1 : q;
+  ihi = q < a.n - 2 ? q : a.n - 2;
+}
+
+// Candidate c of coordinate g, in ascending tile order: c = 0, 1 the regular tiles ilo, ilo + 1, c = 2 the last tile (pulled
+// back inside the image, or the one tile of a short axis).  Returns whether it covers g; tile and the tile-local coordinate u
+// are clamped into range either way, so that the load behind them is unconditional.
+__device__ __forceinline__ bool candidate(const Axis& a, int T, int c, int g, int ilo, int ihi, int& tile, int& u) {
+  const int i = c < 2 ? ilo + c : a.n - 1;
+  const bool covers = c < 2 ? i <= ihi : g >= a.last;
+  tile = i < a.n - 1 ? i : a.n - 1;
+  u = clampi(g - tile_origin(a, tile), 0, T - 1);
+  return covers;
+}
+
+// predict_merge_kernel's skeleton (resize.hip) with tiles for views: a thread owns four consecutive flat pixels and walks
+// the at most 3 x 3 candidate tiles of each in row-major tile order over acc[4][NC].  A candidate that covers none of the
+// wave's pixels is skipped by a wave-uniform branch; otherwise its NC values are loaded unconditionally at clamped indices
+// and a tile that does not cover the pixel is dropped with a SELECT, never through a zero weight: Y may hold NaN wherever no
+// pixel maps.  Weights are integers below 2^24 (exact in fp32), Wtot is exact.  Classes past C repeat class C - 1 and can
+// never win the strict comparison; sums over classes skip them.
+template <int NC, bool LAB>
+__global__ __launch_bounds__(256) void predict_tiles_kernel(const float* __restrict__ Y, int C, int kind, int merge, int window, int H,
+                                                            int W, int T, Axis ay, Axis ax, uint8_t* __restrict__ mask,
+                                                            uint8_t* __restrict__ color, const uint8_t* __restrict__ palette,
+                                                            unsigned long long* __restrict__ counts,
+                                                            const long long* __restrict__ labels, unsigned long long* __restrict__ M,
+                                                            uint8_t* __restrict__ conf, float* __restrict__ scores) {
+  constexpr int NB = SEGK_MAX_CLASSES * SEGK_MAX_CLASSES;
+  __shared__ unsigned int hist[NB + SEGK_MAX_CLASSES];            // confusion bins, then class counts
+  if (threadIdx.x < NB + SEGK_MAX_CLASSES) hist[threadIdx.x] = 0;
+  unsigned int pal[NC], cnt[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) { pal[k] = 0; cnt[k] = 0; }
+  if (color) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const uint8_t* q = palette + 3 * (k < C ? k : C - 1);
+      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
+    }
+  }
+  __syncthreads();
+  const int total = H * W;
+  const unsigned TT4 = 4u * (unsigned)T * (unsigned)T;            // bytes of one class plane; all of Y is below 2^32 bytes
+  unsigned koff[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) koff[k] = (unsigned)(k < C ? k : C - 1) * TT4;
+  const bool soft = merge == SEGK_MERGE_PROB && kind == 0;
+  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
+    const int p = (int)(q * 4);
+    long long lab[4];
+    if (LAB) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
+    }
+    // the thread's four pixels (one past the end repeats the last); a thread may straddle a row end
+    int oy[4], ox[4];
+    oy[0] = p / W; ox[0] = p - oy[0] * W;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      oy[j] = oy[j - 1]; ox[j] = ox[j - 1];
+      if (p + j < total && ++ox[j] == W) { ox[j] = 0; ++oy[j]; }
+    }
+    int ylo[4], yhi[4], xlo[4], xhi[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      regular_range(oy[j], T, ay, ylo[j], yhi[j]);
+      regular_range(ox[j], T, ax, xlo[j], xhi[j]);
+    }
+    float acc[4][NC], wtot[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      wtot[j] = 0.f;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc[j][k] = 0.f;
+    }
+#pragma unroll 1
+    for (int a = 0; a < 3; ++a) {                                  // row-major tile order: the order is part of the result
+      int tyl[4], uy[4];
+      bool vy[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) vy[j] = candidate(ay, T, a, oy[j], ylo[j], yhi[j], tyl[j], uy[j]);
+      if (!__any(vy[0] | vy[1] | vy[2] | vy[3])) continue;
+#pragma unroll 1
+      for (int b = 0; b < 3; ++b) {
+        int txl[4], ux[4];
+        bool v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = candidate(ax, T, b, ox[j], xlo[j], xhi[j], txl[j], ux[j]) & vy[j];
+        if (!__any(v[0] | v[1] | v[2] | v[3])) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned off = (unsigned)(tyl[j] * ax.n + txl[j]) * (unsigned)C * TT4 + 4u * (unsigned)(uy[j] * T + ux[j]);
+          float z[NC];
+#pragma unroll
+          for (int k = 0; k < NC; ++k) z[k] = tap((const char*)Y, off + koff[k]);
+          if (soft) softmax_classes<NC>(z, C);
+          const int wy = (uy[j] < T - 1 - uy[j] ? uy[j] : T - 1 - uy[j]) + 1, wx = (ux[j] < T - 1 - ux[j] ? ux[j] : T - 1 - ux[j]) + 1;
+          const float w = window == SEGK_TILE_WINDOW_TRIANGLE ? (float)(wy * wx) : 1.f;
+#pragma unroll
+          for (int k = 0; k < NC; ++k) {
+            const float t = acc[j][k] + w * z[k];
+            acc[j][k] = v[j] ? t : acc[j][k];
+          }
+          wtot[j] = v[j] ? wtot[j] + w : wtot[j];
+        }
+      }
+    }
+    if (merge == SEGK_MERGE_LOGIT) {                               // a_k = acc_k / Wtot
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < NC; ++k) acc[j][k] = acc[j][k] / wtot[j];
+    }
+    const bool full = p + 3 < total;
+    int best[4];
+    unsigned int c4[4], cf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int bi = 0;
+      float bv = acc[j][0];
+#pragma unroll
+      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
+        const bool take = (acc[j][k] > bv) | ((acc[j][k] != acc[j][k]) & (bv == bv));
+        bv = take ? acc[j][k] : bv;
+        bi = take ? k : bi;
+      }
+      best[j] = bi;
+      const unsigned live = p + j < total ? 1u : 0u;
+      c4[j] = 0; cf[j] = 0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        cnt[k] += bi == k ? live : 0u;
+        c4[j] = bi == k ? pal[k] : c4[j];
+      }
+      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[bi * SEGK_MAX_CLASSES + (int)lab[j]], 1u);
+      if (conf || scores) {                               // p = acc / sum acc (prob) or softmax(a) (logit)
+        float pr[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) pr[k] = acc[j][k];
+        if (merge == SEGK_MERGE_PROB) {
+          float sum = 0.f;
+#pragma unroll
+          for (int k = 0; k < NC; ++k) sum = sum + ((NC <= 4 || k < C) ? pr[k] : 0.f);
+#pragma unroll
+          for (int k = 0; k < NC; ++k) pr[k] = pr[k] / sum;
+        } else {
+          softmax_classes<NC>(pr, C);
+        }
+        float pb = pr[0];
+#pragma unroll
+        for (int k = 1; k < NC; ++k) pb = bi == k ? pr[k] : pb;
+        const float c = 255.f * pb + 0.5f;
+        cf[j] = c >= 0.f ? (unsigned)(c > 255.f ? 255.f : c) : 0u;     // a NaN confidence is stored as 0
+        if (scores && live) {
+#pragma unroll
+          for (int k = 0; k < NC; ++k)
+            if (NC <= 4 || k < C) scores[(size_t)k * total + (unsigned)(p + j)] = pr[k];
+        }
+      }
+    }
+    if (full) {
+      *(uint32_t*)(mask + (unsigned)p) = (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
+      if (conf) *(uint32_t*)(conf + (unsigned)p) = cf[0] | (cf[1] << 8) | (cf[2] << 16) | (cf[3] << 24);
+      if (color)
+        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (p + j < total) {
+          mask[p + j] = (uint8_t)best[j];
+          if (conf) conf[p + j] = (uint8_t)cf[j];
+          if (color)
+            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
+        }
+    }
+  }
+  if (counts) {   // wave sums first: 64 lanes adding to one LDS word serialise
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      unsigned int c = cnt[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
+    }
+  }
+  __syncthreads();
+  // integer sums: one 64-bit atomic per non-zero bin per block, order-independent and bit-stable
+  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+  if (counts && threadIdx.x >= NB && threadIdx.x < NB + SEGK_MAX_CLASSES && hist[threadIdx.x])
+    atomicAdd(&counts[threadIdx.x - NB], (unsigned long long)hist[threadIdx.x]);
+}
+
+// the checks the three entries share: the plan's scalars, before anything is derived from them
+int check_plan(const char* name, int H, int W, int T, int overlap) {
+  SEGK_REQUIRE(H > 0 && W > 0 && (long)H * W < (1L << 31) - 4, "%s: image of %d x %d (sides positive, H W < 2^31 - 4)", name, H, W);
+  SEGK_REQUIRE(T >= 1 && T <= 4096, "%s: tile side 1..4096, got %d", name, T);
+  SEGK_REQUIRE(overlap >= 0 && overlap <= T / 2, "%s: overlap 0..T/2 = %d, got %d", name, T / 2, overlap);
+  return 0;
+}
+
+int check_gather(const char* name, const void* img, const float* out, int c, int H, int W, int T, int overlap, int pad, int tile0,
+                 int ntiles) {
+  SEGK_REQUIRE(img && out, "%s: NULL image or output", name);
+  if (int rc = check_plan(name, H, W, T, overlap)) return rc;
+  SEGK_REQUIRE(pad == SEGK_TILE_PAD_ZERO || pad == SEGK_TILE_PAD_REFLECT, "%s: bad pad mode %d", name, pad);
+  const long n = (long)tile_count(H, T, T - overlap) * tile_count(W, T, T - overlap);
+  SEGK_REQUIRE(tile0 >= 0 && ntiles >= 1 && (long)tile0 + ntiles <= n, "%s: tiles %d .. %d + %d of a plan of %ld", name, tile0, tile0,
+               ntiles, n);
+  SEGK_REQUIRE(((uintptr_t)out & 3) == 0, "%s: the output must be 4-byte aligned", name);
+  // the kernels index their work items (a thread's four columns of one slot row) with 32 bits
+  SEGK_REQUIRE((long)ntiles * T * ((T + 3) / 4) < (1L << 31) / c, "%s: %d tiles in one call: split the range", name, ntiles);
+  return 0;
+}
+
+long gather_grid(long items) {
+  long g = (items + 255) / 256;
+  return g > 16384 ? 16384 : g;
+}
+
+}  // namespace
+
+extern "C" int segk_tile_gather_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int T, int overlap, int pad, int tile0,
+                                   int ntiles, segk_stream_t s) {
+  SEGK_REQUIRE(Cin == 1 || Cin == 3 || Cin == 4, "tile_gather_u8: 1, 3 or 4 interleaved channels, got %d", Cin);
+  if (int rc = check_gather("tile_gather_u8", img_hwc, out, Cin < 3 ? Cin : 3, H, W, T, overlap, pad, tile0, ntiles)) return rc;
+  SEGK_REQUIRE(Cin != 4 || ((uintptr_t)img_hwc & 3) == 0, "tile_gather_u8: a 4-channel image must be 4-byte aligned");
+  const Axis ay = make_axis(H, T, overlap), ax = make_axis(W, T, overlap);
+  const long g = gather_grid((long)ntiles * T * ((T + 3) / 4));
+  const bool vec = T % 4 == 0 && ((uintptr_t)out & 15) == 0;
+  hipStream_t st = (hipStream_t)s;
+  auto launch = [&](auto cin, auto v) {
+    hipLaunchKernelGGL((tile_gather_u8_kernel<decltype(cin)::value, decltype(v)::value>), dim3((int)g), dim3(256), 0, st, img_hwc, out, H,
+                       W, T, ay, ax, pad, tile0, ntiles);
+  };
+  auto by_vec = [&](auto cin) {
+    if (vec) launch(cin, std::true_type{});
+    else launch(cin, std::false_type{});
+  };
+  if (Cin == 1) by_vec(std::integral_constant<int, 1>{});
+  else if (Cin == 3) by_vec(std::integral_constant<int, 3>{});
+  else by_vec(std::integral_constant<int, 4>{});
+  SEGK_CHECK_LAUNCH("tile_gather_u8");
+  return 0;
+}
+
+extern "C" int segk_tile_gather(const float* img_chw, float* out, int C, int H, int W, int T, int overlap, int pad, int tile0,
+                                int ntiles, segk_stream_t s) {
+  SEGK_REQUIRE(C >= 1 && C <= 65536, "tile_gather: 1..65536 channels, got %d", C);
+  if (int rc = check_gather("tile_gather", img_chw, out, C, H, W, T, overlap, pad, tile0, ntiles)) return rc;
+  SEGK_REQUIRE(((uintptr_t)img_chw & 3) == 0, "tile_gather: the image must be 4-byte aligned");
+  const Axis ay = make_axis(H, T, overlap), ax = make_axis(W, T, overlap);
+  const long g = gather_grid((long)ntiles * C * T * ((T + 3) / 4));
+  hipStream_t st = (hipStream_t)s;
+  if (T % 4 == 0 && ((uintptr_t)out & 15) == 0)
+    hipLaunchKernelGGL(tile_gather_kernel<true>, dim3((int)g), dim3(256), 0, st, img_chw, out, C, H, W, T, ay, ax, pad, tile0, ntiles);
+  else
+    hipLaunchKernelGGL(tile_gather_kernel<false>, dim3((int)g), dim3(256), 0, st, img_chw, out, C, H, W, T, ay, ax, pad, tile0, ntiles);
+  SEGK_CHECK_LAUNCH("tile_gather");
+  return 0;
+}
+
+extern "C" int segk_predict_tiles(const float* Y, int C, int kind, int merge, int window, int H, int W, int T, int overlap,
+                                  uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels,
+                                  uint64_t* M, uint8_t* conf, float* scores, segk_stream_t s) {
+  SEGK_REQUIRE(Y && mask, "predict_tiles: NULL tile outputs or mask");
+  SEGK_REQUIRE(C >= 1 && C <= SEGK_MAX_CLASSES, "predict_tiles: 1..%d classes supported, got %d", SEGK_MAX_CLASSES, C);
+  SEGK_REQUIRE(kind == 0 || kind == 1, "predict_tiles: kind is 0 (logits) or 1 (probabilities), got %d", kind);
+  SEGK_REQUIRE(merge == SEGK_MERGE_PROB || merge == SEGK_MERGE_LOGIT, "predict_tiles: bad merge %d", merge);
+  SEGK_REQUIRE(!(merge == SEGK_MERGE_LOGIT && kind == 1), "predict_tiles: the logit merge needs logits, not probabilities");
+  SEGK_REQUIRE(window == SEGK_TILE_WINDOW_FLAT || window == SEGK_TILE_WINDOW_TRIANGLE, "predict_tiles: bad window %d", window);
+  if (int rc = check_plan("predict_tiles", H, W, T, overlap)) return rc;
+  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "predict_tiles: color and palette come together");
+  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "predict_tiles: labels and M come together");
+  const Axis ay = make_axis(H, T, overlap), ax = make_axis(W, T, overlap);
+  SEGK_REQUIRE((long)ay.n * ax.n * C * T * T < (1L << 30), "predict_tiles: %d x %d tiles of %d x %d x %d: too large for 32-bit offsets",
+               ay.n, ax.n, C, T, T);
+  SEGK_REQUIRE(((uintptr_t)Y & 3) == 0, "predict_tiles: the tile outputs must be 4-byte aligned");
+  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)conf & 3) == 0 && ((uintptr_t)scores & 3) == 0,
+               "predict_tiles: mask, color, conf and scores must be 4-byte aligned");
+  long g = (((long)H * W + 3) / 4 + 255) / 256;
+  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;      // as segk_predict_mask: few blocks end in atomics
+  if (g > cap) g = cap;
+  hipStream_t st = (hipStream_t)s;
+  auto launch = [&](auto nc, auto lab) {
+    hipLaunchKernelGGL((predict_tiles_kernel<decltype(nc)::value, decltype(lab)::value>), dim3((int)g), dim3(256), 0, st, Y, C, kind,
+                       merge, window, H, W, T, ay, ax, mask, color, palette, (unsigned long long*)counts, (const long long*)labels,
+                       (unsigned long long*)M, conf, scores);
+  };
+  auto by_lab = [&](auto nc) {
+    if (labels) launch(nc, std::true_type{});
+    else launch(nc, std::false_type{});
+  };
+  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
+  if (C == 1) by_lab(std::integral_constant<int, 1>{});
+  else if (C == 2) by_lab(std::integral_constant<int, 2>{});
+  else if (C == 3) by_lab(std::integral_constant<int, 3>{});
+  else if (C == 4) by_lab(std::integral_constant<int, 4>{});
+  else by_lab(std::integral_constant<int, SEGK_MAX_CLASSES>{});
+  SEGK_CHECK_LAUNCH("predict_tiles");
+  return 0;
+}

@@ -14,7 +14,11 @@ inputs are already on the device; there is no CPU path.
 
 Several views of an image -- flips and target sizes (tta=TTA(...)) and several models (a list: an ensemble) -- are merged
 by segk_predict_merge in one pass per image from the views' network outputs: the mask, colour, counts,
-confusion counts and a confidence map, again without full-size float images."""
+confusion counts and a confidence map, again without full-size float images.
+
+tiles=Tiles(...) is the route for images larger than the training crop: the image is cut at its own
+resolution into overlapping tiles (segk_tile_gather / _u8), the tiles run as network batches, and segk_predict_tiles blends
+the overlapping outputs into the same set of outputs in one pass; nothing is resampled."""
 import inspect
 from dataclasses import dataclass
 from typing import Optional
@@ -22,7 +26,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib, ops, prompts, tta as _tta
+from . import _lib, ops, prompts, tiles as _tiles, tta as _tta
 from .augment import _upload
 from .clipunet import ClipUNet
 from .components import Components, as_clean, components as _components
@@ -165,6 +169,52 @@ def _fixed_input_size(model):
     return None if config is None else int(config.image_size)
 
 
+def _image_size(image):
+    return tuple(image.shape[:2]) if image.dtype == torch.uint8 else tuple(image.shape[-2:])
+
+
+def _gather_tiles(image, out, T, overlap, pad, tile0, what):
+    """Tiles tile0 .. tile0 + len(out) - 1 of one image or heat-map -> out [m,c,T,T]: uint8 [H,W,Cin] / [H,W] through
+    segk_tile_gather_u8, float [C,H,W] through segk_tile_gather."""
+    m, c = int(out.shape[0]), int(out.shape[1])
+    if image.dtype == torch.uint8:
+        if image.ndim == 2:
+            image = image.unsqueeze(-1)
+        if image.ndim != 3 or image.shape[2] not in (1, 3, 4):
+            raise ValueError(f"{what}: 8-bit inputs are [H,W,C] with 1, 3 or 4 channels (or [H,W]), got {tuple(image.shape)}")
+        H, W, cin = image.shape
+        if min(cin, 3) != c:
+            raise ValueError(f"{what}: {min(cin, 3)} channels where the batch has {c}")
+        src = image.contiguous()
+        if cin == 4 and src.data_ptr() % 4:
+            src = src.clone()
+        _lib.call("segk_tile_gather_u8", src.data_ptr(), out.data_ptr(), cin, H, W, T, overlap, pad, tile0, m, ops._stream())
+        return
+    if not torch.is_floating_point(image) or image.ndim != 3:
+        raise ValueError(f"{what}: expected a float [C,H,W] tensor or a uint8 [H,W,C] image, got {image.dtype} {tuple(image.shape)}")
+    if image.shape[0] == 4:
+        image = image[:3]
+    if image.shape[0] != c:
+        raise ValueError(f"{what}: {image.shape[0]} channels where the batch has {c}")
+    src = image.float().contiguous()
+    _lib.call("segk_tile_gather", src.data_ptr(), out.data_ptr(), c, int(src.shape[1]), int(src.shape[2]), T, overlap, pad, tile0, m,
+              ops._stream())
+
+
+def _tile_size_rule(model):
+    """(multiple, why): the tile sides a convolutional model accepts -- every 2x2 pooling halves the side exactly and the
+    transposed convolutions double it back, so the side is a multiple of 2^poolings"""
+    from .autoencoder import Encoder
+    from .unet import unet
+    rule = (1, "")
+    for m in model.modules():
+        if isinstance(m, unet):
+            rule = max(rule, (16, "a U-Net pools four times"))
+        elif isinstance(m, Encoder):
+            rule = max(rule, (8, "the autoencoder's encoder pools three times"))
+    return rule
+
+
 class Segmenter:
     """Callable prediction pipeline around a trained model: `Segmenter(model)(images)` -> list of Prediction.
 
@@ -189,10 +239,19 @@ class Segmenter:
     outputs=  what a model returns, "logits" or "probs", one string or one per model; default "probs" for a PromptModel,
               else "logits" ("logit" merging refuses probabilities)
     return_scores=  Prediction.scores = the merged, normalised class scores, float32 [C,H,W]
-    Prediction.confidence (uint8 [H,W]) is set whenever views are merged; heat-maps and points are flipped with their image."""
+    Prediction.confidence (uint8 [H,W]) is set whenever views are merged; heat-maps and points are flipped with their image.
+
+    Tiled full-resolution prediction (without it every output and the code path are as above):
+    tiles=    a tiles.Tiles (or a dict of its keywords): the image is cut at its own size into size x size tiles (default:
+              target_size) overlapping by `overlap`, and the tiles' outputs are blended ("triangle" / "flat" window, "prob" /
+              "logit" merge); interpolation and antialias are not used.  batch_size counts TILES per forward: a forward is
+              filled with consecutive images' tiles (at least one image), an image with more tiles runs alone in
+              ceil(n / batch_size) forwards.  One model, no tta=; a ClipUNet needs size == its input size, a U-Net a multiple
+              of 16, the autoencoders of 8.  outputs=, return_scores=, clean=, heatmaps / points and labels work as above;
+              Prediction.confidence is always set; meta holds original_size, tile_size, overlap and tiles=(ny, nx)."""
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
-                 sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False):
+                 sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False, tiles=None):
         models = list(model) if isinstance(model, (list, tuple)) else [model]
         if not models:
             raise ValueError("an ensemble needs at least one model")
@@ -214,6 +273,11 @@ class Segmenter:
         if self.num_classes is not None:
             _check_classes(self.num_classes, self._palette)
         self.models, self.return_scores = models, bool(return_scores)
+        self.tiles = None
+        if tiles is not None:
+            self._merged = False
+            self._init_tiles(tiles, tta, model_weights, outputs)
+            return
         self._merged = tta is not None or len(models) > 1 or self.return_scores
         if not self._merged:
             if model_weights is not None or outputs is not None:
@@ -246,6 +310,29 @@ class Segmenter:
                 raise ValueError(f"model {k} is a ClipUNet whose ViT takes {fixed} x {fixed} inputs only: "
                                  f"target_size / TTA sizes must be {fixed}")
 
+    def _init_tiles(self, tiles, tta, model_weights, outputs):
+        if isinstance(tiles, dict):
+            tiles = _tiles.Tiles(**tiles)
+        if not isinstance(tiles, _tiles.Tiles):
+            raise ValueError(f"tiles: a Tiles or a dict of its keywords, got {type(tiles).__name__}")
+        if tta is not None or len(self.models) > 1 or model_weights is not None:
+            raise ValueError("tiles= does not combine with tta=, several models or model_weights=")
+        model = self.model
+        if outputs is None:
+            outputs = "probs" if _is_prompt_model(model) else "logits"
+        if outputs not in _tta.KINDS:
+            raise ValueError(f"outputs: one of {tuple(_tta.KINDS)}, got {outputs!r}")
+        if tiles.merge == "logit" and outputs == "probs":
+            raise ValueError('merge="logit" needs a model that returns logits; this one returns probabilities')
+        size, overlap = tiles.resolve(self.target_size)
+        fixed = _fixed_input_size(model)
+        if fixed is not None and size != fixed:
+            raise ValueError(f"the model is a ClipUNet whose ViT takes {fixed} x {fixed} inputs only: the tile size must be {fixed}")
+        multiple, why = _tile_size_rule(model)
+        if size % multiple:
+            raise ValueError(f"tile size {size}: {why}, the tile side must be a multiple of {multiple}")
+        self.tiles, self.outputs, self._tile = tiles, [outputs], (size, overlap)
+
     def _palette_on(self, dev):
         if self._palette is None:
             return None
@@ -263,7 +350,7 @@ class Segmenter:
                 raise ValueError("points were given to a model whose forward takes the image alone")
             if len(points) != n:
                 raise ValueError(f"{len(points)} point sets for {n} images")
-            sizes = [tuple(im.shape[:2]) if im.dtype == torch.uint8 else tuple(im.shape[-2:]) for im in images]
+            sizes = [_image_size(im) for im in images]
             points = [prompts._points_array(p, H, W, f"points[{k}]") for k, (p, (H, W)) in enumerate(zip(points, sizes))]
         if self._two_input and heatmaps is None and points is None:
             raise ValueError("this model takes (image, heatmap): pass heatmaps= or points=")
@@ -287,6 +374,8 @@ class Segmenter:
             for model in self.models:
                 model.eval()
             with torch.no_grad(), torch.cuda.device(dev):
+                if self.tiles is not None:
+                    return self._tiled(dev, images, heatmaps, points, labels)
                 for i in range(0, n, self.batch_size):
                     j = min(i + self.batch_size, n)
                     hm = None if heatmaps is None else heatmaps[i:j]
@@ -445,7 +534,122 @@ class Segmenter:
         # in stream order, as it does for the batch of the single-view path
         return preds
 
+    def _tiled(self, dev, images, heatmaps, points, labels):
+        """The tiled route: forwards of at most batch_size tiles, filled across consecutive images (at least one image); an
+        image with more tiles runs alone.  One segk_predict_tiles per image."""
+        T, overlap = self._tile
+        n = len(images)
+        plans = []
+        for k, im in enumerate(images):
+            if im.ndim not in (2, 3):
+                raise ValueError(f"image {k}: expected a float [C,H,W] tensor or a uint8 [H,W,C] image, got {tuple(im.shape)}")
+            H, W = _image_size(im)
+            if H < 1 or W < 1:
+                raise ValueError(f"image {k} is empty: {tuple(im.shape)}")
+            plans.append((H, W, len(_tiles.tile_axis(H, T, overlap)), len(_tiles.tile_axis(W, T, overlap))))
+        out, i = [], 0
+        while i < n:
+            j, total = i + 1, plans[i][2] * plans[i][3]
+            while j < n and total + plans[j][2] * plans[j][3] <= self.batch_size:
+                total += plans[j][2] * plans[j][3]
+                j += 1
+            hm = None if heatmaps is None else [_as_tensor(h).to(dev, non_blocking=True) for h in heatmaps[i:j]]
+            if points is not None:          # click(s) -> heat-map on the device, at the image's own size
+                hm = [prompts._heatmap_on(torch.from_numpy(p).to(dev, non_blocking=True), *plans[i + k][:2], self.sigma, dev)
+                      for k, p in enumerate(points[i:j])]
+            out += self._tile_group(dev, [im.to(dev, non_blocking=True) for im in images[i:j]], hm,
+                                    None if labels is None else labels[i:j], plans[i:j])
+            i = j
+        return out
+
+    def _tile_forward(self, dev, parts, c):
+        """One forward over the tile ranges `parts` = [(image, heat-map or None, tile0, m)] -> y [sum m, C, T, T] fp32"""
+        T, overlap = self._tile
+        pad = _tiles.PADS[self.tiles.pad]
+        total = sum(m for *_, m in parts)
+        X = torch.empty((total, c, T, T), dtype=torch.float32, device=dev)
+        Hm = torch.empty((total, 1, T, T), dtype=torch.float32, device=dev) if parts[0][1] is not None else None
+        off = 0
+        for im, hm, tile0, m in parts:
+            _gather_tiles(im, X[off:off + m], T, overlap, pad, tile0, "image")
+            if hm is not None:
+                _gather_tiles(hm, Hm[off:off + m], T, overlap, pad, tile0, "heatmap")
+            off += m
+        y = self.model(X) if Hm is None else self.model(X, Hm)
+        ops._require_cuda(y, "Segmenter (model output)")
+        y = y.detach()
+        if y.ndim != 4 or y.shape[0] != total or y.shape[2] != T or y.shape[3] != T:
+            raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
+        if y.dtype != torch.float32 or not y.is_contiguous():
+            y = y.float().contiguous()
+        return y
+
+    def _tile_group(self, dev, images, heatmaps, labels, plans):
+        T, overlap = self._tile
+        n, c = len(images), _channels(images[0])
+        if heatmaps is not None:
+            for k, hm in enumerate(heatmaps):
+                if _image_size(hm) != plans[k][:2] or _channels(hm) != 1:
+                    raise ValueError(f"heatmap {k} is {tuple(hm.shape)}, its image {plans[k][:2]}")
+        counts_t = [ny * nx for _, _, ny, nx in plans]
+        if n > 1 or counts_t[0] <= self.batch_size:
+            y = self._tile_forward(dev, [(im, None if heatmaps is None else heatmaps[k], 0, counts_t[k])
+                                         for k, im in enumerate(images)], c)
+            offs = np.cumsum([0] + counts_t)
+            Ys = [y[offs[k]:offs[k + 1]] for k in range(n)]
+        else:       # one image in ceil(n / batch_size) forwards, its outputs collected into one contiguous buffer
+            Y = None
+            for t0 in range(0, counts_t[0], self.batch_size):
+                m = min(self.batch_size, counts_t[0] - t0)
+                y = self._tile_forward(dev, [(images[0], None if heatmaps is None else heatmaps[0], t0, m)], c)
+                if Y is None:
+                    Y = torch.empty((counts_t[0],) + tuple(y.shape[1:]), dtype=torch.float32, device=dev)
+                elif y.shape[1] != Y.shape[1]:
+                    raise ValueError(f"the model returned {int(y.shape[1])} classes, the forwards before it {int(Y.shape[1])}")
+                Y[t0:t0 + m].copy_(y)
+            Ys = [Y]
+        C = int(Ys[0].shape[1])
+        pal = self._palette_on(dev)
+        _check_classes(C, pal)
+        counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
+        M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
+        kind, merge = _tta.KINDS[self.outputs[0]], _tta.MERGES[self.tiles.merge]
+        window = _tiles.WINDOWS[self.tiles.window]
+        s = ops._stream()
+        preds = []
+        for k, (oh, ow, ny, nx) in enumerate(plans):
+            meta = {"original_size": (oh, ow), "tile_size": T, "overlap": overlap, "tiles": (ny, nx)}
+            mask = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+            conf = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+            scores = torch.empty((C, oh, ow), dtype=torch.float32, device=dev) if self.return_scores else None
+            color = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev) if pal is not None else None
+            lab = None
+            if labels is not None:
+                lab = _as_tensor(labels[k])
+                if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
+                    raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
+                lab = lab.to(dev, non_blocking=True).long().contiguous()
+            Mk = None if M is None else M[k]
+            if self.clean is None:
+                _lib.call("segk_predict_tiles", Ys[k].data_ptr(), C, kind, merge, window, oh, ow, T, overlap, mask.data_ptr(),
+                          ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab), ops._p(Mk), conf.data_ptr(), ops._p(scores), s)
+                preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
+                preds[-1].confidence, preds[-1].scores = conf, scores
+                continue
+            # the blended argmax alone, its components and the cleaned mask, then the other outputs from the cleaned mask
+            _lib.call("segk_predict_tiles", Ys[k].data_ptr(), C, kind, merge, window, oh, ow, T, overlap, mask.data_ptr(), None, None,
+                      None, None, None, conf.data_ptr(), ops._p(scores), s)
+            cl = self.clean
+            comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
+            _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
+                      ops._p(Mk), C, oh, ow, s)
+            preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
+            preds[-1].confidence, preds[-1].scores = conf, scores
+        # the tile outputs are read by launches still in flight: the caching allocator keeps them valid in stream order
+        return preds
+
 
 def predict(model, images, heatmaps=None, labels=None, points=None, **kw):
-    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels, points); clean= is a Segmenter keyword."""
+    """One-shot convenience: Segmenter(model, **kw)(images, heatmaps, labels, points); clean= and tiles= are Segmenter
+    keywords."""
     return Segmenter(model, **kw)(images, heatmaps=heatmaps, labels=labels, points=points)

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 317
-#define SEGK_ENTRY_COUNT 91
+#define SEGK_ABI_VERSION 318
+#define SEGK_ENTRY_COUNT 94
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -300,6 +300,44 @@ typedef struct segk_view_desc {      /* one view; 48 bytes, 16-byte aligned */
  * 1 <= C <= 8; mask, color and conf 4-byte aligned; oh ow < 2^31 - 4.  Only the scalar arguments and the output pointers
  * are validated (-2 before any launch). */
 int segk_predict_merge(const void* views_dev, int V, int C, int merge, int mode, int oh, int ow, uint8_t* mask,
+                       uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels, uint64_t* M,
+                       uint8_t* conf, float* scores, segk_stream_t s);
+
+/* ---- tiled full-resolution prediction: tile gather and blend (the reference holds no code for it) ----
+ * The image is cut at its own resolution into T x T tiles, the tiles run through the network as batches, and the overlapping
+ * outputs are blended into one mask; nothing is resampled.  The tile plan is derived INSIDE the kernels from the scalars (no
+ * descriptor table, no host-read array); image_segmentation_amd/tiles.py: tile_axis is the same arithmetic.  Per axis of
+ * length L, with stride s = T - overlap (0 <= overlap <= T / 2):
+ *   L <= T: one tile at origin -((T - L) / 2) (the image centred, the odd pixel after it);
+ *   L >  T: n = ceil((L - T) / s) + 1 tiles at origins min(i s, L - T) (the last tile pulled back inside the image).
+ * A pixel is covered by 1..3 tiles per axis; tiles are numbered row-major, t = iy nx + ix.
+ *
+ * segk_tile_gather_u8 / segk_tile_gather: tiles tile0 .. tile0 + ntiles - 1 of an 8-bit interleaved [H,W,Cin] image (Cin 1,
+ * 3 or 4; alpha dropped; value (float)u8 / 255.0f, segk_resize_pad_u8's expression) or a float [C,H,W] image (values
+ * unchanged) -> out fp32 [ntiles][min(Cin,3) or C][T][T].  Tile pixel (ty, tx) of tile (iy, ix) is image pixel (y_iy + ty,
+ * x_ix + tx); outside the image (an axis with L < T only) it is 0 (SEGK_TILE_PAD_ZERO) or the pixel at r(g, L)
+ * (SEGK_TILE_PAD_REFLECT): r = 0 for L == 1, else m = 2 L - 2, j = g mod m (non-negative), r = j < L ? j : m - j.
+ * 1 <= T <= 4096; tile0 >= 0, ntiles >= 1, tile0 + ntiles <= ny nx; ntiles c T ceil(T/4) < 2^31 per call (split the range
+ * otherwise); out 4-byte aligned (16-byte stores when T % 4 == 0 and out is 16-byte aligned); a 4-channel image 4-byte
+ * aligned. */
+#define SEGK_TILE_PAD_ZERO 0
+#define SEGK_TILE_PAD_REFLECT 1
+#define SEGK_TILE_WINDOW_FLAT 0      /* wa(u) = 1 */
+#define SEGK_TILE_WINDOW_TRIANGLE 1  /* wa(u) = min(u, T - 1 - u) + 1 */
+int segk_tile_gather_u8(const uint8_t* img_hwc, float* out, int Cin, int H, int W, int T, int overlap, int pad, int tile0,
+                        int ntiles, segk_stream_t s);
+int segk_tile_gather(const float* img_chw, float* out, int C, int H, int W, int T, int overlap, int pad, int tile0, int ntiles,
+                     segk_stream_t s);
+/* Y fp32 [ny nx][C][T][T]: the network outputs of ALL tiles of the plan, kind 0 logits / 1 probabilities.  Per output pixel
+ * (oy, ox), for the covering tiles in row-major tile order: z = Y[t][.][oy - y_iy][ox - x_ix], w = wa(ty) wa(tx) (an
+ * integer below 2^24: exact in fp32), s = softmax(z) (segk_predict_merge's) when merge is SEGK_MERGE_PROB and kind is 0,
+ * else z; acc_k = acc_k + w s_k (a multiply, then an add), Wtot = Wtot + w.  SEGK_MERGE_PROB: mask = argmax acc, p = acc /
+ * sum_k acc.  SEGK_MERGE_LOGIT (kind 0 only): a = acc / Wtot, mask = argmax a, p = softmax(a).  Argmax rule, color, palette,
+ * counts, labels, M, conf and scores as in segk_predict_merge.  Positions of Y that no pixel maps to (the padded border of
+ * a short axis) are never used: a NaN there reaches no output.  No float atomics: bit-stable from run to run.
+ * 1 <= C <= 8; ny nx C T T < 2^30; H W < 2^31 - 4; Y, mask, color, conf and scores 4-byte aligned; every scalar and pointer
+ * pairing is validated (-2 before any launch). */
+int segk_predict_tiles(const float* Y, int C, int kind, int merge, int window, int H, int W, int T, int overlap, uint8_t* mask,
                        uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels, uint64_t* M,
                        uint8_t* conf, float* scores, segk_stream_t s);
 

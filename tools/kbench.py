@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -689,7 +689,101 @@ def tta():
     print(f"tta clock probe: median {clk['median_ghz']} GHz; written to {path}")
 
 
+def tiles():
+    """Tiled full-resolution prediction through the C ABI (csrc/tiles.hip) at 1200 x 1600, C = 4, T = 256,
+    overlap 64, triangle window, "prob" merge of logits: segk_tile_gather_u8 of the whole plan plus segk_predict_tiles (mask,
+    colour, class counts and confidence in one pass) against the materialised torch route they replace: crop / pad every tile
+    out of the image, per-tile softmax, weighted add into full-size fp32 accumulators, divide, argmax, the confidence and
+    segk_mask_finish.  The network forward between the two halves is the same for both routes and left out.  Both routes run
+    in this process, alternating, seven rounds each: median and min..max.  Written to profiles/kbench_tiles.txt and .json (or
+    the .json given with --out, the .txt beside it)."""
+    import json
+    from image_segmentation_amd import tiles as T_
+    H, W, C, T, o = 1200, 1600, 4, 256, 64
+    st = ops._stream()
+    ys, xs = T_.tile_axis(H, T, o), T_.tile_axis(W, T, o)
+    n = len(ys) * len(xs)
+    pal = torch.tensor([(0, 0, 0), (255, 0, 0), (0, 255, 0), (0, 0, 255)], dtype=torch.uint8, device="cuda")
+    img = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device="cuda")
+    Y = torch.randn((n, C, T, T), device="cuda")
+    X = torch.empty((n, 3, T, T), device="cuda")
+    mask, conf = (torch.empty((H, W), dtype=torch.uint8, device="cuda") for _ in range(2))
+    color = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
+    counts = torch.zeros(8, dtype=torch.int64, device="cuda")
+    u = torch.arange(T, device="cuda")
+    wa = (torch.minimum(u, T - 1 - u) + 1).float()
+    w2 = wa[:, None] * wa[None, :]
+
+    def gather():
+        _lib.call("segk_tile_gather_u8", img.data_ptr(), X.data_ptr(), 3, H, W, T, o, 1, 0, n, st)
+
+    def blend():
+        _lib.call("segk_predict_tiles", Y.data_ptr(), C, 0, 0, 1, H, W, T, o, mask.data_ptr(), color.data_ptr(), pal.data_ptr(),
+                  counts.data_ptr(), None, None, conf.data_ptr(), None, st)
+
+    def fused():
+        gather()
+        blend()
+
+    def old_gather():
+        chw = img.permute(2, 0, 1).float() / 255.0
+        return torch.stack([chw[:, y:y + T, x:x + T] for y in ys for x in xs])
+
+    def old_blend():
+        acc = torch.zeros((C, H, W), device="cuda")
+        t = 0
+        for y in ys:
+            for x in xs:
+                acc[:, y:y + T, x:x + T] += w2 * torch.softmax(Y[t], 0)
+                t += 1
+        p = acc / acc.sum(0, keepdim=True)
+        m = p.argmax(0).to(torch.uint8)
+        cf = (255 * p.max(0).values + 0.5).to(torch.uint8)
+        _lib.call("segk_mask_finish", m.data_ptr(), color.data_ptr(), pal.data_ptr(), counts.data_ptr(), None, None, C, H, W, st)
+        return m, cf
+
+    def old():
+        old_gather()
+        return old_blend()
+
+    def rounds(fns, iters=20):
+        ts = [[] for _ in fns]
+        for _ in range(7):
+            for t, fn in zip(ts, fns):
+                t.append(timeit(fn, iters))
+        return [{"median": sorted(t)[3], "min": min(t), "max": max(t)} for t in ts]
+
+    m_old, cf_old = old()
+    fused()
+    torch.cuda.synchronize()
+    differ = int((mask != m_old).sum())
+    conf_off = int((conf.int() - cf_old.int()).abs().max())
+    tiles_equal = bool(torch.equal(X, old_gather()))
+    names = ["fused", "materialised", "segk_tile_gather_u8", "segk_predict_tiles", "torch crop/pad", "torch blend"]
+    res = dict(zip(names, rounds([fused, old, gather, blend, old_gather, old_blend])))
+    clk = ops.clock_probe()
+    lines = [f"tiles {H}x{W} C={C} T={T} overlap={o} ({len(ys)} x {len(xs)} = {n} tiles), triangle window, prob merge of logits"]
+    lines += [f"  {k:22s} {v['median']:9.1f} us [{v['min']:.1f}..{v['max']:.1f}]" for k, v in res.items()]
+    lines += [f"  materialised / fused   {res['materialised']['median'] / res['fused']['median']:9.1f} x",
+              f"  mask pixels differing {differ} of {H * W}, confidence off by <= {conf_off}, gathered tiles equal: {tiles_equal}",
+              f"  clock probe: median {clk['median_ghz']} GHz; build {_lib.build_id()}"]
+    print("\n".join(lines))
+    path = os.path.join(ROOT, "profiles", "kbench_tiles.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump({"size": [H, W], "C": C, "T": T, "overlap": o, "tiles": [len(ys), len(xs)], "us": res,
+                   "mask_pixels_differing": differ, "confidence_max_difference": conf_off, "gathered_tiles_equal": tiles_equal,
+                   "clock_probe_ghz": clk["median_ghz"], "build_id": _lib.build_id()}, f, indent=1)
+    with open(os.path.splitext(path)[0] + ".txt", "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "tiles":
+        tiles()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tta":
         tta()
         sys.exit(0)

@@ -12,7 +12,11 @@ non-largest components take their neighbours' class); --boxes FILE.json writes, 
 --tta h,v,hv adds flipped views to the plain one, --sizes 224,256 several target sizes, a repeated --checkpoint several models
 of the same kind (an ensemble); the views are merged on the device (--merge prob averages probabilities,
 --merge logit logits) and --confidence DIR writes DIR/<name>_confidence.png (8-bit, 255 = certain).  The prompt model's
-ViT takes 224 x 224 inputs only."""
+ViT takes 224 x 224 inputs only.
+--tile N segments every image at its own resolution in N x N tiles that overlap by --tile-overlap M pixels (default N / 4)
+and blends the tiles' outputs on the device (--tile-window triangle|flat weighs a tile's pixels, --tile-pad
+reflect|zero fills a tile beyond an image smaller than itself, --merge as above); --batch-size then counts tiles per forward.
+It does not combine with --tta, --sizes or several --checkpoint; --confidence works with it."""
 import argparse
 import os
 import sys
@@ -34,6 +38,10 @@ def main():
     ap.add_argument("--sizes", default=None, metavar="T,T", help="comma-separated target sizes (default: --size alone)")
     ap.add_argument("--merge", choices=["prob", "logit"], default="prob", help="how the views are merged")
     ap.add_argument("--confidence", metavar="DIR", help="write the merged views' confidence maps as 8-bit PNGs into DIR")
+    ap.add_argument("--tile", type=int, default=None, metavar="N", help="tiled full-resolution prediction with N x N tiles")
+    ap.add_argument("--tile-overlap", type=int, default=None, metavar="M", help="pixels two neighbouring tiles share (default N / 4)")
+    ap.add_argument("--tile-window", choices=["flat", "triangle"], default="triangle", help="blend weight of a tile's pixels")
+    ap.add_argument("--tile-pad", choices=["reflect", "zero"], default="reflect", help="a tile's content beyond a smaller image")
     ap.add_argument("--classes", type=int, default=4)
     ap.add_argument("--size", type=int, default=224, help="side of the square network input")
     ap.add_argument("--interpolation", choices=["bilinear", "nearest"], default="bilinear")
@@ -56,8 +64,18 @@ def main():
     if (args.model == "prompt") != bool(clicks):
         ap.error("--model prompt needs --point Y,X, and --point needs --model prompt")
 
+    tiles = None
+    if args.tile is not None:
+        if args.tta or args.sizes or len(args.checkpoint) > 1:
+            ap.error("--tile does not combine with --tta, --sizes or several --checkpoint")
+        tiles = dict(size=args.tile, overlap=args.tile_overlap, window=args.tile_window, pad=args.tile_pad, merge=args.merge)
+    elif args.tile_overlap is not None or args.tile_window != "triangle" or args.tile_pad != "reflect":
+        ap.error("--tile-overlap, --tile-window and --tile-pad need --tile N")
+
     tta = None
-    if args.tta or args.sizes or args.confidence or len(args.checkpoint) > 1 or args.merge != "prob":
+    if tiles is not None:
+        pass
+    elif args.tta or args.sizes or args.confidence or len(args.checkpoint) > 1 or args.merge != "prob":
         flips = ("",) + tuple(f for f in (args.tta or "").split(",") if f)
         try:
             sizes = tuple(int(t) for t in args.sizes.split(",")) if args.sizes else None
@@ -92,7 +110,7 @@ def main():
     palette = seg.COLOR_MAP if args.classes <= len(seg.COLOR_MAP) else None
     try:
         segmenter = seg.Segmenter(models if tta is not None else models[0], target_size=args.size, interpolation=args.interpolation,
-                                  palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta)
+                                  palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta, tiles=tiles)
     except ValueError as e:
         ap.error(str(e))
     if args.confidence:
