@@ -25,17 +25,13 @@ import stem_pool_cases as K
 import stem_pool_reference as R
 from bn_reference import apply_reference
 from conv_reference import channel_stats
+from matrix_helpers import (BITS_DT, NAN_BITS, SEGK_DT, TORCH_DT, assert_equal, assert_within, make_recorder, nan_buffer, ptr, stream,
+                            sync, take, write_parity)
 from stem_pool_cases import FINALIZE_CASES, NUM_CUS, POOL_CASES, STAT_CASES, STEM_CASES, STEM_WGRAD_DENSE, PoolCase
 
 pytestmark = pytest.mark.gpu
 
-TORCH_DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
-SEGK_DT = {"fp32": 0, "bf16": 1}
-NAN_BITS = {"bf16": 0x7FDE, "fp32": 0x7FDEAD00}      # quiet-NaN patterns: what a kernel must overwrite, and leave in the guard
-BITS_DT = {"bf16": torch.int16, "fp32": torch.int32}
-GUARD = 4096                                         # elements behind every output buffer
-
-_PARITY = {}                   # "kernel quantity regime" -> [worst error / bound, case id]
+_PARITY, record = make_recorder()                   # "kernel quantity regime" -> [worst error / bound, case id]
 
 
 @pytest.fixture(scope="module")
@@ -50,66 +46,9 @@ def lib():
     yield _lib
     out = os.environ.get("SEGK_STEM_POOL_PARITY_OUT")
     if out and _PARITY:
-        with open(out, "w") as f:
-            f.write("# worst error / bound per kernel, quantity and regime of tests/test_gpu_stem_pool_matrix.py (bounds derived in\n"
-                    "# tests/stem_pool_reference.py); 0.0000 on an exact run: every element equal to the float64 restatement\n")
-            for name in sorted(_PARITY):
-                f.write(f"{name:58s} {_PARITY[name][0]:.4f}   {_PARITY[name][1]}\n")
-
-
-def record(name, ratio, cid):
-    ratio = float(ratio)
-    if name not in _PARITY or ratio > _PARITY[name][0]:
-        _PARITY[name] = [ratio, cid]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _sync(what):
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:      # a GPU fault is sticky: nothing more is started on the device in this session
-        pytest.exit(f"{what}: the device reported {e}", returncode=3)
-
-
-def nan_buffer(n, dtype):
-    return torch.full((n + GUARD,), NAN_BITS[dtype], dtype=BITS_DT[dtype], device="cuda")
-
-
-def take(buf, n, dtype, what, written=None):
-    """the first n elements on the CPU in the dtype; all of them (or the first `written`) overwritten, the guard untouched"""
-    bits = buf.cpu()
-    assert bool((bits[n:] == NAN_BITS[dtype]).all()), f"{what}: wrote behind the buffer"
-    w = n if written is None else written
-    left = (bits[:w] == NAN_BITS[dtype]).nonzero()
-    assert len(left) == 0, f"{what}: {len(left)} of {w} elements were not written, first at {int(left[0])}"
-    return bits[:n].view(TORCH_DT[dtype])
-
-
-def ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def assert_equal(got, want, what):
-    got, want = got.float(), want.float()
-    if torch.equal(got, want):
-        return
-    idx = ((got != want) | torch.isnan(got)).nonzero()
-    lines = [f"  [{', '.join(map(str, i))}] = {got[tuple(i)].item()!r}, want {want[tuple(i)].item()!r}" for i in idx[:10].tolist()]
-    raise AssertionError(f"{what}: {len(idx)} of {got.numel()} elements differ\n" + "\n".join(lines))
-
-
-def assert_within(got, ref, bound, what):
-    """-> worst |got - ref| / bound (0 / 0 counts as 0); fails above 1 or on a non-finite value"""
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
-    err = (got.double() - ref).abs()
-    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.expand_as(err).clamp(min=1e-300))
-    worst = float(ratio.max())
-    print(f"{what}: error / bound = {worst:.4f}")
-    assert worst <= 1.0, f"{what}: error is {worst:.3f} x the bound at {tuple(int(i) for i in (ratio == ratio.max()).nonzero()[0])}"
-    return worst
+        write_parity(out, _PARITY,
+                     "# worst error / bound per kernel, quantity and regime of tests/test_gpu_stem_pool_matrix.py (bounds derived in\n"
+                     "# tests/stem_pool_reference.py); 0.0000 on an exact run: every element equal to the float64 restatement\n")
 
 
 # ---- the restated launch arithmetic against the ABI's own queries ----------------------------------------------------------
@@ -139,8 +78,8 @@ def run_stem(lib, c, x, w, with_xn=True, with_stats=True):
     nst = lib.query("segk_bn_stats_floats", rows, 64)
     assert nst >= rows * 128
     st = nan_buffer(nst, "fp32") if with_stats else None
-    lib.call("segk_stem3x3", ptr(xd), ptr(wd), ptr(z), ptr(xn), ptr(st), c.B, c.H, c.W, c.Cin, 64, 1, _stream())
-    _sync(what)
+    lib.call("segk_stem3x3", ptr(xd), ptr(wd), ptr(z), ptr(xn), ptr(st), c.B, c.H, c.W, c.Cin, 64, 1, stream())
+    sync(what)
     zc = take(z, P * 64, "bf16", what + " z").reshape(c.B, c.H, c.W, 64)
     xc = take(xn, P * 32, "bf16", what + " xn").reshape(c.B, c.H, c.W, 32) if with_xn else None
     rc = take(st, nst, "fp32", what + " statistics rows", written=rows * 128)[:rows * 128].reshape(rows, 64, 2) if with_stats else None
@@ -212,9 +151,9 @@ def run_stem_wgrad(lib, c, x, dz):
     Kc = 9 * c.Cin
     xd, dd = x.cuda(), dz.contiguous().cuda()
     slabs, grad = nan_buffer(S * 2048, "fp32"), nan_buffer(64 * Kc, "fp32")
-    lib.call("segk_stem3x3_wgrad", ptr(xd), ptr(dd), ptr(slabs), c.B, c.H, c.W, c.Cin, 64, 1, _stream())
-    lib.call("segk_wgrad_reduce", ptr(slabs), S, ptr(grad), 64, Kc, 0, 64, 32, 0, 1, _stream())
-    _sync(what)
+    lib.call("segk_stem3x3_wgrad", ptr(xd), ptr(dd), ptr(slabs), c.B, c.H, c.W, c.Cin, 64, 1, stream())
+    lib.call("segk_wgrad_reduce", ptr(slabs), S, ptr(grad), 64, Kc, 0, 64, 32, 0, 1, stream())
+    sync(what)
     return (take(slabs, S * 2048, "fp32", what + " slabs").reshape(S, 64, 32), take(grad, 64 * Kc, "fp32", what + " gradient").reshape(64, Kc))
 
 
@@ -277,13 +216,13 @@ def test_maxpool_forward_and_backward_are_exact(lib, case):
     n_in, n_out = x.numel(), dy.numel()
     xd, dyd = x.cuda(), dy.cuda()
     y = nan_buffer(n_out, c.dtype)
-    lib.call("segk_maxpool2x2_fwd", ptr(xd), ptr(y), c.B, c.H, c.W, c.Cp, sdt, _stream())
+    lib.call("segk_maxpool2x2_fwd", ptr(xd), ptr(y), c.B, c.H, c.W, c.Cp, sdt, stream())
     dx = nan_buffer(n_in, c.dtype)
-    lib.call("segk_maxpool2x2_bwd", ptr(xd), ptr(dyd), ptr(dx), c.B, c.H, c.W, c.Cp, 0, sdt, _stream())
+    lib.call("segk_maxpool2x2_bwd", ptr(xd), ptr(dyd), ptr(dx), c.B, c.H, c.W, c.Cp, 0, sdt, stream())
     dxa = nan_buffer(n_in, c.dtype)
     dxa[:n_in] = dx0.reshape(-1).view(BITS_DT[c.dtype]).cuda()
-    lib.call("segk_maxpool2x2_bwd", ptr(xd), ptr(dyd), ptr(dxa), c.B, c.H, c.W, c.Cp, 1, sdt, _stream())
-    _sync(f"maxpool {cid}")
+    lib.call("segk_maxpool2x2_bwd", ptr(xd), ptr(dyd), ptr(dxa), c.B, c.H, c.W, c.Cp, 1, sdt, stream())
+    sync(f"maxpool {cid}")
     assert_equal(take(y, n_out, c.dtype, f"maxpool_fwd {cid}").reshape(dy.shape), R.maxpool_fwd_reference(x), f"maxpool_fwd {cid}")
     record(f"maxpool2x2_fwd {_trips(c, 'fwd')}", 0.0, cid)
     assert_equal(take(dx, n_in, c.dtype, f"maxpool_bwd {cid}").reshape(x.shape), R.maxpool_bwd_reference(x, dy), f"maxpool_bwd {cid}")
@@ -300,8 +239,8 @@ def test_bn_relu_apply_pool_is_exact(lib, case):
     zd, scd, shd = z.cuda(), scale.cuda(), shift.cuda()
     n_in, n_out = z.numel(), c.B * (c.H // 2) * (c.W // 2) * c.Cp
     y, pooled = nan_buffer(n_in, c.dtype), nan_buffer(n_out, c.dtype)
-    lib.call("segk_bn_relu_apply_pool", ptr(zd), ptr(y), ptr(pooled), ptr(scd), ptr(shd), c.B, c.H, c.W, c.Cp, sdt, _stream())
-    _sync(f"bn_relu_apply_pool {cid}")
+    lib.call("segk_bn_relu_apply_pool", ptr(zd), ptr(y), ptr(pooled), ptr(scd), ptr(shd), c.B, c.H, c.W, c.Cp, sdt, stream())
+    sync(f"bn_relu_apply_pool {cid}")
     want_y, want_p = R.apply_pool_reference(z, scale, shift, TORCH_DT[c.dtype])
     assert bool((R.windows(want_y.float()).amax(3) == 0).any())          # windows whose four y are all zero
     assert_equal(take(y, n_in, c.dtype, f"bn_relu_apply_pool {cid} y").reshape(z.shape), want_y, f"bn_relu_apply_pool {cid} y")
@@ -323,8 +262,8 @@ def test_maxpool_bwd_bnstat_against_float64(lib, stat):
         dx[:n_in] = dx0.reshape(-1).view(BITS_DT[c.dtype]).cuda()
     part = nan_buffer(nb * c.Cp * 2, "fp32")
     lib.call("segk_maxpool2x2_bwd_bnstat", ptr(yd), ptr(dyd), ptr(dx), c.B, c.H, c.W, c.Cp, s.accumulate, *(ptr(v) for v in vec),
-             ptr(part), ptr(zd), sdt, _stream())
-    _sync(f"maxpool_bwd_bnstat {cid}")
+             ptr(part), ptr(zd), sdt, stream())
+    sync(f"maxpool_bwd_bnstat {cid}")
     pre = R.maxpool_bwd_presum(y, dy, dx0 if s.accumulate else None)
     want_dx = pre.to(TORCH_DT[c.dtype])
     got = dx.cpu()
@@ -369,8 +308,8 @@ def run_finalize(lib, rows, C, Cr, count, cb, gamma, beta, rm0, rv0, training, w
         run[name][:Cr] = v[:Cr].view(torch.int32).cuda()
     out = {name: nan_buffer(C, "fp32") for name in (("scale", "shift", "mean", "rstd") if with_mean else ("scale", "shift"))}
     lib.call("segk_bn_finalize", ptr(part), MT, C, Cr, float(count), ptr(cbd), ptr(gd), ptr(bd), ptr(run["rmean"]), ptr(run["rvar"]),
-             0.1, 1e-5, training, ptr(out["scale"]), ptr(out["shift"]), ptr(out.get("mean")), ptr(out.get("rstd")), _stream())
-    _sync(what)
+             0.1, 1e-5, training, ptr(out["scale"]), ptr(out["shift"]), ptr(out.get("mean")), ptr(out.get("rstd")), stream())
+    sync(what)
     res = {name: take(buf, C, "fp32", f"{what} {name}") for name, buf in out.items()}
     for name, buf in run.items():
         bits = buf.cpu()
