@@ -10,9 +10,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 318          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 319          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
+MAX_TEMPS = 32           # SEGK_MAX_TEMPS
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
 
 _vp, _fp, _i, _l, _f, _d = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
@@ -80,6 +81,8 @@ SIGNATURES = {
     "segk_tile_gather_u8": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_tile_gather": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_predict_tiles": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _vp]),
+    "segk_calib_hist": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "segk_calib_temps": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _fp, _i, _vp, _vp, _vp, _vp, _vp]),
     "segk_cc_label": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_cc_clean": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_mask_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

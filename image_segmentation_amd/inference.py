@@ -248,10 +248,17 @@ class Segmenter:
               filled with consecutive images' tiles (at least one image), an image with more tiles runs alone in
               ceil(n / batch_size) forwards.  One model, no tta=; a ClipUNet needs size == its input size, a U-Net a multiple
               of 16, the autoencoders of 8.  outputs=, return_scores=, clean=, heatmaps / points and labels work as above;
-              Prediction.confidence is always set; meta holds original_size, tile_size, overlap and tiles=(ny, nx)."""
+              Prediction.confidence is always set; meta holds original_size, tile_size, overlap and tiles=(ny, nx).
+
+    Calibrated confidence (with None every output and the code path are as above):
+    temperature=  a positive float (calibration.fit_temperature finds it), or one per model of an ensemble: each model's
+              logits are multiplied by the float32 1/T before the prediction kernels run.  One view: the mask is unchanged
+              up to rounding and the confidence is the calibrated one; merged views under "prob": the merge itself changes.
+              Refused for outputs="probs"."""
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
-                 sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False, tiles=None):
+                 sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False, tiles=None,
+                 temperature=None):
         models = list(model) if isinstance(model, (list, tuple)) else [model]
         if not models:
             raise ValueError("an ensemble needs at least one model")
@@ -277,11 +284,13 @@ class Segmenter:
         if tiles is not None:
             self._merged = False
             self._init_tiles(tiles, tta, model_weights, outputs)
+            self._init_temperature(temperature, self.outputs)
             return
         self._merged = tta is not None or len(models) > 1 or self.return_scores
         if not self._merged:
             if model_weights is not None or outputs is not None:
                 raise ValueError("model_weights= and outputs= belong to merged views: pass tta= or several models")
+            self._init_temperature(temperature, ["probs" if _is_prompt_model(model) else "logits"])
             return
         if isinstance(tta, dict):
             tta = _tta.TTA(**tta)
@@ -309,6 +318,20 @@ class Segmenter:
             if fixed is not None and any(T != fixed for _, T, _, _ in self._views):
                 raise ValueError(f"model {k} is a ClipUNet whose ViT takes {fixed} x {fixed} inputs only: "
                                  f"target_size / TTA sizes must be {fixed}")
+        self._init_temperature(temperature, outputs)
+
+    def _init_temperature(self, temperature, outputs):
+        """self._inv_T: None, or per model the float32 1/T its logits are multiplied by"""
+        self._inv_T = None
+        if temperature is None:
+            return
+        if "probs" in outputs:
+            raise ValueError('temperature= scales logits: it is refused for outputs="probs" (a PromptModel returns probabilities)')
+        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * len(self.models)
+        if len(temps) != len(self.models):
+            raise ValueError(f"temperature: {len(temps)} entries for {len(self.models)} models")
+        temps = _tta._positive(temps, "temperature")
+        self._inv_T = [float(np.float32(1.0 / t)) for t in temps]           # 1/T in float64, rounded once
 
     def _init_tiles(self, tiles, tta, model_weights, outputs):
         if isinstance(tiles, dict):
@@ -410,6 +433,8 @@ class Segmenter:
             raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
         if y.dtype != torch.float32 or not y.is_contiguous():
             y = y.float().contiguous()
+        if self._inv_T is not None:
+            y = y * self._inv_T[0]
         C = int(y.shape[1])
         pal = self._palette_on(dev)
         _check_classes(C, pal)
@@ -479,6 +504,8 @@ class Segmenter:
                 raise ValueError(f"model {m} returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
             if y.dtype != torch.float32 or not y.is_contiguous():
                 y = y.float().contiguous()
+            if self._inv_T is not None:
+                y = y * self._inv_T[m]
             if C is not None and int(y.shape[1]) != C:
                 raise ValueError(f"model {m} returned {int(y.shape[1])} classes, the views before it {C}")
             C = int(y.shape[1])
@@ -582,6 +609,8 @@ class Segmenter:
             raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
         if y.dtype != torch.float32 or not y.is_contiguous():
             y = y.float().contiguous()
+        if self._inv_T is not None:
+            y = y * self._inv_T[0]
         return y
 
     def _tile_group(self, dev, images, heatmaps, labels, plans):

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 318
-#define SEGK_ENTRY_COUNT 94
+#define SEGK_ABI_VERSION 319
+#define SEGK_ENTRY_COUNT 96
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -340,6 +340,34 @@ int segk_tile_gather(const float* img_chw, float* out, int C, int H, int W, int 
 int segk_predict_tiles(const float* Y, int C, int kind, int merge, int window, int H, int W, int T, int overlap, uint8_t* mask,
                        uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels, uint64_t* M,
                        uint8_t* conf, float* scores, segk_stream_t s);
+
+/* ---- confidence calibration: reliability histograms and the temperature sweep (the reference holds no code
+ * for it).  Integer sums only, accumulated with += into caller-zeroed uint64 buffers (a data set is a sequence of calls into
+ * one set of buffers): order-independent and bit-stable, no float atomics, no finalize pass.
+ * A pixel is VALID when 0 <= label < C and label != ignore_index (ignore_index -1: none).
+ *
+ * segk_calib_hist: conf uint8 [H,W] (Prediction.confidence), mask uint8 [H,W], labels int64 [H,W] ->
+ * hist uint64 [SEGK_MAX_CLASSES][256][2]: every valid pixel adds 1 to hist[m][q][0], and 1 to hist[m][q][1] when m == l.  The
+ * maps are device data, so a mask value m >= C cannot be refused: it is counted under class C - 1 (and, being no label, is
+ * never correct).  H W < 2^31 - 4; labels and hist 8-byte aligned. */
+#define SEGK_MAX_TEMPS 32
+#define SEGK_CALIB_NLL_MAX 262144.0f /* 2^18 nat: a per-pixel NLL at or above it (NaN and inf included) counts as non-finite */
+int segk_calib_hist(const uint8_t* conf, const uint8_t* mask, const int64_t* labels, int H, int W, int C, int ignore_index,
+                    uint64_t* hist, segk_stream_t s);
+/* segk_calib_temps: one view's slot [C,T,T] fp32 of LOGITS, the geometry arguments and modes of segk_predict_mask, labels
+ * int64 [oh,ow] and a DEVICE table inv_T_dev of K floats 1/T_j (1 <= K <= SEGK_MAX_TEMPS; the host never reads it).  Per valid
+ * pixel: z = the slot sampled with the arithmetic of segk_predict_mask, best = its argmax (first maximum, NaN maximal; the
+ * same for every j); per j: s = z inv_T[j], mx = max s, e_k = expf(s_k - mx), S = sum_k e_k in class order, p = e / S, then
+ * p = p / sum_k p (a one-view SEGK_MERGE_PROB merge of weight 1: at inv_T = 1.0f the confidence is segk_predict_merge's bit
+ * for bit), q = (uint8)(255 p_best + 0.5) clamped, NaN -> 0, nll = logf(S) - (s_l - mx).
+ *   hist uint64 [K][256][2]: hist[j][q][0] += 1, hist[j][q][1] += (best == l)
+ *   nll_fx[j] += (uint64)((double)max(nll, 0) 65536 + 0.5) when nll < SEGK_CALIB_NLL_MAX, else nonfinite[j] += 1
+ *   valid[0] += 1 once per valid pixel
+ * The 2^-16 nat fixed point errs by at most 2^-17 nat per pixel; 2^30 pixels at the cap stay inside uint64.  T T < 2^30,
+ * oh ow < 2^31 - 4; labels and the outputs 8-byte aligned.  Every scalar and pointer is validated (-2 before any launch). */
+int segk_calib_temps(const float* slot, int C, int T, int pad_top, int pad_left, int nh, int nw, int oh, int ow, int mode,
+                     const int64_t* labels, int ignore_index, const float* inv_T_dev, int K, uint64_t* hist, uint64_t* nll_fx,
+                     uint64_t* nonfinite, uint64_t* valid, segk_stream_t s);
 
 /* ---- mask clean-up: connected components, boxes, blob removal (the reference has no such code: this
  * replaces a mask.cpu() + scipy.ndimage.label post-process).  Integer arithmetic only: results are unique and bit-stable.

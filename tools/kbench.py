@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -780,7 +780,84 @@ def tiles():
     print(f"written to {path}")
 
 
+def calib():
+    """Confidence calibration through the C ABI (csrc/calib.hip) at 1200 x 1600, C = 4, one 224 x 224 slot:
+    segk_calib_temps at K = 1 and K = 17 (the default grid) and segk_calib_hist on the mask and confidence of the same slot,
+    each on a PEAKED field (every pixel favours one class by 10: almost everything lands in q = 255) and a FLAT one (white
+    noise of scale 1).  The yardstick is segk_predict_merge at V = 1 ("prob", mask and confidence only) on the same slot,
+    in this process, alternating, seven rounds each: median and min..max.  Also written to profiles/kbench_calib.json (or
+    the file given with --out) and the lines to the .txt beside it."""
+    import json
+    import numpy as np
+    from image_segmentation_amd import tta as T_, calibration
+    from image_segmentation_amd.utils import _geometry
+    T, C, oh, ow = 224, 4, 1200, 1600
+    st = ops._stream()
+    nh, nw, pt, pl, _ = _geometry(oh, ow, T)
+    mask, conf = (torch.empty((oh, ow), dtype=torch.uint8, device="cuda") for _ in range(2))
+    g = torch.Generator(device="cuda").manual_seed(0)
+    lab = torch.randint(0, C, (oh, ow), device="cuda", generator=g)
+    inv = torch.from_numpy(calibration.inverse_temperatures(calibration.default_temperatures())).cuda()
+    acc = torch.zeros(17 * 512 + 2 * 17 + 1, dtype=torch.int64, device="cuda")
+    hist, nll, nonf, valid = acc[:17 * 512], acc[17 * 512:17 * 513], acc[17 * 513:17 * 514], acc[17 * 514:]
+    hist8 = torch.zeros((8, 256, 2), dtype=torch.int64, device="cuda")
+
+    def rounds(fns, iters=50):
+        ts = [[] for _ in fns]
+        for _ in range(7):
+            for t, fn in zip(ts, fns):
+                t.append(timeit(fn, iters))
+        return [{"median": sorted(t)[3], "min": min(t), "max": max(t)} for t in ts]
+
+    rows, lines = [], []
+    for name in ("peaked", "flat"):
+        slot = torch.randn((C, T, T), device="cuda", generator=g)
+        if name == "peaked":
+            slot = 0.1 * slot + 10.0 * torch.nn.functional.one_hot(torch.randint(0, C, (T // 8, T // 8), device="cuda", generator=g), C) \
+                .permute(2, 0, 1).repeat_interleave(8, 1).repeat_interleave(8, 2).float()
+            slot = slot.contiguous()
+        table = T_.view_table([(slot.data_ptr(), T, pt, pl, nh, nw, 0, 0, 1.0)])
+        dev = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).cuda()
+
+        def merge():
+            _lib.call("segk_predict_merge", dev.data_ptr(), 1, C, 0, 0, oh, ow, mask.data_ptr(), None, None, None, None, None,
+                      conf.data_ptr(), None, st)
+
+        def temps(K, first):
+            def f():
+                _lib.call("segk_calib_temps", slot.data_ptr(), C, T, pt, pl, nh, nw, oh, ow, 0, lab.data_ptr(), -1,
+                          inv.data_ptr() + 4 * first, K, hist.data_ptr(), nll.data_ptr(), nonf.data_ptr(), valid.data_ptr(), st)
+            return f
+
+        def hist_entry():
+            _lib.call("segk_calib_hist", conf.data_ptr(), mask.data_ptr(), lab.data_ptr(), oh, ow, C, -1, hist8.data_ptr(), st)
+        merge()
+        acc.zero_()
+        temps(1, 8)()
+        torch.cuda.synchronize()
+        top = int(hist[255 * 2]) / (oh * ow)
+        res = dict(zip(["segk_predict_merge V=1", "segk_calib_temps K=1", "segk_calib_temps K=17", "segk_calib_hist"],
+                       rounds([merge, temps(1, 8), temps(17, 0), hist_entry])))
+        rows.append({"field": name, "size": [oh, ow], "C": C, "T": T, "share_in_top_bin_at_T1": top, "us": res})
+        lines.append(f"calib {oh}x{ow} C={C} T={T} {name} field ({top:.3f} of the pixels in q = 255 at 1/T = 1)")
+        lines += [f"  {k:24s} {v['median']:9.1f} us [{v['min']:.1f}..{v['max']:.1f}]" for k, v in res.items()]
+    clk = ops.clock_probe()
+    lines.append(f"  clock probe: median {clk['median_ghz']} GHz; build {_lib.build_id()}")
+    print("\n".join(lines))
+    path = os.path.join(ROOT, "profiles", "kbench_calib.json")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        json.dump({"rows": rows, "clock_probe_ghz": clk["median_ghz"], "build_id": _lib.build_id()}, f, indent=1)
+    with open(os.path.splitext(path)[0] + ".txt", "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "calib":
+        calib()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tiles":
         tiles()
         sys.exit(0)

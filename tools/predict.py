@@ -16,7 +16,9 @@ ViT takes 224 x 224 inputs only.
 --tile N segments every image at its own resolution in N x N tiles that overlap by --tile-overlap M pixels (default N / 4)
 and blends the tiles' outputs on the device (--tile-window triangle|flat weighs a tile's pixels, --tile-pad
 reflect|zero fills a tile beyond an image smaller than itself, --merge as above); --batch-size then counts tiles per forward.
-It does not combine with --tta, --sizes or several --checkpoint; --confidence works with it."""
+It does not combine with --tta, --sizes or several --checkpoint; --confidence works with it.
+--temperature T divides every model's logits by T before the prediction kernels run (tools/calibrate.py fits
+it): the confidence maps become the calibrated ones.  Not for --model prompt, whose outputs are probabilities."""
 import argparse
 import os
 import sys
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--tile-overlap", type=int, default=None, metavar="M", help="pixels two neighbouring tiles share (default N / 4)")
     ap.add_argument("--tile-window", choices=["flat", "triangle"], default="triangle", help="blend weight of a tile's pixels")
     ap.add_argument("--tile-pad", choices=["reflect", "zero"], default="reflect", help="a tile's content beyond a smaller image")
+    ap.add_argument("--temperature", type=float, default=None, metavar="T", help="divide the logits by T (calibrated confidence)")
     ap.add_argument("--classes", type=int, default=4)
     ap.add_argument("--size", type=int, default=224, help="side of the square network input")
     ap.add_argument("--interpolation", choices=["bilinear", "nearest"], default="bilinear")
@@ -110,7 +113,8 @@ def main():
     palette = seg.COLOR_MAP if args.classes <= len(seg.COLOR_MAP) else None
     try:
         segmenter = seg.Segmenter(models if tta is not None else models[0], target_size=args.size, interpolation=args.interpolation,
-                                  palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta, tiles=tiles)
+                                  palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta, tiles=tiles,
+                                  temperature=args.temperature)
     except ValueError as e:
         ap.error(str(e))
     if args.confidence:
