@@ -1,12 +1,15 @@
-"""What the GPU matrices (test_gpu_stem_pool_matrix.py, test_gpu_vit_matrix.py) share: NaN-patterned output buffers with a
-guard behind them, the element-wise comparisons, the sticky-error exit and the worst error / bound record."""
+"""What the GPU matrices (test_gpu_stem_pool_matrix.py, test_gpu_vit_matrix.py, test_gpu_resize_matrix.py) share: NaN-patterned
+output buffers with a guard behind them (byte- and int64-patterned ones for integer outputs), the element-wise comparisons, the
+sticky-error exit and the worst error / bound record."""
 import pytest
 import torch
 
-TORCH_DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
+TORCH_DT = {"bf16": torch.bfloat16, "fp32": torch.float32, "u8": torch.uint8, "i64": torch.int64}
 SEGK_DT = {"fp32": 0, "bf16": 1}
-NAN_BITS = {"bf16": 0x7FDE, "fp32": 0x7FDEAD00}      # quiet-NaN patterns: what a kernel must overwrite, and leave in the guard
-BITS_DT = {"bf16": torch.int16, "fp32": torch.int32}
+# quiet-NaN patterns: what a kernel must overwrite, and leave in the guard; integer outputs ("u8", "i64") take a pattern no
+# valid result of their tests holds
+NAN_BITS = {"bf16": 0x7FDE, "fp32": 0x7FDEAD00, "u8": 0xA5, "i64": 0x7FDEAD007FDEAD00}
+BITS_DT = {"bf16": torch.int16, "fp32": torch.int32, "u8": torch.uint8, "i64": torch.int64}
 GUARD = 4096                                         # elements behind every output buffer
 
 
@@ -70,6 +73,16 @@ def assert_equal(got, want, what):
     if torch.equal(got, want):
         return
     idx = ((got != want) | torch.isnan(got)).nonzero()
+    lines = [f"  [{', '.join(map(str, i))}] = {got[tuple(i)].item()!r}, want {want[tuple(i)].item()!r}" for i in idx[:10].tolist()]
+    raise AssertionError(f"{what}: {len(idx)} of {got.numel()} elements differ\n" + "\n".join(lines))
+
+
+def assert_identical(got, want, what):
+    """integer tensors: every element the same integer (no pass through a float)"""
+    assert got.dtype == want.dtype and not got.dtype.is_floating_point and got.shape == want.shape, f"{what}: {got.dtype} {tuple(got.shape)}"
+    if torch.equal(got, want):
+        return
+    idx = (got != want).nonzero()
     lines = [f"  [{', '.join(map(str, i))}] = {got[tuple(i)].item()!r}, want {want[tuple(i)].item()!r}" for i in idx[:10].tolist()]
     raise AssertionError(f"{what}: {len(idx)} of {got.numel()} elements differ\n" + "\n".join(lines))
 
