@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from . import inference as I
 from . import utils as U
 
 MAX_TEMPS = _lib.MAX_TEMPS
@@ -121,13 +122,6 @@ def _ignore(ignore_index, C):
     return int(ignore_index)
 
 
-def _label_on(lab, size, dev, k):
-    lab = torch.from_numpy(np.ascontiguousarray(lab)) if isinstance(lab, np.ndarray) else lab
-    if torch.is_floating_point(lab) or tuple(lab.shape) not in (tuple(size), (1,) + tuple(size)):
-        raise ValueError(f"labels {k}: expected an integer map of {tuple(size)}, got {lab.dtype} {tuple(lab.shape)}")
-    return lab.to(dev, non_blocking=True).long().contiguous()
-
-
 def reliability(predictions, labels, num_classes, ignore_index=None, out=None):
     """Reliability histogram of Segmenter predictions against label maps at the images' own sizes: one segk_calib_hist launch
     per image into one device buffer, no host sync.  Uses Prediction.raw_mask where clean= was used (the confidence belongs to
@@ -160,7 +154,7 @@ def reliability(predictions, labels, num_classes, ignore_index=None, out=None):
             if conf.dtype != torch.uint8 or mask.dtype != torch.uint8 or conf.ndim != 2 or conf.shape != mask.shape:
                 raise ValueError(f"prediction {k}: confidence and mask are uint8 [H,W] maps of one size")
             H, W = (int(a) for a in conf.shape)
-            lab = _label_on(labels[k], (H, W), dev, k)
+            lab = I._label_on(labels[k], (H, W), dev, k)
             _lib.call("segk_calib_hist", conf.data_ptr(), mask.data_ptr(), lab.data_ptr(), H, W, C, ign, out.hist.data_ptr(),
                       ops._stream())
     return out
@@ -256,7 +250,6 @@ def fit_temperature(model, images, labels, target_size=224, interpolation="bilin
     pixel counts when 0 <= label < C and label != ignore_index).  Slots are filled as Segmenter fills them, one forward runs
     per chunk of batch_size images and one segk_calib_temps launch per image adds into one set of device accumulators; the
     host waits once, at the end.  Returns a TemperatureFit."""
-    from . import inference as I
     if isinstance(model, (list, tuple)):
         raise ValueError("fit_temperature takes one model: fit each model of an ensemble on its own and pass Segmenter one "
                          "temperature per model")
@@ -286,38 +279,25 @@ def fit_temperature(model, images, labels, target_size=224, interpolation="bilin
     ops._require_cuda(param, "fit_temperature")
     dev = param.device
     mode = 1 if interpolation == U.NEAREST else 0
-    modes = [(m, m.training) for m in model.modules()]
-    try:
-        model.eval()
-        with torch.no_grad(), torch.cuda.device(dev):
-            inv = torch.from_numpy(inverse_temperatures(temps)).to(dev)
-            acc = torch.zeros(K * 512 + 2 * K + 1, dtype=torch.int64, device=dev)      # hist, nll_fx, nonfinite, valid
-            hist, nll_fx, nonf, valid = acc[:K * 512], acc[K * 512:K * 513], acc[K * 513:K * 514], acc[K * 514:]
-            for i in range(0, len(images), bs):
-                chunk = [im.to(dev, non_blocking=True) for im in images[i:i + bs]]
-                X = torch.empty((len(chunk), I._channels(chunk[0]), T, T), dtype=torch.float32, device=dev)
-                metas = [I._into_slot(im, X[k], T, interpolation, antialias, "image") for k, im in enumerate(chunk)]
-                y = model(X)
-                ops._require_cuda(y, "fit_temperature (model output)")
-                y = y.detach()
-                if y.ndim != 4 or y.shape[0] != len(chunk) or y.shape[2] != T or y.shape[3] != T:
-                    raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
-                if y.dtype != torch.float32 or not y.is_contiguous():
-                    y = y.float().contiguous()
-                C = int(y.shape[1])
-                if C > _lib.MAX_CLASSES:
-                    raise ValueError(f"the model has {C} classes, calibration supports at most {_lib.MAX_CLASSES}")
-                ign = _ignore(ignore_index, C)
-                s = ops._stream()
-                for k, meta in enumerate(metas):
-                    pl, pt, _, _ = meta["pad"]
-                    nh, nw = meta["new_size"]
-                    oh, ow = meta["original_size"]
-                    lab = _label_on(labels[i + k], (oh, ow), dev, i + k)
-                    _lib.call("segk_calib_temps", y[k].data_ptr(), C, T, pt, pl, nh, nw, oh, ow, mode, lab.data_ptr(), ign,
-                              inv.data_ptr(), K, hist.data_ptr(), nll_fx.data_ptr(), nonf.data_ptr(), valid.data_ptr(), s)
-            host = acc.cpu().numpy()                      # the one host sync
-    finally:
-        for m, was in modes:
-            m.training = was
+    with I._eval_mode([model]), torch.no_grad(), torch.cuda.device(dev):
+        inv = torch.from_numpy(inverse_temperatures(temps)).to(dev)
+        acc = torch.zeros(K * 512 + 2 * K + 1, dtype=torch.int64, device=dev)      # hist, nll_fx, nonfinite, valid
+        hist, nll_fx, nonf, valid = acc[:K * 512], acc[K * 512:K * 513], acc[K * 513:K * 514], acc[K * 514:]
+        for i in range(0, len(images), bs):
+            chunk = [im.to(dev, non_blocking=True) for im in images[i:i + bs]]
+            X, _, metas = I._slots(dev, chunk, None, T, interpolation, antialias)
+            y = I._forward(model, X, None, ("the model", "fit_temperature"))
+            C = int(y.shape[1])
+            if C > _lib.MAX_CLASSES:
+                raise ValueError(f"the model has {C} classes, calibration supports at most {_lib.MAX_CLASSES}")
+            ign = _ignore(ignore_index, C)
+            s = ops._stream()
+            for k, meta in enumerate(metas):
+                pl, pt, _, _ = meta["pad"]
+                nh, nw = meta["new_size"]
+                oh, ow = meta["original_size"]
+                lab = I._label_on(labels[i + k], (oh, ow), dev, i + k)
+                _lib.call("segk_calib_temps", y[k].data_ptr(), C, T, pt, pl, nh, nw, oh, ow, mode, lab.data_ptr(), ign,
+                          inv.data_ptr(), K, hist.data_ptr(), nll_fx.data_ptr(), nonf.data_ptr(), valid.data_ptr(), s)
+        host = acc.cpu().numpy()                      # the one host sync
     return fit_from_counts(temps, host[:K * 512], host[K * 512:K * 513], host[K * 513:K * 514], host[K * 514])

@@ -19,6 +19,7 @@ confusion counts and a confidence map, again without full-size float images.
 tiles=Tiles(...) is the route for images larger than the training crop: the image is cut at its own
 resolution into overlapping tiles (segk_tile_gather / _u8), the tiles run as network batches, and segk_predict_tiles blends
 the overlapping outputs into the same set of outputs in one pass; nothing is resampled."""
+import contextlib
 import inspect
 from dataclasses import dataclass
 from typing import Optional
@@ -104,46 +105,98 @@ def _as_tensor(a):
     return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
 
 
-def _into_slot(image, slot, T, interpolation, antialias, what, flip=0):
-    """One image or heat-map -> its slot [c,T,T]: uint8 [H,W,Cin] / [H,W] through segk_resize_pad_u8, float [C,H,W]
-    through segk_resize_pad; with flip (bit 0: x, bit 1: y) the slot of the flipped image, through their _flip forms.
-    Returns the metadata."""
+def _source(image, c, what):
+    """One image or heat-map, checked against a batch of c channels -> (src, u8, cin, H, W): the contiguous tensor a kernel
+    reads and whether it is the 8-bit form, uint8 [H,W,cin] (cin of 4: RGBA, the kernels drop A), or the float one, float32
+    [cin,H,W]."""
     if image.dtype == torch.uint8:
         if image.ndim == 2:
             image = image.unsqueeze(-1)
         if image.ndim != 3 or image.shape[2] not in (1, 3, 4):
             raise ValueError(f"{what}: 8-bit inputs are [H,W,C] with 1, 3 or 4 channels (or [H,W]), got {tuple(image.shape)}")
         H, W, cin = image.shape
-        if min(cin, 3) != slot.shape[0]:
-            raise ValueError(f"{what}: {min(cin, 3)} channels where the batch has {slot.shape[0]}")
-        nh, nw, pt, pl, meta = U._geometry(H, W, T)
-        antialias = U.ANTIALIAS if antialias is None else antialias
-        mode = 1 if interpolation == U.NEAREST else (0 if antialias else 2)
+        if min(cin, 3) != c:
+            raise ValueError(f"{what}: {min(cin, 3)} channels where the batch has {c}")
         src = image.contiguous()
         if cin == 4 and src.data_ptr() % 4:
             src = src.clone()
-        if flip:
-            _lib.call("segk_resize_pad_u8_flip", src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, mode, flip,
-                      ops._stream())
-        else:
-            _lib.call("segk_resize_pad_u8", src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, mode, ops._stream())
-        return meta
+        return src, True, cin, H, W
     if not torch.is_floating_point(image) or image.ndim != 3:
         raise ValueError(f"{what}: expected a float [C,H,W] tensor or a uint8 [H,W,C] image, got {image.dtype} {tuple(image.shape)}")
     if image.shape[0] == 4:
         image = image[:3]
-    if image.shape[0] != slot.shape[0]:
-        raise ValueError(f"{what}: {image.shape[0]} channels where the batch has {slot.shape[0]}")
-    if not flip:
-        return U._resize_pad_into(image, slot, T, interpolation, antialias)
-    C, H, W = image.shape
+    cin, H, W = image.shape
+    if cin != c:
+        raise ValueError(f"{what}: {cin} channels where the batch has {c}")
+    return image.float().contiguous(), False, cin, H, W
+
+
+def _into_slot(image, slot, T, interpolation, antialias, what, flip=0):
+    """One image or heat-map -> its slot [c,T,T]: uint8 [H,W,Cin] / [H,W] through segk_resize_pad_u8, float [C,H,W]
+    through segk_resize_pad; with flip (bit 0: x, bit 1: y) the slot of the flipped image, through their _flip forms.
+    Returns the metadata."""
+    src, u8, cin, H, W = _source(image, slot.shape[0], what)
+    if not u8 and not flip:
+        return U._resize_pad_into(src, slot, T, interpolation, antialias)
     nh, nw, pt, pl, meta = U._geometry(H, W, T)
-    antialias = U.ANTIALIAS if antialias is None else antialias
-    mode = 1 if interpolation == U.NEAREST else (0 if antialias else 2)
-    src = image.float().contiguous()
-    _lib.call("segk_resize_pad_flip", src.data_ptr(), slot.data_ptr(), C, H, W, nh, nw, T, pt, pl, mode, 0,
-              flip, ops._stream())
+    args = (src.data_ptr(), slot.data_ptr(), cin, H, W, nh, nw, T, pt, pl, U._resize_mode(interpolation, antialias))
+    if not u8:
+        _lib.call("segk_resize_pad_flip", *args, 0, flip, ops._stream())
+    elif flip:
+        _lib.call("segk_resize_pad_u8_flip", *args, flip, ops._stream())
+    else:
+        _lib.call("segk_resize_pad_u8", *args, ops._stream())
     return meta
+
+
+def _slots(dev, images, heatmaps, T, interpolation, antialias, flip=0):
+    """The network batch of one (size, flip) -> (X [n,c,T,T], Hm [n,1,T,T] or None, the images' metadata)"""
+    n = len(images)
+    X = torch.empty((n, _channels(images[0]), T, T), dtype=torch.float32, device=dev)
+    metas = [_into_slot(im, X[k], T, interpolation, antialias, "image", flip) for k, im in enumerate(images)]
+    if heatmaps is None:
+        return X, None, metas
+    Hm = torch.empty((n, 1, T, T), dtype=torch.float32, device=dev)
+    for k, hm in enumerate(heatmaps):
+        hm = _as_tensor(hm).to(dev, non_blocking=True)      # the merged route has uploaded it already, once for all its views
+        hmeta = _into_slot(hm, Hm[k], T, interpolation, antialias, "heatmap", flip)
+        if hmeta["original_size"] != metas[k]["original_size"]:
+            raise ValueError(f"heatmap {k} is {hmeta['original_size']}, its image {metas[k]['original_size']}")
+    return X, Hm, metas
+
+
+def _forward(model, X, Hm, who, inv_T=None):
+    """model(X) or model(X, Hm) -> its output, checked to be [n,C,T,T] on the device, as contiguous float32 (times inv_T).
+    who = (the model, the caller) as the messages name them: ("model 1", "Segmenter")"""
+    y = model(X) if Hm is None else model(X, Hm)
+    ops._require_cuda(y, f"{who[1]} (model output)")
+    y = y.detach()
+    if y.ndim != 4 or y.shape[0] != X.shape[0] or y.shape[2] != X.shape[2] or y.shape[3] != X.shape[3]:
+        raise ValueError(f"{who[0]} returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        y = y.float().contiguous()
+    return y if inv_T is None else y * inv_T
+
+
+def _label_on(lab, size, dev, k):
+    """Label map k, checked to be an integer [H,W] / [1,H,W] map of `size` -> int64 on the device"""
+    lab = _as_tensor(lab)
+    if torch.is_floating_point(lab) or tuple(lab.shape) not in (tuple(size), (1,) + tuple(size)):
+        raise ValueError(f"labels {k}: expected an integer map of {tuple(size)}, got {lab.dtype} {tuple(lab.shape)}")
+    return lab.to(dev, non_blocking=True).long().contiguous()
+
+
+@contextlib.contextmanager
+def _eval_mode(models):
+    """eval() on every model; each module's own training flag is put back on the way out"""
+    modes = [(m, m.training) for model in models for m in model.modules()]
+    try:
+        for model in models:
+            model.eval()
+        yield
+    finally:
+        for m, was in modes:
+            m.training = was
 
 
 def _channels(image):
@@ -176,29 +229,9 @@ def _image_size(image):
 def _gather_tiles(image, out, T, overlap, pad, tile0, what):
     """Tiles tile0 .. tile0 + len(out) - 1 of one image or heat-map -> out [m,c,T,T]: uint8 [H,W,Cin] / [H,W] through
     segk_tile_gather_u8, float [C,H,W] through segk_tile_gather."""
-    m, c = int(out.shape[0]), int(out.shape[1])
-    if image.dtype == torch.uint8:
-        if image.ndim == 2:
-            image = image.unsqueeze(-1)
-        if image.ndim != 3 or image.shape[2] not in (1, 3, 4):
-            raise ValueError(f"{what}: 8-bit inputs are [H,W,C] with 1, 3 or 4 channels (or [H,W]), got {tuple(image.shape)}")
-        H, W, cin = image.shape
-        if min(cin, 3) != c:
-            raise ValueError(f"{what}: {min(cin, 3)} channels where the batch has {c}")
-        src = image.contiguous()
-        if cin == 4 and src.data_ptr() % 4:
-            src = src.clone()
-        _lib.call("segk_tile_gather_u8", src.data_ptr(), out.data_ptr(), cin, H, W, T, overlap, pad, tile0, m, ops._stream())
-        return
-    if not torch.is_floating_point(image) or image.ndim != 3:
-        raise ValueError(f"{what}: expected a float [C,H,W] tensor or a uint8 [H,W,C] image, got {image.dtype} {tuple(image.shape)}")
-    if image.shape[0] == 4:
-        image = image[:3]
-    if image.shape[0] != c:
-        raise ValueError(f"{what}: {image.shape[0]} channels where the batch has {c}")
-    src = image.float().contiguous()
-    _lib.call("segk_tile_gather", src.data_ptr(), out.data_ptr(), c, int(src.shape[1]), int(src.shape[2]), T, overlap, pad, tile0, m,
-              ops._stream())
+    src, u8, cin, H, W = _source(image, int(out.shape[1]), what)
+    _lib.call("segk_tile_gather_u8" if u8 else "segk_tile_gather", src.data_ptr(), out.data_ptr(), cin, H, W, T, overlap, pad,
+              tile0, int(out.shape[0]), ops._stream())
 
 
 def _tile_size_rule(model):
@@ -213,6 +246,20 @@ def _tile_size_rule(model):
         elif isinstance(m, Encoder):
             rule = max(rule, (8, "the autoencoder's encoder pools three times"))
     return rule
+
+
+def _resolve_outputs(outputs, models, merge):
+    """outputs= -> "logits" or "probs" per model (default: "probs" for a PromptModel); "logit" merging refuses probabilities"""
+    if outputs is None:
+        outputs = ["probs" if _is_prompt_model(m) else "logits" for m in models]
+    elif isinstance(outputs, str):
+        outputs = [outputs] * len(models)
+    outputs = list(outputs)
+    if len(outputs) != len(models) or any(o not in _tta.KINDS for o in outputs):
+        raise ValueError(f"outputs: one of {tuple(_tta.KINDS)} per model, got {outputs!r}")
+    if merge == "logit" and "probs" in outputs:
+        raise ValueError('merge="logit" needs models that return logits; a model here returns probabilities')
+    return outputs
 
 
 class Segmenter:
@@ -302,16 +349,7 @@ class Segmenter:
                 raise ValueError(f"model {k} takes {'(image, heatmap)' if _arity(m) else 'the image alone'}, model 0 does not")
             if None not in (_num_classes(m), self.num_classes) and _num_classes(m) != self.num_classes:
                 raise ValueError(f"model {k} has {_num_classes(m)} classes, model 0 has {self.num_classes}")
-        if outputs is None:
-            outputs = ["probs" if _is_prompt_model(m) else "logits" for m in models]
-        elif isinstance(outputs, str):
-            outputs = [outputs] * len(models)
-        outputs = list(outputs)
-        if len(outputs) != len(models) or any(o not in _tta.KINDS for o in outputs):
-            raise ValueError(f"outputs: one of {tuple(_tta.KINDS)} per model, got {outputs!r}")
-        if self.tta.merge == "logit" and "probs" in outputs:
-            raise ValueError('merge="logit" needs models that return logits; a model here returns probabilities')
-        self.outputs = outputs
+        self.outputs = outputs = _resolve_outputs(outputs, models, self.tta.merge)
         self._views = _tta.view_order(len(models), self.tta, self.target_size, model_weights)
         for k, m in enumerate(models):
             fixed = _fixed_input_size(m)
@@ -341,12 +379,7 @@ class Segmenter:
         if tta is not None or len(self.models) > 1 or model_weights is not None:
             raise ValueError("tiles= does not combine with tta=, several models or model_weights=")
         model = self.model
-        if outputs is None:
-            outputs = "probs" if _is_prompt_model(model) else "logits"
-        if outputs not in _tta.KINDS:
-            raise ValueError(f"outputs: one of {tuple(_tta.KINDS)}, got {outputs!r}")
-        if tiles.merge == "logit" and outputs == "probs":
-            raise ValueError('merge="logit" needs a model that returns logits; this one returns probabilities')
+        outputs = _resolve_outputs(outputs, self.models, tiles.merge)
         size, overlap = tiles.resolve(self.target_size)
         fixed = _fixed_input_size(model)
         if fixed is not None and size != fixed:
@@ -354,7 +387,7 @@ class Segmenter:
         multiple, why = _tile_size_rule(model)
         if size % multiple:
             raise ValueError(f"tile size {size}: {why}, the tile side must be a multiple of {multiple}")
-        self.tiles, self.outputs, self._tile = tiles, [outputs], (size, overlap)
+        self.tiles, self.outputs, self._tile = tiles, outputs, (size, overlap)
 
     def _palette_on(self, dev):
         if self._palette is None:
@@ -391,84 +424,80 @@ class Segmenter:
         dev = params[0].device
         if any(p.device != dev for p in params):
             raise ValueError("the models of an ensemble live on one device")
-        modes = [(m, m.training) for model in self.models for m in model.modules()]
-        out = []
-        try:
-            for model in self.models:
-                model.eval()
-            with torch.no_grad(), torch.cuda.device(dev):
-                if self.tiles is not None:
-                    return self._tiled(dev, images, heatmaps, points, labels)
-                for i in range(0, n, self.batch_size):
-                    j = min(i + self.batch_size, n)
-                    hm = None if heatmaps is None else heatmaps[i:j]
-                    if points is not None:      # click(s) -> heat-map on the device, at the image's own size
-                        hm = [prompts._heatmap_on(torch.from_numpy(p).to(dev, non_blocking=True), *sizes[i + k], self.sigma, dev)
-                              for k, p in enumerate(points[i:j])]
-                    chunk = self._chunk_merged if self._merged else self._chunk
-                    out += chunk(dev, images[i:j], hm, None if labels is None else labels[i:j])
-        finally:
-            for m, was in modes:
-                m.training = was
+        with _eval_mode(self.models), torch.no_grad(), torch.cuda.device(dev):
+            if self.tiles is not None:
+                return self._tiled(dev, images, heatmaps, points, labels)
+            chunk = self._chunk_merged if self._merged else self._chunk
+            out = []
+            for i in range(0, n, self.batch_size):
+                j = min(i + self.batch_size, n)
+                hm = None if heatmaps is None else heatmaps[i:j]
+                if points is not None:
+                    hm = self._click_maps(dev, points[i:j], sizes[i:j])
+                out += chunk(dev, images[i:j], hm, None if labels is None else labels[i:j])
         return out
 
-    def _chunk(self, dev, images, heatmaps, labels):
-        T, n = self.target_size, len(images)
-        images = [im.to(dev, non_blocking=True) for im in images]
-        X = torch.empty((n, _channels(images[0]), T, T), dtype=torch.float32, device=dev)
-        metas = [_into_slot(im, X[k], T, self.interpolation, self.antialias, "image") for k, im in enumerate(images)]
-        if heatmaps is None:
-            y = self.model(X)
-        else:
-            Hm = torch.empty((n, 1, T, T), dtype=torch.float32, device=dev)
-            for k, hm in enumerate(heatmaps):
-                hm = _as_tensor(hm).to(dev, non_blocking=True)
-                hmeta = _into_slot(hm, Hm[k], T, self.interpolation, self.antialias, "heatmap")
-                if hmeta["original_size"] != metas[k]["original_size"]:
-                    raise ValueError(f"heatmap {k} is {hmeta['original_size']}, its image {metas[k]['original_size']}")
-            y = self.model(X, Hm)
-        ops._require_cuda(y, "Segmenter (model output)")
-        y = y.detach()
-        if y.ndim != 4 or y.shape[0] != n or y.shape[2] != T or y.shape[3] != T:
-            raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
-        if y.dtype != torch.float32 or not y.is_contiguous():
-            y = y.float().contiguous()
-        if self._inv_T is not None:
-            y = y * self._inv_T[0]
-        C = int(y.shape[1])
+    def _click_maps(self, dev, points, sizes):
+        """click(s) -> heat-map on the device, at the image's own size"""
+        return [prompts._heatmap_on(torch.from_numpy(p).to(dev, non_blocking=True), H, W, self.sigma, dev)
+                for p, (H, W) in zip(points, sizes)]
+
+    def _scale(self, m):
+        return None if self._inv_T is None else self._inv_T[m]
+
+    def _palette_for(self, dev, C):
         pal = self._palette_on(dev)
         _check_classes(C, pal)
+        return pal
+
+    def _finish(self, dev, C, pal, metas, labels, launch, confident):
+        """The per-image end of every route: allocate the outputs, load the label map, run the route's one kernel and build
+        the Prediction.  launch(k, mask, outs, conf, scores) is that kernel for image k, on pointers: outs = (color, palette,
+        counts, labels, confusion), all null with clean= -- the kernel then writes the argmax (and confidence / scores) alone,
+        and colour, counts and confusion counts come from the cleaned mask afterwards.  confident: the route writes a
+        confidence map (and scores on request); metas[k]["original_size"] is the size of output k."""
+        n = len(metas)
         counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
         M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
-        mode = 1 if self.interpolation == U.NEAREST else 0
-        s = ops._stream()
+        cl, s = self.clean, ops._stream()
         preds = []
         for k, meta in enumerate(metas):
-            pl, pt, _, _ = meta["pad"]
-            nh, nw = meta["new_size"]
             oh, ow = meta["original_size"]
             mask = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+            conf = torch.empty((oh, ow), dtype=torch.uint8, device=dev) if confident else None
+            scores = torch.empty((C, oh, ow), dtype=torch.float32, device=dev) if confident and self.return_scores else None
             color = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev) if pal is not None else None
-            lab = None
-            if labels is not None:
-                lab = _as_tensor(labels[k])
-                if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
-                    raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
-                lab = lab.to(dev, non_blocking=True).long().contiguous()
-            if self.clean is None:
-                _lib.call("segk_predict_mask", y[k].data_ptr(), mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(),
-                          ops._p(lab), ops._p(None if M is None else M[k]), C, T, pt, pl, nh, nw, oh, ow, mode, s)
-                preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
-                continue
-            # the argmax alone, its components and the cleaned mask, then the other outputs from the cleaned mask
-            _lib.call("segk_predict_mask", y[k].data_ptr(), mask.data_ptr(), None, None, None, None, None, C, T, pt, pl, nh, nw,
-                      oh, ow, mode, s)
-            cl = self.clean
-            comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
-            _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
-                      ops._p(None if M is None else M[k]), C, oh, ow, s)
-            preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
+            lab = None if labels is None else _label_on(labels[k], (oh, ow), dev, k)
+            outs = (ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab), ops._p(None if M is None else M[k]))
+            Mk = None if M is None else M[k, :C, :C]
+            if cl is None:
+                launch(k, mask.data_ptr(), outs, ops._p(conf), ops._p(scores))
+                pred = Prediction(mask, color, counts[k, :C], Mk, meta)
+            else:
+                launch(k, mask.data_ptr(), (0,) * 5, ops._p(conf), ops._p(scores))
+                comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
+                _lib.call("segk_mask_finish", comps.mask.data_ptr(), *outs, C, oh, ow, s)
+                pred = Prediction(comps.mask, color, counts[k, :C], Mk, meta, mask, comps)
+            if confident:
+                pred.confidence, pred.scores = conf, scores
+            preds.append(pred)
         return preds
+
+    def _chunk(self, dev, images, heatmaps, labels):
+        T = self.target_size
+        images = [im.to(dev, non_blocking=True) for im in images]
+        X, Hm, metas = _slots(dev, images, heatmaps, T, self.interpolation, self.antialias)
+        y = _forward(self.model, X, Hm, ("the model", "Segmenter"), self._scale(0))
+        C = int(y.shape[1])
+        pal = self._palette_for(dev, C)
+        mode = 1 if self.interpolation == U.NEAREST else 0
+        s = ops._stream()
+
+        def launch(k, mask, outs, conf, scores):
+            pl, pt, _, _ = metas[k]["pad"]
+            _lib.call("segk_predict_mask", y[k].data_ptr(), mask, *outs, C, T, pt, pl, *metas[k]["new_size"],
+                      *metas[k]["original_size"], mode, s)
+        return self._finish(dev, C, pal, metas, labels, launch, False)
 
     def _chunk_merged(self, dev, images, heatmaps, labels):
         """The merged-views form of _chunk: one forward per view over the whole chunk, one table upload for all its images,
@@ -480,38 +509,18 @@ class Segmenter:
         # the network batches, one per (size, flip), shared by the models
         batches, metas = {}, {}
         for _, T, f, _ in self._views:
-            if (T, f) in batches:
-                continue
-            flip = _tta.FLIPS[f]
-            X = torch.empty((n, _channels(images[0]), T, T), dtype=torch.float32, device=dev)
-            ms = [_into_slot(im, X[k], T, self.interpolation, self.antialias, "image", flip) for k, im in enumerate(images)]
-            Hm = None
-            if heatmaps is not None:
-                Hm = torch.empty((n, 1, T, T), dtype=torch.float32, device=dev)
-                for k, hm in enumerate(heatmaps):
-                    hmeta = _into_slot(hm, Hm[k], T, self.interpolation, self.antialias, "heatmap", flip)
-                    if hmeta["original_size"] != ms[k]["original_size"]:
-                        raise ValueError(f"heatmap {k} is {hmeta['original_size']}, its image {ms[k]['original_size']}")
-            batches[(T, f)], metas[T] = (X, Hm), ms
+            if (T, f) not in batches:
+                X, Hm, metas[T] = _slots(dev, images, heatmaps, T, self.interpolation, self.antialias, _tta.FLIPS[f])
+                batches[(T, f)] = (X, Hm)
         # one forward per view, in view order
         ys, C = [], None
         for m, T, f, _ in self._views:
-            X, Hm = batches[(T, f)]
-            y = self.models[m](X) if Hm is None else self.models[m](X, Hm)
-            ops._require_cuda(y, "Segmenter (model output)")
-            y = y.detach()
-            if y.ndim != 4 or y.shape[0] != n or y.shape[2] != T or y.shape[3] != T:
-                raise ValueError(f"model {m} returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
-            if y.dtype != torch.float32 or not y.is_contiguous():
-                y = y.float().contiguous()
-            if self._inv_T is not None:
-                y = y * self._inv_T[m]
+            y = _forward(self.models[m], *batches[(T, f)], (f"model {m}", "Segmenter"), self._scale(m))
             if C is not None and int(y.shape[1]) != C:
                 raise ValueError(f"model {m} returned {int(y.shape[1])} classes, the views before it {C}")
             C = int(y.shape[1])
             ys.append(y)
-        pal = self._palette_on(dev)
-        _check_classes(C, pal)
+        pal = self._palette_for(dev, C)
         V = len(self._views)
         table = np.zeros((n, V), dtype=_tta.VIEW_DESC)
         for k in range(n):
@@ -522,44 +531,17 @@ class Segmenter:
                 rows.append((y[k].data_ptr(), T, pt, pl, nh, nw, f, self.outputs[m], w))
             table[k] = _tta.view_table(rows)
         table_dev, (p_table,) = _upload([table], dev)
-        counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
-        M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
         merge = _tta.MERGES[self.tta.merge]
         mode = 1 if self.interpolation == U.NEAREST else 0
         s = ops._stream()
-        preds = []
-        for k, meta in enumerate(metas[self._views[0][1]]):
-            oh, ow = meta["original_size"]
-            mask = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
-            conf = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
-            scores = torch.empty((C, oh, ow), dtype=torch.float32, device=dev) if self.return_scores else None
-            color = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev) if pal is not None else None
-            lab = None
-            if labels is not None:
-                lab = _as_tensor(labels[k])
-                if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
-                    raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
-                lab = lab.to(dev, non_blocking=True).long().contiguous()
-            views = p_table + k * V * _tta.VIEW_DESC.itemsize
-            Mk = None if M is None else M[k]
-            if self.clean is None:
-                _lib.call("segk_predict_merge", views, V, C, merge, mode, oh, ow, mask.data_ptr(), ops._p(color), ops._p(pal),
-                          counts[k].data_ptr(), ops._p(lab), ops._p(Mk), conf.data_ptr(), ops._p(scores), s)
-                preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
-                preds[-1].confidence, preds[-1].scores = conf, scores
-                continue
-            # the merged argmax alone, its components and the cleaned mask, then the other outputs from the cleaned mask
-            _lib.call("segk_predict_merge", views, V, C, merge, mode, oh, ow, mask.data_ptr(), None, None, None, None, None,
-                      conf.data_ptr(), ops._p(scores), s)
-            cl = self.clean
-            comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
-            _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
-                      ops._p(Mk), C, oh, ow, s)
-            preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
-            preds[-1].confidence, preds[-1].scores = conf, scores
+        first = metas[self._views[0][1]]
+
+        def launch(k, mask, outs, conf, scores):
+            _lib.call("segk_predict_merge", p_table + k * V * _tta.VIEW_DESC.itemsize, V, C, merge, mode,
+                      *first[k]["original_size"], mask, *outs, conf, scores, s)
         # the slots and the table (table_dev) are read by launches still in flight: the caching allocator keeps them valid
         # in stream order, as it does for the batch of the single-view path
-        return preds
+        return self._finish(dev, C, pal, first, labels, launch, True)
 
     def _tiled(self, dev, images, heatmaps, points, labels):
         """The tiled route: forwards of at most batch_size tiles, filled across consecutive images (at least one image); an
@@ -581,9 +563,8 @@ class Segmenter:
                 total += plans[j][2] * plans[j][3]
                 j += 1
             hm = None if heatmaps is None else [_as_tensor(h).to(dev, non_blocking=True) for h in heatmaps[i:j]]
-            if points is not None:          # click(s) -> heat-map on the device, at the image's own size
-                hm = [prompts._heatmap_on(torch.from_numpy(p).to(dev, non_blocking=True), *plans[i + k][:2], self.sigma, dev)
-                      for k, p in enumerate(points[i:j])]
+            if points is not None:
+                hm = self._click_maps(dev, points[i:j], [p[:2] for p in plans[i:j]])
             out += self._tile_group(dev, [im.to(dev, non_blocking=True) for im in images[i:j]], hm,
                                     None if labels is None else labels[i:j], plans[i:j])
             i = j
@@ -602,16 +583,7 @@ class Segmenter:
             if hm is not None:
                 _gather_tiles(hm, Hm[off:off + m], T, overlap, pad, tile0, "heatmap")
             off += m
-        y = self.model(X) if Hm is None else self.model(X, Hm)
-        ops._require_cuda(y, "Segmenter (model output)")
-        y = y.detach()
-        if y.ndim != 4 or y.shape[0] != total or y.shape[2] != T or y.shape[3] != T:
-            raise ValueError(f"the model returned {tuple(y.shape)} for a batch {tuple(X.shape)}")
-        if y.dtype != torch.float32 or not y.is_contiguous():
-            y = y.float().contiguous()
-        if self._inv_T is not None:
-            y = y * self._inv_T[0]
-        return y
+        return _forward(self.model, X, Hm, ("the model", "Segmenter"), self._scale(0))
 
     def _tile_group(self, dev, images, heatmaps, labels, plans):
         T, overlap = self._tile
@@ -638,44 +610,17 @@ class Segmenter:
                 Y[t0:t0 + m].copy_(y)
             Ys = [Y]
         C = int(Ys[0].shape[1])
-        pal = self._palette_on(dev)
-        _check_classes(C, pal)
-        counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
-        M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
+        pal = self._palette_for(dev, C)
         kind, merge = _tta.KINDS[self.outputs[0]], _tta.MERGES[self.tiles.merge]
         window = _tiles.WINDOWS[self.tiles.window]
         s = ops._stream()
-        preds = []
-        for k, (oh, ow, ny, nx) in enumerate(plans):
-            meta = {"original_size": (oh, ow), "tile_size": T, "overlap": overlap, "tiles": (ny, nx)}
-            mask = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
-            conf = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
-            scores = torch.empty((C, oh, ow), dtype=torch.float32, device=dev) if self.return_scores else None
-            color = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev) if pal is not None else None
-            lab = None
-            if labels is not None:
-                lab = _as_tensor(labels[k])
-                if torch.is_floating_point(lab) or tuple(lab.shape) not in ((oh, ow), (1, oh, ow)):
-                    raise ValueError(f"labels {k}: expected an integer map of {(oh, ow)}, got {lab.dtype} {tuple(lab.shape)}")
-                lab = lab.to(dev, non_blocking=True).long().contiguous()
-            Mk = None if M is None else M[k]
-            if self.clean is None:
-                _lib.call("segk_predict_tiles", Ys[k].data_ptr(), C, kind, merge, window, oh, ow, T, overlap, mask.data_ptr(),
-                          ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab), ops._p(Mk), conf.data_ptr(), ops._p(scores), s)
-                preds.append(Prediction(mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta))
-                preds[-1].confidence, preds[-1].scores = conf, scores
-                continue
-            # the blended argmax alone, its components and the cleaned mask, then the other outputs from the cleaned mask
-            _lib.call("segk_predict_tiles", Ys[k].data_ptr(), C, kind, merge, window, oh, ow, T, overlap, mask.data_ptr(), None, None,
-                      None, None, None, conf.data_ptr(), ops._p(scores), s)
-            cl = self.clean
-            comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
-            _lib.call("segk_mask_finish", comps.mask.data_ptr(), ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab),
-                      ops._p(Mk), C, oh, ow, s)
-            preds.append(Prediction(comps.mask, color, counts[k, :C], None if M is None else M[k, :C, :C], meta, mask, comps))
-            preds[-1].confidence, preds[-1].scores = conf, scores
+        metas = [{"original_size": (oh, ow), "tile_size": T, "overlap": overlap, "tiles": (ny, nx)} for oh, ow, ny, nx in plans]
+
+        def launch(k, mask, outs, conf, scores):
+            _lib.call("segk_predict_tiles", Ys[k].data_ptr(), C, kind, merge, window, *plans[k][:2], T, overlap, mask, *outs,
+                      conf, scores, s)
         # the tile outputs are read by launches still in flight: the caching allocator keeps them valid in stream order
-        return preds
+        return self._finish(dev, C, pal, metas, labels, launch, True)
 
 
 def predict(model, images, heatmaps=None, labels=None, points=None, **kw):

@@ -40,21 +40,27 @@ def _geometry(orig_h, orig_w, target_size):
     return new_h, new_w, pad_top, pad_left, meta
 
 
+def _resize_mode(interpolation, antialias=None, integer=False):
+    """The `mode` of the segk_resize_pad* entries: 1 nearest (integer maps always), 0 bilinear with the anti-aliasing
+    filter, 2 bilinear without.  antialias: see ANTIALIAS."""
+    if interpolation == NEAREST or integer:
+        return 1
+    return 0 if (ANTIALIAS if antialias is None else antialias) else 2
+
+
 def _is_cuda_device(device):
     return device is not None and torch.device(device).type == "cuda"
 
 
 def _resize_pad_into(image, slot, target_size, interpolation, antialias=None):
     """image (C,H,W) on the slot's device -> slot (C,T,T) (HIP kernel); returns the metadata."""
-    antialias = ANTIALIAS if antialias is None else antialias
     C, H, W = image.shape
     nh, nw, pt, pl, meta = _geometry(H, W, target_size)
     integer = not torch.is_floating_point(image)
     src = image.contiguous() if (image.dtype in (torch.float32, torch.int64)) else \
         (image.long().contiguous() if integer else image.float().contiguous())
-    mode = 1 if (interpolation == NEAREST or integer) else (0 if antialias else 2)
-    _lib.call("segk_resize_pad", src.data_ptr(), slot.data_ptr(), C, H, W, nh, nw, target_size, pt, pl, mode,
-              1 if integer else 0, torch.cuda.current_stream().cuda_stream)
+    _lib.call("segk_resize_pad", src.data_ptr(), slot.data_ptr(), C, H, W, nh, nw, target_size, pt, pl,
+              _resize_mode(interpolation, antialias, integer), 1 if integer else 0, torch.cuda.current_stream().cuda_stream)
     return meta
 
 
@@ -62,21 +68,15 @@ def resize_with_padding(image, target_size=512, interpolation=BILINEAR, antialia
     """utils.py:13-49 -- (C,H,W) -> (C,target,target) plus metadata.  antialias: see ANTIALIAS."""
     antialias = ANTIALIAS if antialias is None else antialias
     _, orig_h, orig_w = image.shape
-    scale = min(target_size / orig_w, target_size / orig_h)
-    new_w = int(round(orig_w * scale))
-    new_h = int(round(orig_h * scale))
+    new_h, new_w, _, _, meta = _geometry(orig_h, orig_w, target_size)
     img = image.unsqueeze(0)
     if interpolation == NEAREST or not torch.is_floating_point(image):
         resized = F.interpolate(img.float(), size=(new_h, new_w), mode="nearest").to(image.dtype)
     else:
         resized = F.interpolate(img, size=(new_h, new_w), mode="bilinear", align_corners=False, antialias=bool(antialias))
     resized = resized.squeeze(0)
-    pad_w, pad_h = target_size - new_w, target_size - new_h
-    pad_left, pad_top = pad_w // 2, pad_h // 2
-    pad_right, pad_bottom = pad_w - pad_left, pad_h - pad_top
+    pad_left, pad_top, pad_right, pad_bottom = meta["pad"]
     padded = F.pad(resized, (pad_left, pad_right, pad_top, pad_bottom), value=0)
-    meta = {"original_size": (orig_h, orig_w), "new_size": (new_h, new_w),
-            "pad": (pad_left, pad_top, pad_right, pad_bottom), "scale": scale}
     return padded, meta
 
 
