@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 319          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 320          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
@@ -97,6 +97,8 @@ SIGNATURES = {
     "segk_loss_state_floats": (_i, []),
     "segk_loss_fwd": (_i, [_fp, _vp, _fp, _i, _i, _l, _i, _f, _f, _f, _fp, _fp, _fp, _vp]),
     "segk_loss_bwd": (_i, [_fp, _vp, _fp, _fp, _fp, _i, _i, _l, _i, _f, _f, _fp, _vp]),
+    "segk_distill_fwd": (_i, [_fp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _fp, _fp, _fp, _vp]),
+    "segk_distill_bwd": (_i, [_fp, _vp, _i, _vp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _f, _fp, _vp]),
     "segk_prompt_mix_fwd": (_i, [_fp, _fp, _fp, _i, _l, _vp]),
     "segk_prompt_mix_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _l, _vp]),
     "segk_prob_loss_fwd": (_i, [_fp, _vp, _fp, _i, _i, _l, _i, _f, _f, _f, _i, _f, _fp, _fp, _fp, _vp]),

@@ -1,0 +1,365 @@
+// Distillation: the fused multi-teacher soft-target loss (the reference holds no code for it).
+//
+// Per pixel, teachers v = 0..V-1 in table order, everything in fp32 and in this order:
+//   z_v  = the teacher's values at the (flipped) pixel, kind 1: logf(fmaxf(t, 2^-126))
+//   q    = sum_v weight_v * softmax(z_v * invT)          (a multiply, then an add, per class)
+//   q1   = the same with invT = 1 (the gate's confidence); the very same numbers as q when invT == 1
+//   p    = softmax(s * invT), log p = (a - max a) - logf(sum exp)
+//   KL   = sum_k q_k * (logf(q_k) - log p_k), terms with q_k == 0 are 0
+// A pixel counts when (labels == NULL or label != ignore_index) and max_k q1_k >= min_conf.
+// One pass forward (block partials -> the last arriver finishes them in float64, ticket.hpp), one pass backward that forms q
+// again through the same teacher_mix() -- no per-pixel buffer, no float atomics, one fixed order of additions.
+#include <type_traits>
+#include "common.hpp"
+#include "segk_internal.h"
+#include "ticket.hpp"
+#include "../../include/segk.h"
+
+int segk_loss_blocks(long P);          // head_loss.hip: rows of the partial buffer segk_loss_part_floats(P) sizes
+
+namespace {
+constexpr int MAXC = SEGK_MAX_CLASSES;
+constexpr int DT = 1024;               // threads of a forward block (segk_loss_blocks counts 4 pixels per thread and pass)
+constexpr int DROWS = 256;             // most partial rows (segk_loss_blocks' cap)
+constexpr int DP = 4;                  // words per partial row: [0] sum KL (float), [1] n, [2] n_agree (uint32 bits), [3] unused
+constexpr float TINYF = 1.17549435e-38f;   // 2^-126
+
+static_assert(sizeof(segk_teacher_desc) == 32, "segk_teacher_desc is 32 bytes (image_segmentation_amd/distill.py: TEACHER_DESC)");
+
+// pixels a forward thread keeps in flight: every load of all of them (per teacher) is issued before the first is used
+template <int NC> constexpr int fwd_pif() { return NC <= 4 ? 4 : 2; }
+template <int NC> constexpr int bwd_pif() { return NC <= 4 ? 2 : 1; }
+
+// p = softmax(a) over the NC compiled classes (padded entries are -inf and come out as 0); returns max and sum through m, S
+template <int NC>
+__device__ __forceinline__ void softmax_nc(const float (&a)[NC], float (&p)[NC], float& m, float& S) {
+  m = a[0];
+#pragma unroll
+  for (int k = 1; k < NC; ++k) m = fmaxf(m, a[k]);
+  S = 0.f;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) { p[k] = expf(a[k] - m); S += p[k]; }
+  const float inv = 1.f / S;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) p[k] *= inv;
+}
+
+// first maximum, NaN maximal (segk_predict_mask's rule) over the first C entries
+template <int NC>
+__device__ __forceinline__ int argmax_nc(const float (&v)[NC], int C) {
+  int best = 0;
+  float bv = v[0];
+#pragma unroll
+  for (int k = 1; k < NC; ++k)
+    if (k < C && (v[k] > bv || (v[k] != v[k] && bv == bv))) { bv = v[k]; best = k; }
+  return best;
+}
+
+// The tempered teacher q (and, TEMP, the untempered q1) of PIF pixels (image b[u], offset r[u] inside the image).  Forward and
+// backward both come through here, so they see the same bits.  All loads of a teacher (PIF pixels x NC classes) are
+// unconditional, from a class index clamped into the tensor, and in flight together.
+template <int NC, bool TEMP, int PIF>
+__device__ __forceinline__ void teacher_mix(const segk_teacher_desc* __restrict__ tab, int V, int C, int H, int W, long HW,
+                                            float invT, const long (&b)[PIF], const long (&r)[PIF], float (&q)[PIF][NC],
+                                            float (&q1)[TEMP ? PIF : 1][NC]) {
+  int yy[PIF], xx[PIF];
+#pragma unroll
+  for (int u = 0; u < PIF; ++u) {
+    yy[u] = (int)((unsigned)r[u] / (unsigned)W);
+    xx[u] = (int)r[u] - yy[u] * W;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      q[u][k] = 0.f;
+      if constexpr (TEMP) q1[u][k] = 0.f;
+    }
+  }
+  for (int v = 0; v < V; ++v) {
+    const segk_teacher_desc d = tab[v];                          // uniform: scalar loads
+    const float* __restrict__ base = (const float*)d.ptr;
+    float raw[PIF][NC];
+#pragma unroll
+    for (int u = 0; u < PIF; ++u) {
+      const int ry = (d.flip & 2) ? H - 1 - yy[u] : yy[u];
+      const int rx = (d.flip & 1) ? W - 1 - xx[u] : xx[u];
+      const long o = b[u] * C * HW + (long)ry * W + rx;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) raw[u][k] = base[o + (long)(k < C ? k : C - 1) * HW];
+    }
+#pragma unroll
+    for (int u = 0; u < PIF; ++u) {
+      float z[NC], pv[NC], m, S;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        float t = raw[u][k];
+        if (d.kind) t = logf(fmaxf(t, TINYF));
+        z[k] = (k < C) ? t : -INFINITY;
+      }
+      if constexpr (TEMP) {
+        softmax_nc<NC>(z, pv, m, S);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) q1[u][k] += d.weight * pv[k];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) z[k] = (k < C) ? z[k] * invT : -INFINITY;
+      }
+      softmax_nc<NC>(z, pv, m, S);
+#pragma unroll
+      for (int k = 0; k < NC; ++k) q[u][k] += d.weight * pv[k];
+    }
+  }
+}
+
+// max_k q1_k >= min_conf (false for a NaN maximum)
+template <int NC>
+__device__ __forceinline__ bool confident(const float (&q1)[NC], int C, float min_conf) {
+  float mx = q1[0];
+#pragma unroll
+  for (int k = 1; k < NC; ++k) mx = fmaxf(mx, (k < C) ? q1[k] : mx);
+  return mx >= min_conf;
+}
+
+// runs in the block that arrived last: NB <= DROWS rows of [sum KL, n, n_agree] -> state, loss_out.  One row per thread, all
+// loads in flight at once; a wave butterfly and four wave rows in float64 / uint64: one fixed order
+__device__ __forceinline__ void distill_finalize_block(const float* __restrict__ part, int NB, float Tsq,
+                                                       float* __restrict__ state, float* __restrict__ loss_out) {
+  __shared__ double skl[DROWS / 64];
+  __shared__ unsigned long long scn[DROWS / 64], sag[DROWS / 64];
+  const int t = threadIdx.x;
+  if (t < DROWS) {
+    const int row = t < NB ? t : NB - 1;                         // unconditional loads of a clamped row
+    const float f0 = part[row * DP];
+    const unsigned u1 = __float_as_uint(part[row * DP + 1]), u2 = __float_as_uint(part[row * DP + 2]);
+    double kl = t < NB ? (double)f0 : 0.0;
+    unsigned long long cn = t < NB ? u1 : 0u, ag = t < NB ? u2 : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      kl += __shfl_xor(kl, o);
+      cn += __shfl_xor(cn, o);
+      ag += __shfl_xor(ag, o);
+    }
+    if ((t & 63) == 0) { skl[t >> 6] = kl; scn[t >> 6] = cn; sag[t >> 6] = ag; }
+  }
+  __syncthreads();
+  if (t != 0) return;
+  double kl = 0.0;
+  unsigned long long cn = 0, ag = 0;
+  for (int w = 0; w < DROWS / 64; ++w) { kl += skl[w]; cn += scn[w]; ag += sag[w]; }   // fixed order
+  // a gate or an ignore mask that passes nothing: exactly 0, not 0 / 0 (the backward pass then writes exact zeros)
+  const float soft = cn > 0 ? (float)((double)Tsq * kl / (double)cn) : 0.f;
+  state[0] = soft;
+  state[1] = (float)cn;
+  state[2] = cn > 0 ? (float)kl : 0.f;
+  state[3] = (float)ag;
+  for (int i = 4; i < 4 + 3 * MAXC; ++i) state[i] = 0.f;
+  if (loss_out) *loss_out = soft;
+}
+
+template <int NC, bool TEMP, bool LAB>
+__global__ __launch_bounds__(DT) void distill_fwd_kernel(const float* __restrict__ student,
+                                                         const segk_teacher_desc* __restrict__ tab, int V,
+                                                         const long long* __restrict__ labels, long P, long HW, int C, int H,
+                                                         int W, int ignore_index, float invT, float Tsq, float min_conf,
+                                                         float* __restrict__ part, float* __restrict__ state,
+                                                         float* __restrict__ loss_out, unsigned* __restrict__ ticket) {
+  __shared__ float shk[DT / 64];
+  __shared__ unsigned shn[DT / 64], sha[DT / 64];
+  __shared__ int last;
+  float akl = 0.f;
+  unsigned cnt = 0, agree = 0;
+  auto pixels = [&](auto PIFc, long p, long step) {
+    constexpr int PIF = decltype(PIFc)::value;
+    long b[PIF], r[PIF];
+    float s[PIF][NC];
+    long long y[PIF];
+#pragma unroll
+    for (int u = 0; u < PIF; ++u) {
+      const unsigned pp = (unsigned)(p + u * step);
+      const unsigned bb = pp / (unsigned)HW;                     // one 32-bit division per pixel (P < 2^31)
+      b[u] = (long)bb;
+      r[u] = (long)pp - (long)bb * HW;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) s[u][k] = student[(b[u] * C + (k < C ? k : C - 1)) * HW + r[u]];
+      if constexpr (LAB) y[u] = labels[pp];
+      else y[u] = 0;
+    }
+    float q[PIF][NC], q1[TEMP ? PIF : 1][NC];
+    teacher_mix<NC, TEMP, PIF>(tab, V, C, H, W, HW, invT, b, r, q, q1);
+#pragma unroll
+    for (int u = 0; u < PIF; ++u) {
+      float a[NC], pr[NC], m, S;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) a[k] = (k < C) ? (TEMP ? s[u][k] * invT : s[u][k]) : -INFINITY;
+      softmax_nc<NC>(a, pr, m, S);
+      const float lse = logf(S);
+      float kl = 0.f;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        const float qk = q[u][k];
+        const float term = qk * (logf(qk) - ((a[k] - m) - lse));
+        kl += (k < C && qk > 0.f) ? term : 0.f;
+      }
+      bool ok = TEMP ? confident<NC>(q1[TEMP ? u : 0], C, min_conf) : confident<NC>(q[u], C, min_conf);
+      if constexpr (LAB) ok = ok && y[u] != (long long)ignore_index;
+      if (ok) {
+        akl += kl;
+        cnt += 1u;
+        agree += (argmax_nc<NC>(pr, C) == argmax_nc<NC>(q[u], C)) ? 1u : 0u;
+      }
+    }
+  };
+  constexpr int PIF = fwd_pif<NC>();
+  const long step = (long)gridDim.x * DT;
+  long p = (long)blockIdx.x * DT + threadIdx.x;
+  for (; p + (PIF - 1) * step < P; p += PIF * step) pixels(std::integral_constant<int, PIF>{}, p, step);
+  for (; p < P; p += step) pixels(std::integral_constant<int, 1>{}, p, step);
+  // wave sums by butterfly, the wave rows through LDS, one partial row per block
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    akl += __shfl_xor(akl, o);
+    cnt += __shfl_xor(cnt, o);
+    agree += __shfl_xor(agree, o);
+  }
+  if ((threadIdx.x & 63) == 0) { shk[threadIdx.x >> 6] = akl; shn[threadIdx.x >> 6] = cnt; sha[threadIdx.x >> 6] = agree; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s2 = 0.f;
+    unsigned n2 = 0, a2 = 0;
+#pragma unroll
+    for (int w = 0; w < DT / 64; ++w) { s2 += shk[w]; n2 += shn[w]; a2 += sha[w]; }   // fixed order
+    float* row = part + (size_t)blockIdx.x * DP;
+    row[0] = s2;
+    row[1] = __uint_as_float(n2);
+    row[2] = __uint_as_float(a2);
+    row[3] = 0.f;
+  }
+  if (last_arriver(ticket, gridDim.x, &last)) distill_finalize_block(part, (int)gridDim.x, Tsq, state, loss_out);
+}
+
+template <int NC, bool TEMP, bool LAB>
+__global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restrict__ student,
+                                                          const segk_teacher_desc* __restrict__ tab, int V,
+                                                          const long long* __restrict__ labels,
+                                                          const float* __restrict__ state, const float* __restrict__ gout,
+                                                          long P, long HW, int C, int H, int W, int ignore_index, float invT,
+                                                          float Tsq, float min_conf, float* __restrict__ dstudent) {
+  const float n = state[1];
+  const float coef = n > 0.f ? ((gout[0] * Tsq) * invT) / n : 0.f;
+  auto pixels = [&](auto PIFc, long p, long step) {
+    constexpr int PIF = decltype(PIFc)::value;
+    long b[PIF], r[PIF];
+    float s[PIF][NC];
+    long long y[PIF];
+#pragma unroll
+    for (int u = 0; u < PIF; ++u) {
+      const unsigned pp = (unsigned)(p + u * step);
+      const unsigned bb = pp / (unsigned)HW;
+      b[u] = (long)bb;
+      r[u] = (long)pp - (long)bb * HW;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) s[u][k] = student[(b[u] * C + (k < C ? k : C - 1)) * HW + r[u]];
+      if constexpr (LAB) y[u] = labels[pp];
+      else y[u] = 0;
+    }
+    float q[PIF][NC], q1[TEMP ? PIF : 1][NC];
+    teacher_mix<NC, TEMP, PIF>(tab, V, C, H, W, HW, invT, b, r, q, q1);
+#pragma unroll
+    for (int u = 0; u < PIF; ++u) {
+      float a[NC], pr[NC], m, S;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) a[k] = (k < C) ? (TEMP ? s[u][k] * invT : s[u][k]) : -INFINITY;
+      softmax_nc<NC>(a, pr, m, S);
+      bool ok = TEMP ? confident<NC>(q1[TEMP ? u : 0], C, min_conf) : confident<NC>(q[u], C, min_conf);
+      if constexpr (LAB) ok = ok && y[u] != (long long)ignore_index;
+      ok = ok && n > 0.f;
+#pragma unroll
+      for (int k = 0; k < NC; ++k)
+        if (k < C) dstudent[(b[u] * C + k) * HW + r[u]] = ok ? coef * (pr[k] - q[u][k]) : 0.f;
+    }
+  };
+  constexpr int PIF = bwd_pif<NC>();
+  const long step = (long)gridDim.x * 256;
+  long p = (long)blockIdx.x * 256 + threadIdx.x;
+  for (; p + (PIF - 1) * step < P; p += PIF * step) pixels(std::integral_constant<int, PIF>{}, p, step);
+  for (; p < P; p += step) pixels(std::integral_constant<int, 1>{}, p, step);
+}
+
+// kernels are compiled for 1, 2, 3, 4 and MAXC classes (the smallest that holds C), with and without a temperature (invT == 1
+// needs no second softmax per teacher) and with and without labels
+template <typename F>
+int by_variant(int C, bool temp, bool lab, F&& launch) {
+  auto by_lab = [&](auto NCc, auto TEMPc) {
+    return lab ? launch(NCc, TEMPc, std::true_type{}) : launch(NCc, TEMPc, std::false_type{});
+  };
+  auto by_temp = [&](auto NCc) { return temp ? by_lab(NCc, std::true_type{}) : by_lab(NCc, std::false_type{}); };
+  if (C == 1) return by_temp(std::integral_constant<int, 1>{});
+  if (C == 2) return by_temp(std::integral_constant<int, 2>{});
+  if (C == 3) return by_temp(std::integral_constant<int, 3>{});
+  if (C == 4) return by_temp(std::integral_constant<int, 4>{});
+  return by_temp(std::integral_constant<int, MAXC>{});
+}
+
+int check_common(const char* name, const void* student, const void* tab, int V, int N, int C, int H, int W, float invT, float Tsq,
+                 float min_conf) {
+  SEGK_REQUIRE(student != nullptr, "%s: null student logits", name);
+  SEGK_REQUIRE(tab != nullptr, "%s: null teacher table", name);
+  SEGK_REQUIRE(((uintptr_t)tab & 15) == 0, "%s: the teacher table must be 16-byte aligned", name);
+  SEGK_REQUIRE(((uintptr_t)student & 3) == 0, "%s: the student logits must be 4-byte aligned", name);
+  SEGK_REQUIRE(V >= 1 && V <= SEGK_MAX_VIEWS, "%s: 1..%d teachers supported, got %d", name, SEGK_MAX_VIEWS, V);
+  SEGK_REQUIRE(C >= 1 && C <= MAXC, "%s: 1..%d classes supported, got %d", name, MAXC, C);
+  SEGK_REQUIRE(N > 0 && H > 0 && W > 0, "%s: bad shape N=%d H=%d W=%d", name, N, H, W);
+  SEGK_REQUIRE((long)N * H * W < (1L << 31), "%s: pixels are indexed with 32 bits: %ld pixels", name, (long)N * H * W);
+  SEGK_REQUIRE((long)N * H * W * C < (1L << 40), "%s: tensor too large", name);
+  SEGK_REQUIRE(invT > 0.f && invT < INFINITY, "%s: 1/T must be positive and finite, got %g", name, (double)invT);
+  SEGK_REQUIRE(Tsq > 0.f && Tsq < INFINITY, "%s: T*T must be positive and finite, got %g", name, (double)Tsq);
+  SEGK_REQUIRE(min_conf == min_conf && min_conf > -INFINITY && min_conf < INFINITY, "%s: min_conf must be finite", name);
+  return 0;
+}
+}  // namespace
+
+extern "C" int segk_distill_fwd(const float* student, const void* teachers_dev, int V, const int64_t* labels, int N, int C, int H,
+                                int W, int ignore_index, float inv_T, float T_sq, float min_conf, float* part, float* state,
+                                float* loss_out, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  if (const int rc = check_common("distill_fwd", student, teachers_dev, V, N, C, H, W, inv_T, T_sq, min_conf)) return rc;
+  SEGK_REQUIRE(part != nullptr, "distill_fwd: null partial buffer");
+  SEGK_REQUIRE(state != nullptr, "distill_fwd: null state");
+  SEGK_REQUIRE(((uintptr_t)part & 3) == 0 && ((uintptr_t)state & 3) == 0 && ((uintptr_t)loss_out & 3) == 0 &&
+               ((uintptr_t)labels & 7) == 0, "distill_fwd: misaligned buffer");
+  const long HW = (long)H * W, P = (long)N * HW;
+  const int nb = segk_loss_blocks(P);                            // nb * DP <= segk_loss_part_floats(P)
+  SEGK_REQUIRE(nb >= 1 && nb <= DROWS, "distill_fwd: bad block count %d", nb);
+  unsigned* const ticket = segk_ticket_slot(1, st);
+  SEGK_REQUIRE(ticket != nullptr, "distill_fwd: no ticket array");
+  const int rc = by_variant(C, inv_T != 1.0f, labels != nullptr, [&](auto NCc, auto TEMPc, auto LABc) {
+    hipLaunchKernelGGL((distill_fwd_kernel<decltype(NCc)::value, decltype(TEMPc)::value, decltype(LABc)::value>), dim3(nb),
+                       dim3(DT), 0, st, student, (const segk_teacher_desc*)teachers_dev, V, (const long long*)labels, P, HW, C, H,
+                       W, ignore_index, inv_T, T_sq, min_conf, part, state, loss_out, ticket);
+    return 0;
+  });
+  (void)rc;
+  SEGK_CHECK_LAUNCH("distill_fwd");
+  return 0;
+}
+
+extern "C" int segk_distill_bwd(const float* student, const void* teachers_dev, int V, const int64_t* labels, const float* state,
+                                const float* grad_out, int N, int C, int H, int W, int ignore_index, float inv_T, float T_sq,
+                                float min_conf, float* dstudent, segk_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  if (const int rc = check_common("distill_bwd", student, teachers_dev, V, N, C, H, W, inv_T, T_sq, min_conf)) return rc;
+  SEGK_REQUIRE(state != nullptr, "distill_bwd: null state");
+  SEGK_REQUIRE(grad_out != nullptr, "distill_bwd: null upstream gradient");
+  SEGK_REQUIRE(dstudent != nullptr, "distill_bwd: null gradient buffer");
+  SEGK_REQUIRE(((uintptr_t)state & 3) == 0 && ((uintptr_t)grad_out & 3) == 0 && ((uintptr_t)dstudent & 3) == 0 &&
+               ((uintptr_t)labels & 7) == 0, "distill_bwd: misaligned buffer");
+  const long HW = (long)H * W, P = (long)N * HW;
+  long g = (P + 255) / 256;
+  if (g > 4096) g = 4096;
+  const int rc = by_variant(C, inv_T != 1.0f, labels != nullptr, [&](auto NCc, auto TEMPc, auto LABc) {
+    hipLaunchKernelGGL((distill_bwd_kernel<decltype(NCc)::value, decltype(TEMPc)::value, decltype(LABc)::value>), dim3((int)g),
+                       dim3(256), 0, st, student, (const segk_teacher_desc*)teachers_dev, V, (const long long*)labels, state,
+                       grad_out, P, HW, C, H, W, ignore_index, inv_T, T_sq, min_conf, dstudent);
+    return 0;
+  });
+  (void)rc;
+  SEGK_CHECK_LAUNCH("distill_bwd");
+  return 0;
+}

@@ -1489,6 +1489,73 @@ class ProbLossFn(torch.autograd.Function):
         return dp, None, None, None, None, None, None, None, None
 
 
+class DistillFn(torch.autograd.Function):
+    """T*T * mean over the counted pixels of KL(q || softmax(logits / T)), q the weighted mean of the teachers' tempered
+    softmaxes -- one pass over the student logits and every teacher view forward, one backward (the reference
+    holds no code for distillation).  views: an object with `outputs` (V detached fp32 contiguous [N,C,H,W] tensors, kept alive
+    here) and `table` (the device table of segk_teacher_desc rows naming them; distill.TeacherViews).  target: int64 [N,H,W]
+    labels or None; a label equal to ignore_index takes the pixel out.  Returns (soft, state): the soft term in a buffer of
+    its own and the kernel's state [soft, n, sum KL, n_agree, ...] (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, logits, views, target, ignore_index, temperature, min_confidence):
+        if logits.dim() != 4:
+            raise ValueError(f"expected logits [N,C,H,W], got {tuple(logits.shape)}")
+        N, C, H, W = logits.shape
+        if C > _lib.MAX_CLASSES:
+            raise RuntimeError(f"fused distillation loss supports up to {_lib.MAX_CLASSES} classes, got {C}")
+        V = len(views.outputs)
+        if not 1 <= V <= _lib.MAX_VIEWS:
+            raise ValueError(f"{V} teacher views: 1..{_lib.MAX_VIEWS} supported")
+        for v, t in enumerate(views.outputs):
+            if tuple(t.shape) != (N, C, H, W):
+                raise ValueError(f"teacher view {v} has shape {tuple(t.shape)}, the student's logits {tuple(logits.shape)}: "
+                                 "class count and resolution must agree")
+        T = float(temperature)
+        if not (T > 0 and T < float("inf")):
+            raise ValueError(f"temperature must be positive and finite, got {temperature}")
+        _require_cuda(logits, "distillation loss")
+        for t in views.outputs:
+            _require_cuda(t, "distillation loss (teacher view)")
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != logits.device:
+                raise ValueError("teacher views must be contiguous float32 tensors on the student's device")
+        lg = logits.detach()
+        if lg.dtype != torch.float32 or not lg.is_contiguous():
+            lg = lg.float().contiguous()
+        tg = None
+        if target is not None and ignore_index is not None:
+            tg = target.detach()
+            if tg.dtype != torch.int64 or not tg.is_contiguous():
+                tg = tg.long().contiguous()
+            if tg.numel() != N * H * W:
+                raise ValueError(f"target shape {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+        dev = logits.device
+        ign = 0 if ignore_index is None else int(ignore_index)
+        part = _f32(_lib.query("segk_loss_part_floats", N * H * W), dev)
+        state = _f32(_lib.query("segk_loss_state_floats"), dev)
+        out = _f32(1, dev)
+        cfg = (V, N, C, H, W, ign, 1.0 / T, T * T, float(min_confidence))
+        with _span("distill_fwd", 0.0, N * H * W * (4.0 * C * (1 + V) + (8 if tg is not None else 0))):
+            _lib.call("segk_distill_fwd", lg.data_ptr(), views.table.data_ptr(), V, _p(tg), N, C, H, W, ign, cfg[6], cfg[7],
+                      cfg[8], part.data_ptr(), state.data_ptr(), out.data_ptr(), _stream())
+        ctx.cfg = cfg
+        ctx.views = views                    # keeps the teacher outputs and the table alive until backward has run
+        ctx.save_for_backward(lg, tg, state)
+        ctx.mark_non_differentiable(state)
+        return out.view(()), state
+
+    @staticmethod
+    def backward(ctx, gout, _gstate):
+        lg, tg, state = ctx.saved_tensors
+        V, N, C, H, W, ign, inv_t, t_sq, min_conf = ctx.cfg
+        go = gout.detach().float().reshape(1).contiguous()
+        dl = torch.empty_like(lg)
+        with _span("distill_bwd", 0.0, N * H * W * (4.0 * C * (2 + V) + (8 if tg is not None else 0))):
+            _lib.call("segk_distill_bwd", lg.data_ptr(), ctx.views.table.data_ptr(), V, _p(tg), state.data_ptr(), go.data_ptr(),
+                      N, C, H, W, ign, inv_t, t_sq, min_conf, dl.data_ptr(), _stream())
+        return dl, None, None, None, None, None
+
+
 class PromptMixFn(torch.autograd.Function):
     """final_probs of the prompt model (reference prompt_based/prompt.py:35-56): softmax of the frozen 4-class CLIP-UNet
     logits remixed with the sigmoid of the mask U-Net's logit; gradient flows to the mask logit only (prompt.py:30-31)."""

@@ -292,6 +292,58 @@ def train_loop_prompt(dataloader, model, loss_fn, optimizer, accumulation_steps,
     return avg_loss
 
 
+def train_loop_distill(dataloader, student, teacher, loss_fn, optimizer, accumulation_steps, device, scheduler=None,
+                       target_size=None, grad_sync=None):
+    """One epoch of distillation: train_loop's accumulation / step / averaging protocol with the frozen
+    teacher (distill.Teacher) run on the same resized batch and loss_fn (distill.DistillLoss) called as
+    loss_fn(pred, y, teacher_views).  Batches are (X, y), (X, None) or X alone; without labels y is None and the loss must be
+    all soft (alpha = 1)."""
+    student.train()
+    total_loss = 0.0
+    processed_batches = 0
+
+    optimizer.zero_grad()
+
+    n = len(dataloader)
+    pbar = _bar(enumerate(dataloader), total=n, desc="Training")
+    for batch_idx, batch in pbar:
+        X, y = (batch[0], batch[1] if len(batch) > 1 else None) if isinstance(batch, (tuple, list)) else (batch, None)
+        if target_size is not None:
+            X, _ = process_batch_forward(X, target_size=target_size, device=device)
+            if y is not None:
+                y, _ = process_batch_forward(y, target_size=target_size, interpolation=NEAREST, device=device)
+
+        X = X.to(device)
+        if y is not None:
+            y = y.to(device).long()
+        views = teacher(X)
+        pred = student(X)
+        loss = loss_fn(pred, None if y is None else y.squeeze(1), views)
+
+        scaled_loss = loss / accumulation_steps
+        stepping = (batch_idx + 1) % accumulation_steps == 0 or (batch_idx + 1) == n
+        if grad_sync is not None and stepping:
+            grad_sync.arm()               # overlap the RCCL all-reduce with this backward
+        scaled_loss.backward()
+
+        if stepping:
+            if grad_sync is not None:
+                grad_sync.sync()
+            optimizer.step()
+            if scheduler:
+                scheduler.step()
+            optimizer.zero_grad()
+
+            total_loss += loss.item()
+            processed_batches += 1
+            if hasattr(pbar, "set_postfix"):
+                pbar.set_postfix({'loss': loss.item(), 'lr': optimizer.param_groups[0]['lr']})
+
+    avg_loss = total_loss / processed_batches if processed_batches > 0 else 0
+    _say(f"Training Avg loss (per effective batch): {avg_loss:>8f}")
+    return avg_loss
+
+
 def eval_loop_prompt(dataloader, model, loss_fn, device, target_size, agg, grad_sync=None):
     """training.py:242-296: eval_loop for (image, heat-map, label) batches; the heat-map takes the image's
     resize + pad.  Returns (avg_loss, mean_dice, mean_iou)."""

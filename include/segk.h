@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 319
-#define SEGK_ENTRY_COUNT 96
+#define SEGK_ABI_VERSION 320
+#define SEGK_ENTRY_COUNT 98
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -442,6 +442,35 @@ int segk_loss_fwd(const float* logits, const int64_t* labels, const float* class
 int segk_loss_bwd(const float* logits, const int64_t* labels, const float* class_weights, const float* state,
                   const float* grad_out, int N, int C, long HW, int ignore_index, float dice_weight, float ce_weight,
                   float* dlogits, segk_stream_t s);
+
+/* ---- distillation: fused multi-teacher soft-target loss (the reference holds no code for it) ----
+ * student fp32 [N,C,H,W] logits; V teacher tensors fp32 [N,C,H,W] named by a DEVICE table of V descriptors (16-byte aligned;
+ * the host never reads it, so its contents are the caller's to get right: image_segmentation_amd/distill.py: teacher_table);
+ * labels int64 [N,H,W] or NULL. */
+typedef struct segk_teacher_desc {   /* one teacher view; 32 bytes, 16-byte aligned */
+  uint64_t ptr;                      /* device address of the teacher's fp32 [N,C,H,W] output */
+  int32_t flip;                      /* bit 0: the view saw the batch reversed in x, bit 1: in y */
+  int32_t kind;                      /* 0: logits, 1: probabilities, taken as z = logf(fmaxf(t, 2^-126)) */
+  float weight;                      /* w_v / sum of the weights, rounded once from float64 */
+  int32_t pad_[3];
+} segk_teacher_desc;
+/* Per pixel (b, y, x), for v = 0..V-1 in table order and in fp32: z_v = teacher v at (flip & 2 ? H-1-y : y, flip & 1 ? W-1-x : x),
+ * q += weight_v * softmax(z_v * inv_T), q1 += weight_v * softmax(z_v) (the same numbers as q when inv_T == 1.0f); p = softmax(s *
+ * inv_T).  The pixel COUNTS when (labels == NULL or label != ignore_index) and max_k q1_k >= min_conf.  KL = sum_k q_k (logf(q_k)
+ * - log p_k), terms with q_k == 0 being 0.  state (segk_loss_state_floats() floats): [0] = soft = T_sq * sum KL / n, [1] = n, the
+ * number of counted pixels, [2] = sum KL, [3] = n_agree, the counted pixels with argmax p == argmax q (first maximum, NaN maximal),
+ * the rest 0; n == 0 gives soft = 0 exactly.  loss_out (may be NULL): a copy of state[0].  part: segk_loss_part_floats(N H W)
+ * floats of scratch.  No float atomics: the block that finishes last sums the block partials in float64 in one fixed order.
+ * 1 <= C <= 8, 1 <= V <= SEGK_MAX_VIEWS, N H W < 2^31, inv_T and T_sq positive and finite, min_conf finite; every scalar and
+ * every host-visible pointer is validated (-2 before any launch). */
+int segk_distill_fwd(const float* student, const void* teachers_dev, int V, const int64_t* labels, int N, int C, int H, int W,
+                     int ignore_index, float inv_T, float T_sq, float min_conf, float* part, float* state, float* loss_out,
+                     segk_stream_t s);
+/* dstudent [N,C,H,W] = grad_out[0] * T_sq * inv_T / n * (p - q) at counted pixels, exactly 0 elsewhere (and everywhere when
+ * n == 0); q is formed again by the code the forward pass ran, from the same arguments.  Teachers get no gradient. */
+int segk_distill_bwd(const float* student, const void* teachers_dev, int V, const int64_t* labels, const float* state,
+                     const float* grad_out, int N, int C, int H, int W, int ignore_index, float inv_T, float T_sq, float min_conf,
+                     float* dstudent, segk_stream_t s);
 
 /* ---- prompt model (prompt_based/prompt.py:33-56; utils/weighted_loss.py:170-343) ---------------------------
  * remix of the frozen 4-class CLIP-UNet softmax with the sigmoid of the 1-channel mask U-Net, fp32 NCHW:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib)"""
+(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -162,6 +162,60 @@ def loss():
         tf = timeit(f, 50); tb = timeit(b, 50)
         print(f"loss {name:8s} fwd {tf:7.1f} us ({N*H*W*(4*C+8)/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({N*H*W*(8*C+8)/tb/1e3:7.1f} GB/s)"
               f"   value {float(out):.6f}")
+
+
+def distill():
+    """Distillation loss forward / backward (segk_distill_fwd / _bwd) through the C ABI at the bench batch, 32 x C x 256 x 256, for
+    C = 3, 4 and V = 1, 3 teacher views (T = 2, no labels), beside segk_loss_fwd / _bwd (CrossEntropy) at the same P and C and the
+    stock-torch composition (softmax + flip per teacher, weighted sum, log_softmax, kl_div; its backward through autograd)."""
+    import numpy as np
+    import torch.nn.functional as F
+    from image_segmentation_amd import distill as dmod
+    N, H, W, T = 32, 256, 256, 2.0
+    P = N * H * W
+    st = ops._stream()
+    for C in (3, 4):
+        lg = torch.randn((N, C, H, W), device="cuda")
+        tg = torch.randint(0, C, (N, H, W), device="cuda")
+        part = torch.empty(_lib.query("segk_loss_part_floats", P), device="cuda")
+        state = torch.empty(_lib.query("segk_loss_state_floats"), device="cuda")
+        out = torch.empty(1, device="cuda"); go = torch.ones(1, device="cuda"); dl = torch.empty_like(lg)
+        f = lambda: _lib.call("segk_loss_fwd", lg.data_ptr(), tg.data_ptr(), None, N, C, H * W, -1, 1e-5, 0.0, 1.0,
+                              part.data_ptr(), state.data_ptr(), out.data_ptr(), st)
+        b = lambda: _lib.call("segk_loss_bwd", lg.data_ptr(), tg.data_ptr(), None, state.data_ptr(), go.data_ptr(), N, C,
+                              H * W, -1, 0.0, 1.0, dl.data_ptr(), st)
+        tf = timeit(f, 50); tb = timeit(b, 50)
+        print(f"loss ce    C={C}      fwd {tf:7.1f} us ({P*(4*C+8)/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({P*(8*C+8)/tb/1e3:7.1f} GB/s)")
+        for V in (1, 3):
+            ts = [torch.randn((N, C, H, W), device="cuda") for _ in range(V)]
+            flips = [v % 4 for v in range(V)]
+            host = dmod.teacher_table((t.data_ptr(), fl, 0, 1.0 + v) for v, (t, fl) in enumerate(zip(ts, flips)))
+            table = torch.from_numpy(host.view(np.uint8).copy()).cuda()
+            f = lambda: _lib.call("segk_distill_fwd", lg.data_ptr(), table.data_ptr(), V, None, N, C, H, W, 0, 1.0 / T, T * T, 0.0,
+                                  part.data_ptr(), state.data_ptr(), out.data_ptr(), st)
+            b = lambda: _lib.call("segk_distill_bwd", lg.data_ptr(), table.data_ptr(), V, None, state.data_ptr(), go.data_ptr(), N, C,
+                                  H, W, 0, 1.0 / T, T * T, 0.0, dl.data_ptr(), st)
+            tf = timeit(f, 50); tb = timeit(b, 50)
+            val = float(out)
+            w = [float(x) for x in host["weight"]]
+            leaf = lg.clone().requires_grad_(True)
+
+            def torch_fwd():
+                q = 0
+                for t, fl, wv in zip(ts, flips, w):
+                    dims = [d for d, bit in ((3, 1), (2, 2)) if fl & bit]
+                    p = torch.softmax(t / T, 1)
+                    q = q + wv * (torch.flip(p, dims) if dims else p)
+                return T * T * F.kl_div(F.log_softmax(leaf / T, 1), q, reduction="sum") / P
+
+            def torch_both():
+                leaf.grad = None
+                torch_fwd().backward()
+            with torch.no_grad():
+                ttf = timeit(torch_fwd, 20)
+            ttb = timeit(torch_both, 20) - ttf
+            print(f"distill    C={C} V={V}  fwd {tf:7.1f} us ({P*4*C*(1+V)/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({P*4*C*(2+V)/tb/1e3:7.1f} GB/s)"
+                  f"   value {val:.6f}   torch fwd {ttf:7.1f} us  bwd {ttb:7.1f} us  value {float(torch_fwd()):.6f}")
 
 
 def head():
@@ -893,6 +947,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "recon":
         recon()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "distill":
+        distill()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "loss":
         loss()
