@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["api.hip", "conv_igemm.hip", "conv_rs.hip", "convt_stream.hip", "stem.hip", "wgrad.hip", "bn_pool.hip", "pack.hip", "head_loss.hip", "distill.hip", "recon.hip", "prompt.hip", "augment.hip", "perturb.hip", "components.hip", "resize.hip", "calib.hip", "tiles.hip", "vit.hip", "gemm.hip", "probe.hip"]
+SOURCES = ["api.hip", "conv_igemm.hip", "conv_rs.hip", "convt_stream.hip", "stem.hip", "wgrad.hip", "bn_pool.hip", "pack.hip", "head_loss.hip", "distill.hip", "recon.hip", "prompt.hip", "augment.hip", "perturb.hip", "components.hip", "resize.hip", "predict.hip", "calib.hip", "tiles.hip", "vit.hip", "gemm.hip", "probe.hip"]
 LIB = os.path.join(CSRC, "libsegk.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
@@ -21,28 +21,30 @@ def _hipcc():
     raise RuntimeError("hipcc not found")
 
 
+def _inputs(suffixes):
+    """The files of csrc/ with one of `suffixes`, in a fixed order, then the public header."""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(suffixes)] + \
+           [os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "segk.h")]
+
+
 def source_hash() -> str:
     """sha256 over every file the library is built from (kernel sources, internal headers, the public header), in a
     fixed order.  Compiled into the library (segk_build_id()), so a shipped libsegk.so can be checked against the
     sources beside it (tests/test_abi.py) and profile records can name the build they were taken on."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".h")))
-    paths = [os.path.join(CSRC, f) for f in files] + \
-            [os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "segk.h")]
-    for path in paths:
+    for path in _inputs((".hip", ".hpp", ".h")):
         h.update(os.path.basename(path).encode() + b"\0")
         h.update(open(path, "rb").read())
     return h.hexdigest()[:16]
 
 
 def _stale(obj, src):
+    """An object is stale when its source or ANY header is newer: no per-unit include lists to keep in step."""
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    deps = [src] + [os.path.join(CSRC, h) for h in ("common.hpp", "segk_internal.h")] + \
-           [os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "segk.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in [src] + _inputs((".hpp", ".h")))
 
 
 def build(force: bool = False, verbose: bool = True) -> str:

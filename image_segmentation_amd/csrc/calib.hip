@@ -3,38 +3,16 @@
 // negative log-likelihood of K temperatures at the image's own size, in one pass.  Integer sums only: no float atomics, no
 // ticket, no finalize pass; every output is order-independent and bit-stable.
 //
-// Both kernels follow predict_mask_kernel / predict_merge_kernel (resize.hip): a thread owns four consecutive flat pixels,
+// Both kernels follow predict_mask_kernel / predict_merge_kernel (predict.hip): a thread owns four consecutive flat pixels,
 // loads are unconditional with clamped indices, histograms live in LDS as 32-bit counters and a block ends with one 64-bit
 // global atomic per NON-ZERO bin.  A trained network puts most pixels into q = 255, and 64 lanes adding to one LDS word
 // serialise, so the top bin is aggregated per wave before the LDS add: a ballot and a population count, added by one lane.
 // The grid-stride loops are wave-uniform (dead pixels are masked, not skipped) so that every ballot sees the whole wave.
 // A (count, correct) pair is ONE 64-bit LDS word (count in the low half: the layout of the uint32 [..][256][2] view), so
 // a pixel costs one ds_add_u64; no count can carry into the other half because a launch holds fewer than 2^31 pixels.
-#include "common.hpp"
-#include "segk_internal.h"
-#include "../../include/segk.h"
-#include <type_traits>
+#include "predict_common.hpp"
 
 namespace {
-
-// The source index, the two-tap blend and the nearest index of resize.hip, expression for expression: with
-// -ffp-contract=off one source expression gives one bit pattern, which is what lets the sweep at inv_T = 1 agree with
-// segk_predict_merge exactly (tests/test_gpu_calibration.py).
-__device__ __forceinline__ void src_index(int o, float scale, int in_size, int& i0, int& i1, float& lam) {
-  float s = scale * ((float)o + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  lam = s - (float)i0;
-}
-__device__ __forceinline__ float bilerp(float a, float b, float d, float e, float ly, float lx) {
-  return (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e);
-}
-__device__ __forceinline__ int nearest_index(int o, float scale, int in_size) {
-  const int s = (int)floorf((float)o * scale);
-  return s > in_size - 1 ? in_size - 1 : s;
-}
 
 __device__ __forceinline__ bool label_valid(long long l, int C, int ignore_index) {
   return l >= 0 && l < C && !(ignore_index >= 0 && l == ignore_index);
@@ -77,9 +55,9 @@ __global__ __launch_bounds__(256) void calib_hist_kernel(const uint8_t* __restri
 }
 
 // ---- temperature sweep ---------------------------------------------------------------------------------------------------
-// z of the thread's four pixels is sampled once (the 4*NC taps of a pixel in flight together, per-class window origins
-// uniform); the K loop then runs over registers only, inv_T[j] indexed by the loop counter alone (uniform loads).  Classes
-// past C repeat class C-1: they never win the strict comparison, and the sums over classes skip them.
+// z of the thread's four pixels is sampled once with predict_merge_kernel's sampler and argmax (predict_common.hpp: the
+// sweep at inv_T = 1 agrees with segk_predict_merge exactly, tests/test_gpu_calibration.py); the K loop then runs over
+// registers only, inv_T[j] indexed by the loop counter alone (uniform loads).
 // K is a run-time count, so per-temperature sums cannot sit in a register array over the grid-stride loop (an array
 // indexed by j would live in scratch).  Per temperature the four pixels' fixed-point NLL (< 2^36) and their non-finite
 // count (bits 48..) are one 64-bit word per thread, summed over the wave with shuffles and added by one lane to the
@@ -101,9 +79,7 @@ __global__ __launch_bounds__(256) void calib_temps_kernel(const float* __restric
   const int total = oh * ow;
   const float sh = (float)nh / (float)oh, sw = (float)nw / (float)ow;
   const char* wk[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k) wk[k] = (const char*)(slot + ((size_t)(k < C ? k : C - 1) * T + pt) * T + pl);
-  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
+  window_origins<NC>(slot, C, T, pt, pl, wk);
   const unsigned pitch = 4u * (unsigned)T;
   unsigned int nvalid = 0;
   for (long base = (long)blockIdx.x * 256; base * 4 < total; base += (long)gridDim.x * 256) {
@@ -120,33 +96,8 @@ __global__ __launch_bounds__(256) void calib_temps_kernel(const float* __restric
       lab[j] = valid[j] ? (int)l : 0;
       nvalid += valid[j] ? 1u : 0u;
       const int oy = i / ow, ox = i - oy * ow;
-      if (MODE == 1) {
-        const unsigned o = (unsigned)nearest_index(oy, sh, nh) * pitch + 4u * (unsigned)nearest_index(ox, sw, nw);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) z[j][k] = tap(wk[k], o);
-      } else {
-        int y0, y1, x0, x1;
-        float ly, lx;
-        src_index(oy, sh, nh, y0, y1, ly);
-        src_index(ox, sw, nw, x0, x1, lx);
-        const unsigned r0 = (unsigned)y0 * pitch, r1 = (unsigned)y1 * pitch, c0 = 4u * (unsigned)x0, c1 = 4u * (unsigned)x1;
-        float a[NC], b[NC], d[NC], e[NC];
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-          a[k] = tap(wk[k], r0 + c0); b[k] = tap(wk[k], r0 + c1); d[k] = tap(wk[k], r1 + c0); e[k] = tap(wk[k], r1 + c1);
-        }
-#pragma unroll
-        for (int k = 0; k < NC; ++k) z[j][k] = bilerp(a[k], b[k], d[k], e[k], ly, lx);
-      }
-      int bi = 0;
-      float bv = z[j][0];
-#pragma unroll
-      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
-        const bool take = (z[j][k] > bv) | ((z[j][k] != z[j][k]) & (bv == bv));
-        bv = take ? z[j][k] : bv;
-        bi = take ? k : bi;
-      }
-      best[j] = bi;
+      sample_window<NC, MODE>(wk, pitch, oy, ox, sh, sw, nh, nw, z[j]);
+      best[j] = argmax_first<NC>(z[j]);
     }
     for (int t = 0; t < K; ++t) {
       const float it = inv_T[t];                          // uniform
@@ -263,13 +214,7 @@ extern "C" int segk_calib_temps(const float* slot, int C, int T, int pad_top, in
         (const long long*)labels, ignore_index, inv_T_dev, K, (unsigned long long*)hist, (unsigned long long*)nll_fx,
         (unsigned long long*)nonfinite, (unsigned long long*)valid);
   };
-  auto by_mode = [&](auto nc) {
+  return dispatch_classes(C, [&](auto nc) {
     return mode == 0 ? launch(nc, std::integral_constant<int, 0>{}) : launch(nc, std::integral_constant<int, 1>{});
-  };
-  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
-  if (C == 1) return by_mode(std::integral_constant<int, 1>{});
-  if (C == 2) return by_mode(std::integral_constant<int, 2>{});
-  if (C == 3) return by_mode(std::integral_constant<int, 3>{});
-  if (C == 4) return by_mode(std::integral_constant<int, 4>{});
-  return by_mode(std::integral_constant<int, SEGK_MAX_CLASSES>{});
+  });
 }

@@ -1,8 +1,8 @@
 // Mask clean-up on the device: connected components of a uint8 class mask, their statistics and
-// boxes, removal of small / non-largest components by a one-pass neighbour vote, and the colour / count / confusion
-// outputs of a finished mask.  The reference holds no code for this; the arithmetic is this project's definition, every
-// value is an integer and the result is unique, so the device equals the restatement of tests/components_reference.py
-// bit for bit whatever the tiling and the arrival order of the atomics.
+// boxes, and removal of small / non-largest components by a one-pass neighbour vote (the colour / count / confusion
+// outputs of the finished mask are segk_mask_finish, predict.hip).  The reference holds no code for this; the arithmetic
+// is this project's definition, every value is an integer and the result is unique, so the device equals the restatement
+// of tests/components_reference.py bit for bit whatever the tiling and the arrival order of the atomics.
 //
 // A component's name while it is built is its ROOT: the smallest linear index y*W + x among its pixels.  parent[p] <= p
 // always holds and parents only fall, which bounds every loop below (a walk up a chain strictly decreases, a union's
@@ -22,8 +22,6 @@
 //                      then global atomics filtered by a coherent read)
 //  segk_cc_clean
 //   cc_clean_init_kernel, cc_vote_kernel, cc_apply_kernel
-//  segk_mask_finish
-//   mask_finish_kernel the colour / counts / confusion half of predict_mask_kernel (resize.hip), reading a mask
 #include "common.hpp"
 #include "segk_internal.h"
 #include "../../include/segk.h"
@@ -456,78 +454,6 @@ __global__ __launch_bounds__(256) void cc_apply_kernel(const uint8_t* __restrict
   }
 }
 
-// ------------------------------------------------------------------------------------------------ finish from a mask
-// predict_mask_kernel's outputs past the argmax: a thread owns four consecutive pixels (one mask dword in, three colour
-// dwords out), class counts in registers then per wave, confusion counts in an LDS histogram, one 64-bit atomic per
-// non-zero bin per workgroup.  A mask value >= C is coloured black and counted nowhere.
-template <bool LAB>
-__global__ __launch_bounds__(256) void mask_finish_kernel(const uint8_t* __restrict__ mask, uint8_t* __restrict__ color,
-                                                          const uint8_t* __restrict__ palette, u64* __restrict__ counts,
-                                                          const long long* __restrict__ labels, u64* __restrict__ M, int C, int total) {
-  constexpr int NB = NC * NC;
-  __shared__ unsigned int hist[NB + NC];
-  if (threadIdx.x < NB + NC) hist[threadIdx.x] = 0;
-  unsigned pal[NC], cnt[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    pal[k] = 0; cnt[k] = 0;
-    if (color && k < C) {
-      const uint8_t* q = palette + 3 * k;
-      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-    }
-  }
-  __syncthreads();
-  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
-    const int p = (int)(q * 4);
-    const bool full = p + 3 < total;
-    unsigned w;
-    if (full) w = *(const uint32_t*)(mask + (unsigned)p);
-    else {
-      w = 0;
-      for (int j = 0; j < 4; ++j)
-        if (p + j < total) w |= (unsigned)mask[p + j] << (8 * j);
-    }
-    long long lab[4];
-    if (LAB) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
-    }
-    unsigned c4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int v = (w >> (8 * j)) & 255;
-      const bool live = p + j < total && v < C;
-      c4[j] = 0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        cnt[k] += (live && v == k) ? 1u : 0u;
-        c4[j] = (v == k) ? pal[k] : c4[j];
-      }
-      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[v * NC + (int)lab[j]], 1u);
-    }
-    if (color) {
-      if (full)
-        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
-      else
-        for (int j = 0; j < 4; ++j)
-          if (p + j < total)
-            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
-    }
-  }
-  if (counts) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      unsigned c = cnt[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
-    }
-  }
-  __syncthreads();
-  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (u64)hist[threadIdx.x]);
-  if (counts && threadIdx.x >= NB && threadIdx.x < NB + NC && hist[threadIdx.x]) atomicAdd(&counts[threadIdx.x - NB], (u64)hist[threadIdx.x]);
-}
-
 int flat_grid(long items) {
   long g = (items + 255) / 256;
   const long cap = 8L * segk_num_cus();
@@ -586,28 +512,5 @@ extern "C" int segk_cc_clean(const uint8_t* mask, uint8_t* out, int32_t* ws, int
   hipLaunchKernelGGL(cc_apply_kernel, dim3(g), dim3(256), 0, st, mask, out, ws, kept, new_cls, H, W, min_area, (unsigned)keep_mask,
                      max_components);
   SEGK_CHECK_LAUNCH("cc_clean");
-  return 0;
-}
-
-extern "C" int segk_mask_finish(const uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels,
-                                uint64_t* M, int C, int H, int W, segk_stream_t s) {
-  SEGK_REQUIRE(mask && H >= 1 && W >= 1, "mask_finish: bad shape");
-  SEGK_REQUIRE(C >= 1 && C <= SEGK_MAX_CLASSES, "mask_finish: 1..%d classes supported, got %d", SEGK_MAX_CLASSES, C);
-  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "mask_finish: color and palette come together");
-  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "mask_finish: labels and M come together");
-  SEGK_REQUIRE(color || counts || M, "mask_finish: no output asked for");
-  SEGK_REQUIRE((long)H * W < (1L << 31) - 4, "mask_finish: mask too large for 32-bit offsets");
-  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0, "mask_finish: mask and color must be 4-byte aligned");
-  long g = (((long)H * W + 3) / 4 + 255) / 256;
-  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;      // as segk_predict_mask: few blocks end in atomics
-  if (g > cap) g = cap;
-  hipStream_t st = (hipStream_t)s;
-  if (labels)
-    hipLaunchKernelGGL(mask_finish_kernel<true>, dim3((int)g), dim3(256), 0, st, mask, color, palette, (u64*)counts, (const long long*)labels,
-                       (u64*)M, C, H * W);
-  else
-    hipLaunchKernelGGL(mask_finish_kernel<false>, dim3((int)g), dim3(256), 0, st, mask, color, palette, (u64*)counts, (const long long*)labels,
-                       (u64*)M, C, H * W);
-  SEGK_CHECK_LAUNCH("mask_finish");
   return 0;
 }

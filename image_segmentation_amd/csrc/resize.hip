@@ -1,24 +1,13 @@
 // Bilinear resize of NHWC tensors, align_corners=False -- the skip-feature up-sampling of the CLIP decoder
 // (reference clip/clipunet.py:99-100: F.interpolate(skip, size=x.shape[2:], mode='bilinear',
 // align_corners=False); always taken: 14x14 -> 28/56/112/224).  Source index follows ATen's
-// area_pixel_compute_source_index: src = scale*(dst+0.5)-0.5, clamped at 0; x1 = min(x0+1, in-1).
+// area_pixel_compute_source_index: src = scale*(dst+0.5)-0.5, clamped at 0; x1 = min(x0+1, in-1) (src_index,
+// predict_common.hpp: the prediction finishers blend with the same expressions).
 // Forward: one thread per output pixel x 16-byte channel vector.  Backward: a GATHER (one thread per INPUT
 // pixel x channel vector walks the output pixels that reference it) -- deterministic, no atomics.
-#include "common.hpp"
-#include "segk_internal.h"
-#include "../../include/segk.h"
-#include <type_traits>
+#include "predict_common.hpp"
 
 namespace {
-
-__device__ __forceinline__ void src_index(int o, float scale, int in_size, int& i0, int& i1, float& lam) {
-  float s = scale * ((float)o + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  lam = s - (float)i0;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int IH,
@@ -219,8 +208,8 @@ extern "C" int segk_bilinear_bwd(const void* dy, void* dx, float* scratch, int B
 // mode "nearest": src = min(floor(o*scale), in-1).
 // crop_resize: slot [C,T,T] -> crop the (nh,nw) window -> [C,oh,ow] with F.interpolate bilinear
 // (align_corners=False, no anti-aliasing) or nearest (utils.py:51-75).
-// resize_pad_u8 / predict_mask: the same two steps for prediction (reference segmentation_webapp/app.py:250-326): an 8-bit
-// interleaved image straight into its slot, and slot -> class mask + colour image without the full-size logits.
+// resize_pad_u8: the first step for prediction (reference segmentation_webapp/app.py:250-326): an 8-bit interleaved image
+// straight into its slot.  The way back, slot -> class mask + colour image without the full-size logits, is predict.hip.
 namespace {
 
 struct AA {
@@ -249,18 +238,6 @@ __device__ __forceinline__ float aa_w(const AA& a, int j) {
   const float x = fabsf(((float)(j + a.lo) - a.center + 0.5f) * a.inv);
   const float w = x < 1.f ? 1.f - x : 0.f;
   return a.total != 0.f ? w / a.total : w;
-}
-
-// The two-tap blend and the nearest source index of F.interpolate, shared by every kernel below: with -ffp-contract=off
-// one source expression gives one bit pattern, which is what lets the fused prediction kernel agree with crop_resize
-// exactly (tests/test_gpu_inference.py).
-__device__ __forceinline__ float bilerp(float a, float b, float d, float e, float ly, float lx) {
-  // ATen: (1-ly)*((1-lx)*a + lx*b) + ly*((1-lx)*d + lx*e)
-  return (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e);
-}
-__device__ __forceinline__ int nearest_index(int o, float scale, int in_size) {
-  const int s = (int)floorf((float)o * scale);
-  return s > in_size - 1 ? in_size - 1 : s;
 }
 
 // One output pixel (oy, ox) of the resize of an (H, W) image, N channels at a time; ld(y, x, v) fetches the N source
@@ -386,135 +363,6 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const float* __restric
   }
 }
 
-// Prediction: slot [C,T,T] -> crop + resize (the arithmetic of crop_resize_kernel) -> argmax over classes (first maximum,
-// NaN maximal: confusion_kernel / torch.argmax) -> uint8 mask [oh,ow], optional RGB [oh,ow,3], class counts and confusion
-// counts.  The full-size logits are never stored: 1 + 3 bytes leave per pixel where crop_resize + argmax + palette
-// index move ~50, and the source is a C*T*T*4-byte slot that stays in L2.
-// A thread owns four consecutive FLAT pixels p = oy*ow + ox, p % 4 == 0: the mask leaves as one aligned dword, the colour
-// as three; a thread may straddle a row end, so (oy, ox) advance per pixel.  Loads are unconditional with clamped
-// indices (pixels past the end repeat the last one, classes past C repeat class C-1 and can never win the strict
-// comparison), so the 4*NC taps of a pixel are in flight together.  Class counts live in registers over the grid-stride
-// loop and are summed per wave, confusion counts go to an LDS histogram; a block ends with one 64-bit atomic per non-zero
-// bin (integers: order-independent, bit-stable).
-template <int NC, int MODE, bool LAB>
-__global__ __launch_bounds__(256) void predict_mask_kernel(const float* __restrict__ slot, uint8_t* __restrict__ mask,
-                                                           uint8_t* __restrict__ color, const uint8_t* __restrict__ palette,
-                                                           unsigned long long* __restrict__ counts,
-                                                           const long long* __restrict__ labels, unsigned long long* __restrict__ M,
-                                                           int C, int T, int pt, int pl, int nh, int nw, int oh, int ow) {
-  constexpr int NB = SEGK_MAX_CLASSES * SEGK_MAX_CLASSES;
-  __shared__ unsigned int hist[NB + SEGK_MAX_CLASSES];            // confusion bins, then class counts
-  if (threadIdx.x < NB + SEGK_MAX_CLASSES) hist[threadIdx.x] = 0;
-  unsigned int pal[NC], cnt[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k) { pal[k] = 0; cnt[k] = 0; }
-  if (color) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      const uint8_t* q = palette + 3 * (k < C ? k : C - 1);
-      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-    }
-  }
-  __syncthreads();
-  const int total = oh * ow;
-  const float sh = (float)nh / (float)oh, sw = (float)nw / (float)ow;
-  // per-class window origins are uniform (scalar registers); a tap is origin + a 32-bit BYTE offset, the addressing form
-  // that costs no 64-bit vector arithmetic per load
-  const char* wk[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k) wk[k] = (const char*)(slot + ((size_t)(k < C ? k : C - 1) * T + pt) * T + pl);
-  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
-  const unsigned pitch = 4u * (unsigned)T;
-  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
-    const int p = (int)(q * 4);
-    long long lab[4];
-    if (LAB) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
-    }
-    int oy = p / ow, ox = p - oy * ow;
-    // the row's taps change only where the thread steps over a row end
-    int y0, y1;
-    float ly = 0.f;
-    auto row_taps = [&]() {
-      if (MODE == 1) y0 = y1 = nearest_index(oy, sh, nh);
-      else src_index(oy, sh, nh, y0, y1, ly);
-    };
-    row_taps();
-    int best[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float v[NC];
-      if (MODE == 1) {
-        const unsigned o = (unsigned)y0 * pitch + 4u * (unsigned)nearest_index(ox, sw, nw);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) v[k] = tap(wk[k], o);
-      } else {
-        int x0, x1;
-        float lx;
-        src_index(ox, sw, nw, x0, x1, lx);
-        const unsigned r0 = (unsigned)y0 * pitch, r1 = (unsigned)y1 * pitch, c0 = 4u * (unsigned)x0, c1 = 4u * (unsigned)x1;
-        float a[NC], b[NC], d[NC], e[NC];
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-          a[k] = tap(wk[k], r0 + c0); b[k] = tap(wk[k], r0 + c1); d[k] = tap(wk[k], r1 + c0); e[k] = tap(wk[k], r1 + c1);
-        }
-#pragma unroll
-        for (int k = 0; k < NC; ++k) v[k] = bilerp(a[k], b[k], d[k], e[k], ly, lx);
-      }
-      int bi = 0;
-      float bv = v[0];
-#pragma unroll
-      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
-        const bool take = (v[k] > bv) | ((v[k] != v[k]) & (bv == bv));
-        bv = take ? v[k] : bv;
-        bi = take ? k : bi;
-      }
-      best[j] = bi;
-      if (p + j + 1 < total && ++ox == ow) { ox = 0; ++oy; row_taps(); }
-    }
-    const bool full = p + 3 < total;
-    unsigned int c4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const unsigned live = p + j < total ? 1u : 0u;
-      c4[j] = 0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        cnt[k] += best[j] == k ? live : 0u;
-        c4[j] = best[j] == k ? pal[k] : c4[j];
-      }
-      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[best[j] * SEGK_MAX_CLASSES + (int)lab[j]], 1u);
-    }
-    if (full) {
-      *(uint32_t*)(mask + (unsigned)p) = (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
-      if (color)
-        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
-    } else {
-      for (int j = 0; j < 4; ++j)
-        if (p + j < total) {
-          mask[p + j] = (uint8_t)best[j];
-          if (color)
-            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
-        }
-    }
-  }
-  if (counts) {   // wave sums first: 64 lanes adding to one LDS word serialise
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      unsigned int c = cnt[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
-    }
-  }
-  __syncthreads();
-  // integer sums: one 64-bit atomic per non-zero bin per block, order-independent and bit-stable
-  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-  if (counts && threadIdx.x >= NB && threadIdx.x < NB + SEGK_MAX_CLASSES && hist[threadIdx.x])
-    atomicAdd(&counts[threadIdx.x - NB], (unsigned long long)hist[threadIdx.x]);
-}
-
 }  // namespace
 
 static int resize_pad_launch(const void* img, void* out, int C, int H, int W, int nh, int nw, int T, int pad_top, int pad_left,
@@ -595,275 +443,4 @@ extern "C" int segk_resize_pad_u8_flip(const uint8_t* img_hwc, float* out, int C
                                        int pad_top, int pad_left, int mode, int flip, segk_stream_t s) {
   SEGK_REQUIRE(flip >= 0 && flip <= 3, "resize_pad_u8_flip: flip is 0..3 (bit 0: x, bit 1: y), got %d", flip);
   return resize_pad_u8_launch(img_hwc, out, Cin, H, W, nh, nw, T, pad_top, pad_left, mode, flip, s);
-}
-
-extern "C" int segk_predict_mask(const float* slot, uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts,
-                                 const int64_t* labels, uint64_t* M, int C, int T, int pad_top, int pad_left, int nh, int nw,
-                                 int oh, int ow, int mode, segk_stream_t s) {
-  SEGK_REQUIRE(slot && mask && T > 0 && nh > 0 && nw > 0 && oh > 0 && ow > 0, "predict_mask: bad shape");
-  SEGK_REQUIRE(C >= 1 && C <= SEGK_MAX_CLASSES, "predict_mask: 1..%d classes supported, got %d", SEGK_MAX_CLASSES, C);
-  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "predict_mask: color and palette come together");
-  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "predict_mask: labels and M come together");
-  SEGK_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + nh <= T && pad_left + nw <= T, "predict_mask: window outside the slot");
-  SEGK_REQUIRE(mode == 0 || mode == 1, "predict_mask: bad mode %d", mode);
-  SEGK_REQUIRE((long)T * T < (1L << 30) && (long)oh * ow < (1L << 31) - 4, "predict_mask: slot or output too large for 32-bit offsets");
-  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0, "predict_mask: mask and color must be 4-byte aligned");
-  long g = (((long)oh * ow + 3) / 4 + 255) / 256;
-  // Block cap: the neighbours' 16384 for the mask / colour alone.  With counts or labels every block ends in 64-bit atomics
-  // on the same few words, and those serialise in L2 at ~12 ns per block (measured: 11719 blocks at 3000x4000 took 150 us
-  // against 30 us without the counts), so the grid becomes persistent: three blocks per CU, one resident round for every
-  // instance (the 8-class bilinear one fits three), 17 us at 1200x1600 and 36-42 us at 3000x4000.
-  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;
-  if (g > cap) g = cap;
-  hipStream_t st = (hipStream_t)s;
-  auto launch = [&](auto nc, auto md, auto lab) {
-    hipLaunchKernelGGL((predict_mask_kernel<decltype(nc)::value, decltype(md)::value, decltype(lab)::value>), dim3((int)g), dim3(256), 0,
-                       st, slot, mask, color, palette, (unsigned long long*)counts, (const long long*)labels, (unsigned long long*)M, C,
-                       T, pad_top, pad_left, nh, nw, oh, ow);
-  };
-  auto by_lab = [&](auto nc, auto md) {
-    if (labels) launch(nc, md, std::true_type{});
-    else launch(nc, md, std::false_type{});
-  };
-  auto by_mode = [&](auto nc) {
-    if (mode == 0) by_lab(nc, std::integral_constant<int, 0>{});
-    else by_lab(nc, std::integral_constant<int, 1>{});
-  };
-  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
-  if (C == 1) by_mode(std::integral_constant<int, 1>{});
-  else if (C == 2) by_mode(std::integral_constant<int, 2>{});
-  else if (C == 3) by_mode(std::integral_constant<int, 3>{});
-  else if (C == 4) by_mode(std::integral_constant<int, 4>{});
-  else by_mode(std::integral_constant<int, SEGK_MAX_CLASSES>{});
-  SEGK_CHECK_LAUNCH("predict_mask");
-  return 0;
-}
-
-// ---- multi-view prediction: V views of one image -> one mask ---------------------------------------------
-// predict_mask_kernel with an accumulator: a thread owns four consecutive flat pixels and walks the views in table order
-// over acc[4][NC]; per view it samples the view's window at the FLIPPED pixel with the arithmetic of crop_resize_kernel
-// (clamped indices, unconditional loads: the 4*NC taps of a pixel are in flight together), turns logits into probabilities
-// where the merge asks for it, and adds weight * s.  A view's descriptor is indexed by the loop counter alone, so it is
-// read with uniform loads into scalar registers, and its per-class window origins are scalar too.  The slots (V*C*T*T*4
-// bytes) stay in L2; 1 + 3 + 1 bytes leave per pixel.  Classes past C repeat class C-1, as in predict_mask_kernel: they
-// never win the strict comparison, and the sums over classes skip them.
-namespace {
-
-template <int NC>
-__device__ __forceinline__ void softmax_classes(float (&z)[NC], int C) {
-  // m = max z, e_k = expf(z_k - m), p_k = e_k / sum_k e_k, the sum in class order
-  float m = z[0];
-#pragma unroll
-  for (int k = 1; k < NC; ++k) m = z[k] > m ? z[k] : m;
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    z[k] = expf(z[k] - m);
-    sum = sum + ((NC <= 4 || k < C) ? z[k] : 0.f);
-  }
-#pragma unroll
-  for (int k = 0; k < NC; ++k) z[k] = z[k] / sum;
-}
-
-template <int NC, int MODE, bool LAB>
-__global__ __launch_bounds__(256) void predict_merge_kernel(const segk_view_desc* __restrict__ views, int V, int C, int merge,
-                                                            int oh, int ow, uint8_t* __restrict__ mask, uint8_t* __restrict__ color,
-                                                            const uint8_t* __restrict__ palette,
-                                                            unsigned long long* __restrict__ counts,
-                                                            const long long* __restrict__ labels, unsigned long long* __restrict__ M,
-                                                            uint8_t* __restrict__ conf, float* __restrict__ scores) {
-  constexpr int NB = SEGK_MAX_CLASSES * SEGK_MAX_CLASSES;
-  __shared__ unsigned int hist[NB + SEGK_MAX_CLASSES];            // confusion bins, then class counts
-  if (threadIdx.x < NB + SEGK_MAX_CLASSES) hist[threadIdx.x] = 0;
-  unsigned int pal[NC], cnt[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k) { pal[k] = 0; cnt[k] = 0; }
-  if (color) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      const uint8_t* q = palette + 3 * (k < C ? k : C - 1);
-      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-    }
-  }
-  __syncthreads();
-  const int total = oh * ow;
-  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
-  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
-    const int p = (int)(q * 4);
-    long long lab[4];
-    if (LAB) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
-    }
-    // the thread's four pixels (one past the end repeats the last); a thread may straddle a row end
-    int oy[4], ox[4];
-    oy[0] = p / ow; ox[0] = p - oy[0] * ow;
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-      oy[j] = oy[j - 1]; ox[j] = ox[j - 1];
-      if (p + j < total && ++ox[j] == ow) { ox[j] = 0; ++oy[j]; }
-    }
-    float acc[4][NC];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int k = 0; k < NC; ++k) acc[j][k] = 0.f;
-    for (int v = 0; v < V; ++v) {                                  // fixed order: the order is part of the result
-      const segk_view_desc d = views[v];                           // uniform: scalar loads
-      const float sh = (float)d.nh / (float)oh, sw = (float)d.nw / (float)ow;
-      const char* wk[NC];
-#pragma unroll
-      for (int k = 0; k < NC; ++k)
-        wk[k] = (const char*)((const float*)d.slot + ((size_t)(k < C ? k : C - 1) * d.T + d.pad_top) * d.T + d.pad_left);
-      const unsigned pitch = 4u * (unsigned)d.T;
-      const bool soft = merge == SEGK_MERGE_PROB && d.kind == 0;
-      const float wt = d.weight;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sy = (d.flip & 2) ? oh - 1 - oy[j] : oy[j], sx = (d.flip & 1) ? ow - 1 - ox[j] : ox[j];
-        float z[NC];
-        if (MODE == 1) {
-          const unsigned o = (unsigned)nearest_index(sy, sh, d.nh) * pitch + 4u * (unsigned)nearest_index(sx, sw, d.nw);
-#pragma unroll
-          for (int k = 0; k < NC; ++k) z[k] = tap(wk[k], o);
-        } else {
-          int y0, y1, x0, x1;
-          float ly, lx;
-          src_index(sy, sh, d.nh, y0, y1, ly);
-          src_index(sx, sw, d.nw, x0, x1, lx);
-          const unsigned r0 = (unsigned)y0 * pitch, r1 = (unsigned)y1 * pitch, c0 = 4u * (unsigned)x0, c1 = 4u * (unsigned)x1;
-          float a[NC], b[NC], e[NC], f[NC];
-#pragma unroll
-          for (int k = 0; k < NC; ++k) {
-            a[k] = tap(wk[k], r0 + c0); b[k] = tap(wk[k], r0 + c1); e[k] = tap(wk[k], r1 + c0); f[k] = tap(wk[k], r1 + c1);
-          }
-#pragma unroll
-          for (int k = 0; k < NC; ++k) z[k] = bilerp(a[k], b[k], e[k], f[k], ly, lx);
-        }
-        if (soft) softmax_classes<NC>(z, C);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) acc[j][k] = acc[j][k] + wt * z[k];
-      }
-    }
-    const bool full = p + 3 < total;
-    int best[4];
-    unsigned int c4[4], cf[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int bi = 0;
-      float bv = acc[j][0];
-#pragma unroll
-      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
-        const bool take = (acc[j][k] > bv) | ((acc[j][k] != acc[j][k]) & (bv == bv));
-        bv = take ? acc[j][k] : bv;
-        bi = take ? k : bi;
-      }
-      best[j] = bi;
-      const unsigned live = p + j < total ? 1u : 0u;
-      c4[j] = 0; cf[j] = 0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        cnt[k] += bi == k ? live : 0u;
-        c4[j] = bi == k ? pal[k] : c4[j];
-      }
-      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[bi * SEGK_MAX_CLASSES + (int)lab[j]], 1u);
-      if (conf || scores) {                               // p = acc / sum acc (prob) or softmax(acc) (logit)
-        float pr[NC];
-#pragma unroll
-        for (int k = 0; k < NC; ++k) pr[k] = acc[j][k];
-        if (merge == SEGK_MERGE_PROB) {
-          float sum = 0.f;
-#pragma unroll
-          for (int k = 0; k < NC; ++k) sum = sum + ((NC <= 4 || k < C) ? pr[k] : 0.f);
-#pragma unroll
-          for (int k = 0; k < NC; ++k) pr[k] = pr[k] / sum;
-        } else {
-          softmax_classes<NC>(pr, C);
-        }
-        float pb = pr[0];
-#pragma unroll
-        for (int k = 1; k < NC; ++k) pb = bi == k ? pr[k] : pb;
-        const float c = 255.f * pb + 0.5f;
-        cf[j] = c >= 0.f ? (unsigned)(c > 255.f ? 255.f : c) : 0u;     // a NaN confidence is stored as 0
-        if (scores && live) {
-#pragma unroll
-          for (int k = 0; k < NC; ++k)
-            if (NC <= 4 || k < C) scores[(size_t)k * total + (unsigned)(p + j)] = pr[k];
-        }
-      }
-    }
-    if (full) {
-      *(uint32_t*)(mask + (unsigned)p) = (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
-      if (conf) *(uint32_t*)(conf + (unsigned)p) = cf[0] | (cf[1] << 8) | (cf[2] << 16) | (cf[3] << 24);
-      if (color)
-        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
-    } else {
-      for (int j = 0; j < 4; ++j)
-        if (p + j < total) {
-          mask[p + j] = (uint8_t)best[j];
-          if (conf) conf[p + j] = (uint8_t)cf[j];
-          if (color)
-            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
-        }
-    }
-  }
-  if (counts) {   // wave sums first: 64 lanes adding to one LDS word serialise
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      unsigned int c = cnt[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
-    }
-  }
-  __syncthreads();
-  // integer sums: one 64-bit atomic per non-zero bin per block, order-independent and bit-stable
-  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-  if (counts && threadIdx.x >= NB && threadIdx.x < NB + SEGK_MAX_CLASSES && hist[threadIdx.x])
-    atomicAdd(&counts[threadIdx.x - NB], (unsigned long long)hist[threadIdx.x]);
-}
-
-}  // namespace
-
-static_assert(sizeof(segk_view_desc) == 48, "segk_view_desc is 48 bytes (image_segmentation_amd/tta.py: VIEW_DESC)");
-
-extern "C" int segk_predict_merge(const void* views_dev, int V, int C, int merge, int mode, int oh, int ow, uint8_t* mask,
-                                  uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels, uint64_t* M,
-                                  uint8_t* conf, float* scores, segk_stream_t s) {
-  SEGK_REQUIRE(views_dev && mask && oh > 0 && ow > 0, "predict_merge: bad shape");
-  SEGK_REQUIRE(V >= 1 && V <= SEGK_MAX_VIEWS, "predict_merge: 1..%d views supported, got %d", SEGK_MAX_VIEWS, V);
-  SEGK_REQUIRE(C >= 1 && C <= SEGK_MAX_CLASSES, "predict_merge: 1..%d classes supported, got %d", SEGK_MAX_CLASSES, C);
-  SEGK_REQUIRE(merge == SEGK_MERGE_PROB || merge == SEGK_MERGE_LOGIT, "predict_merge: bad merge %d", merge);
-  SEGK_REQUIRE(mode == 0 || mode == 1, "predict_merge: bad mode %d", mode);
-  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "predict_merge: color and palette come together");
-  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "predict_merge: labels and M come together");
-  SEGK_REQUIRE((long)oh * ow < (1L << 31) - 4, "predict_merge: output too large for 32-bit offsets");
-  SEGK_REQUIRE(((uintptr_t)views_dev & 15) == 0, "predict_merge: the view table must be 16-byte aligned");
-  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)conf & 3) == 0 && ((uintptr_t)scores & 3) == 0,
-               "predict_merge: mask, color, conf and scores must be 4-byte aligned");
-  long g = (((long)oh * ow + 3) / 4 + 255) / 256;
-  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;      // as segk_predict_mask: few blocks end in atomics
-  if (g > cap) g = cap;
-  hipStream_t st = (hipStream_t)s;
-  auto launch = [&](auto nc, auto md, auto lab) {
-    hipLaunchKernelGGL((predict_merge_kernel<decltype(nc)::value, decltype(md)::value, decltype(lab)::value>), dim3((int)g), dim3(256), 0,
-                       st, (const segk_view_desc*)views_dev, V, C, merge, oh, ow, mask, color, palette, (unsigned long long*)counts,
-                       (const long long*)labels, (unsigned long long*)M, conf, scores);
-  };
-  auto by_lab = [&](auto nc, auto md) {
-    if (labels) launch(nc, md, std::true_type{});
-    else launch(nc, md, std::false_type{});
-  };
-  auto by_mode = [&](auto nc) {
-    if (mode == 0) by_lab(nc, std::integral_constant<int, 0>{});
-    else by_lab(nc, std::integral_constant<int, 1>{});
-  };
-  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
-  if (C == 1) by_mode(std::integral_constant<int, 1>{});
-  else if (C == 2) by_mode(std::integral_constant<int, 2>{});
-  else if (C == 3) by_mode(std::integral_constant<int, 3>{});
-  else if (C == 4) by_mode(std::integral_constant<int, 4>{});
-  else by_mode(std::integral_constant<int, SEGK_MAX_CLASSES>{});
-  SEGK_CHECK_LAUNCH("predict_merge");
-  return 0;
 }

@@ -4,10 +4,7 @@
 // No resampling anywhere: a tile pixel IS an image pixel.  The tile plan is derived in the kernels from (L, T, overlap)
 // per axis (image_segmentation_amd/tiles.py: tile_axis is the same arithmetic): stride s = T - overlap;
 //   L <= T: one tile at -((T - L) / 2);   L > T: n = ceil((L - T) / s) + 1 tiles at min(i s, L - T).
-#include <type_traits>
-
-#include "../../include/segk.h"
-#include "segk_internal.h"
+#include "predict_common.hpp"
 
 namespace {
 
@@ -139,23 +136,6 @@ __global__ __launch_bounds__(256) void tile_gather_kernel(const float* __restric
 }
 
 // ---- blend ---------------------------------------------------------------------------------------------------------------
-// m = max z, e_k = expf(z_k - m), p_k = e_k / sum_k e_k, the sum in class order: the source expression of resize.hip's
-// softmax_classes, so one input gives one bit pattern in both kernels
-template <int NC>
-__device__ __forceinline__ void softmax_classes(float (&z)[NC], int C) {
-  float m = z[0];
-#pragma unroll
-  for (int k = 1; k < NC; ++k) m = z[k] > m ? z[k] : m;
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    z[k] = expf(z[k] - m);
-    sum = sum + ((NC <= 4 || k < C) ? z[k] : 0.f);
-  }
-#pragma unroll
-  for (int k = 0; k < NC; ++k) z[k] = z[k] / sum;
-}
-
 // The regular tiles (0 .. n - 2, origin i s) that cover coordinate g are ilo .. ihi, at most two because T <= 2 s: with
 // q = g / s tile q covers g (q s <= g < q s + s <= q s + T), tile q - 1 does when (q - 1) s + T - 1 >= g, and tile q - 2
 // never ((q - 2) s + T - 1 >= g would need T > 2 s).  None when ihi < ilo (n == 1, or g beyond the regular tiles).
@@ -176,12 +156,12 @@ __device__ __forceinline__ bool candidate(const Axis& a, int T, int c, int g, in
   return covers;
 }
 
-// predict_merge_kernel's skeleton (resize.hip) with tiles for views: a thread owns four consecutive flat pixels and walks
-// the at most 3 x 3 candidate tiles of each in row-major tile order over acc[4][NC].  A candidate that covers none of the
+// predict_merge_kernel (predict.hip) with tiles for views, ending in the same MaskSink: a thread walks the at most 3 x 3
+// candidate tiles of each of its four pixels in row-major tile order over acc[4][NC].  A candidate that covers none of the
 // wave's pixels is skipped by a wave-uniform branch; otherwise its NC values are loaded unconditionally at clamped indices
 // and a tile that does not cover the pixel is dropped with a SELECT, never through a zero weight: Y may hold NaN wherever no
-// pixel maps.  Weights are integers below 2^24 (exact in fp32), Wtot is exact.  Classes past C repeat class C - 1 and can
-// never win the strict comparison; sums over classes skip them.
+// pixel maps.  Weights are integers below 2^24 (exact in fp32), Wtot is exact.  Classes past C repeat class C - 1, as in
+// the window sampler.
 template <int NC, bool LAB>
 __global__ __launch_bounds__(256) void predict_tiles_kernel(const float* __restrict__ Y, int C, int kind, int merge, int window, int H,
                                                             int W, int T, Axis ay, Axis ax, uint8_t* __restrict__ mask,
@@ -189,42 +169,21 @@ __global__ __launch_bounds__(256) void predict_tiles_kernel(const float* __restr
                                                             unsigned long long* __restrict__ counts,
                                                             const long long* __restrict__ labels, unsigned long long* __restrict__ M,
                                                             uint8_t* __restrict__ conf, float* __restrict__ scores) {
-  constexpr int NB = SEGK_MAX_CLASSES * SEGK_MAX_CLASSES;
-  __shared__ unsigned int hist[NB + SEGK_MAX_CLASSES];            // confusion bins, then class counts
-  if (threadIdx.x < NB + SEGK_MAX_CLASSES) hist[threadIdx.x] = 0;
-  unsigned int pal[NC], cnt[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k) { pal[k] = 0; cnt[k] = 0; }
-  if (color) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      const uint8_t* q = palette + 3 * (k < C ? k : C - 1);
-      pal[k] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-    }
-  }
-  __syncthreads();
+  using Sink = MaskSink<NC, LAB>;
+  __shared__ unsigned int hist[Sink::HIST];
+  typename Sink::Regs regs;
   const int total = H * W;
+  Sink sink(regs, hist, mask, color, palette, counts, labels, M, conf, scores, C, total);
   const unsigned TT4 = 4u * (unsigned)T * (unsigned)T;            // bytes of one class plane; all of Y is below 2^32 bytes
   unsigned koff[NC];
 #pragma unroll
   for (int k = 0; k < NC; ++k) koff[k] = (unsigned)(k < C ? k : C - 1) * TT4;
   const bool soft = merge == SEGK_MERGE_PROB && kind == 0;
-  auto tap = [](const char* origin, unsigned byte_off) { return *(const float*)(origin + byte_off); };
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q * 4 < total; q += (long)gridDim.x * 256) {
     const int p = (int)(q * 4);
-    long long lab[4];
-    if (LAB) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) lab[j] = labels[(unsigned)(p + j < total ? p + j : total - 1)];
-    }
-    // the thread's four pixels (one past the end repeats the last); a thread may straddle a row end
+    sink.begin(p);
     int oy[4], ox[4];
-    oy[0] = p / W; ox[0] = p - oy[0] * W;
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-      oy[j] = oy[j - 1]; ox[j] = ox[j - 1];
-      if (p + j < total && ++ox[j] == W) { ox[j] = 0; ++oy[j]; }
-    }
+    four_pixels(p, total, W, oy, ox);
     int ylo[4], yhi[4], xlo[4], xhi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -276,82 +235,11 @@ __global__ __launch_bounds__(256) void predict_tiles_kernel(const float* __restr
 #pragma unroll
         for (int k = 0; k < NC; ++k) acc[j][k] = acc[j][k] / wtot[j];
     }
-    const bool full = p + 3 < total;
-    int best[4];
-    unsigned int c4[4], cf[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int bi = 0;
-      float bv = acc[j][0];
-#pragma unroll
-      for (int k = 1; k < NC; ++k) {                      // selects, not branches: NaN counts as maximal, like torch
-        const bool take = (acc[j][k] > bv) | ((acc[j][k] != acc[j][k]) & (bv == bv));
-        bv = take ? acc[j][k] : bv;
-        bi = take ? k : bi;
-      }
-      best[j] = bi;
-      const unsigned live = p + j < total ? 1u : 0u;
-      c4[j] = 0; cf[j] = 0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        cnt[k] += bi == k ? live : 0u;
-        c4[j] = bi == k ? pal[k] : c4[j];
-      }
-      if (LAB && live && lab[j] >= 0 && lab[j] < C) atomicAdd(&hist[bi * SEGK_MAX_CLASSES + (int)lab[j]], 1u);
-      if (conf || scores) {                               // p = acc / sum acc (prob) or softmax(a) (logit)
-        float pr[NC];
-#pragma unroll
-        for (int k = 0; k < NC; ++k) pr[k] = acc[j][k];
-        if (merge == SEGK_MERGE_PROB) {
-          float sum = 0.f;
-#pragma unroll
-          for (int k = 0; k < NC; ++k) sum = sum + ((NC <= 4 || k < C) ? pr[k] : 0.f);
-#pragma unroll
-          for (int k = 0; k < NC; ++k) pr[k] = pr[k] / sum;
-        } else {
-          softmax_classes<NC>(pr, C);
-        }
-        float pb = pr[0];
-#pragma unroll
-        for (int k = 1; k < NC; ++k) pb = bi == k ? pr[k] : pb;
-        const float c = 255.f * pb + 0.5f;
-        cf[j] = c >= 0.f ? (unsigned)(c > 255.f ? 255.f : c) : 0u;     // a NaN confidence is stored as 0
-        if (scores && live) {
-#pragma unroll
-          for (int k = 0; k < NC; ++k)
-            if (NC <= 4 || k < C) scores[(size_t)k * total + (unsigned)(p + j)] = pr[k];
-        }
-      }
-    }
-    if (full) {
-      *(uint32_t*)(mask + (unsigned)p) = (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
-      if (conf) *(uint32_t*)(conf + (unsigned)p) = cf[0] | (cf[1] << 8) | (cf[2] << 16) | (cf[3] << 24);
-      if (color)
-        *(uint3*)(color + (size_t)p * 3) = make_uint3(c4[0] | (c4[1] << 24), (c4[1] >> 8) | (c4[2] << 16), (c4[2] >> 16) | (c4[3] << 8));
-    } else {
-      for (int j = 0; j < 4; ++j)
-        if (p + j < total) {
-          mask[p + j] = (uint8_t)best[j];
-          if (conf) conf[p + j] = (uint8_t)cf[j];
-          if (color)
-            for (int b = 0; b < 3; ++b) color[(size_t)(p + j) * 3 + b] = (uint8_t)(c4[j] >> (8 * b));
-        }
-    }
+    for (int j = 0; j < 4; ++j) sink.merged(j, acc[j], merge);
+    sink.store();
   }
-  if (counts) {   // wave sums first: 64 lanes adding to one LDS word serialise
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      unsigned int c = cnt[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hist[NB + k], c);
-    }
-  }
-  __syncthreads();
-  // integer sums: one 64-bit atomic per non-zero bin per block, order-independent and bit-stable
-  if (LAB && threadIdx.x < NB && hist[threadIdx.x]) atomicAdd(&M[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-  if (counts && threadIdx.x >= NB && threadIdx.x < NB + SEGK_MAX_CLASSES && hist[threadIdx.x])
-    atomicAdd(&counts[threadIdx.x - NB], (unsigned long long)hist[threadIdx.x]);
+  sink.finish();
 }
 
 // the checks the three entries share: the plan's scalars, before anything is derived from them
@@ -433,17 +321,13 @@ extern "C" int segk_predict_tiles(const float* Y, int C, int kind, int merge, in
   SEGK_REQUIRE(!(merge == SEGK_MERGE_LOGIT && kind == 1), "predict_tiles: the logit merge needs logits, not probabilities");
   SEGK_REQUIRE(window == SEGK_TILE_WINDOW_FLAT || window == SEGK_TILE_WINDOW_TRIANGLE, "predict_tiles: bad window %d", window);
   if (int rc = check_plan("predict_tiles", H, W, T, overlap)) return rc;
-  SEGK_REQUIRE((color == nullptr) == (palette == nullptr), "predict_tiles: color and palette come together");
-  SEGK_REQUIRE((labels == nullptr) == (M == nullptr), "predict_tiles: labels and M come together");
+  if (int rc = check_output_pairs("predict_tiles", color, palette, labels, M)) return rc;
   const Axis ay = make_axis(H, T, overlap), ax = make_axis(W, T, overlap);
   SEGK_REQUIRE((long)ay.n * ax.n * C * T * T < (1L << 30), "predict_tiles: %d x %d tiles of %d x %d x %d: too large for 32-bit offsets",
                ay.n, ax.n, C, T, T);
   SEGK_REQUIRE(((uintptr_t)Y & 3) == 0, "predict_tiles: the tile outputs must be 4-byte aligned");
-  SEGK_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)conf & 3) == 0 && ((uintptr_t)scores & 3) == 0,
-               "predict_tiles: mask, color, conf and scores must be 4-byte aligned");
-  long g = (((long)H * W + 3) / 4 + 255) / 256;
-  const long cap = (counts || labels) ? 3L * segk_num_cus() : 16384;      // as segk_predict_mask: few blocks end in atomics
-  if (g > cap) g = cap;
+  if (int rc = check_output_alignment("predict_tiles", true, mask, color, conf, scores)) return rc;
+  const int g = finisher_grid((long)H * W, counts || labels);
   hipStream_t st = (hipStream_t)s;
   auto launch = [&](auto nc, auto lab) {
     hipLaunchKernelGGL((predict_tiles_kernel<decltype(nc)::value, decltype(lab)::value>), dim3((int)g), dim3(256), 0, st, Y, C, kind,
@@ -454,12 +338,7 @@ extern "C" int segk_predict_tiles(const float* Y, int C, int kind, int merge, in
     if (labels) launch(nc, std::true_type{});
     else launch(nc, std::false_type{});
   };
-  // compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: the smallest that holds C
-  if (C == 1) by_lab(std::integral_constant<int, 1>{});
-  else if (C == 2) by_lab(std::integral_constant<int, 2>{});
-  else if (C == 3) by_lab(std::integral_constant<int, 3>{});
-  else if (C == 4) by_lab(std::integral_constant<int, 4>{});
-  else by_lab(std::integral_constant<int, SEGK_MAX_CLASSES>{});
+  dispatch_classes(C, by_lab);
   SEGK_CHECK_LAUNCH("predict_tiles");
   return 0;
 }

@@ -234,10 +234,11 @@ def test_new_entries_refuse_bad_arguments_before_any_launch():
 
 
 def test_components_kernels_compiled_code():
-    """no spills and no scratch in the new unit (tools/spill_report.py), and every kernel of it is there"""
+    """no spills and no scratch in the unit (tools/spill_report.py) and in mask_finish_kernel (csrc/predict.hip), and every
+    kernel is there"""
     spec = importlib.util.spec_from_file_location("spill_report", os.path.join(ROOT, "tools", "spill_report.py"))
     tool = importlib.util.module_from_spec(spec); spec.loader.exec_module(tool)
-    rows = tool.report("components")
+    rows = tool.report("components") + [r for r in tool.report("predict") if "mask_finish_kernel" in r["name"]]
     names = " ".join(r["name"] for r in rows)
     for k in ("cc_tile_kernel", "cc_border_kernel", "cc_flatten_kernel", "cc_scan_kernel", "cc_rank_kernel", "cc_ids_kernel",
               "cc_clean_init_kernel", "cc_vote_kernel", "cc_apply_kernel", "mask_finish_kernel"):

@@ -1,6 +1,6 @@
 """CPU: the host half of the prediction surface (image_segmentation_amd/inference.py, tools/predict.py) -- checkpoint
 handling (reference segmentation_webapp/app.py:65-84), the palette / class-name tables (app.py:187-208), the argument
-errors Segmenter raises before any launch, and the compiled-code bar of the two prediction kernels of csrc/resize.hip
+errors Segmenter raises before any launch, and the compiled-code bar of the two prediction kernels (csrc/predict.hip, csrc/resize.hip)
 (hipcc cross-compiles without a GPU): no spills, no scratch, at most two loads that wait for themselves -- the bar
 tests/test_tools.py sets for the other streaming kernels."""
 import importlib.util
@@ -111,14 +111,16 @@ def _load_tool(name):
 
 def test_prediction_kernels_compiled_code():
     new = ("predict_mask_kernel", "resize_pad_u8_kernel")
-    rows = [r for r in _load_tool("serialized_loads").scan("resize") if any(k in r[3] for k in new)]
+    units = ("predict", "resize")          # predict_mask_kernel lives in csrc/predict.hip, resize_pad_u8_kernel in csrc/resize.hip
+    rows = [r for u in units for r in _load_tool("serialized_loads").scan(u) if any(k in r[3] for k in new)]
     # 5 class counts x 2 modes x with/without labels, and 3 channel counts x 3 modes
     assert sum("predict_mask_kernel" in r[3] for r in rows) == 20 and sum("resize_pad_u8_kernel" in r[3] for r in rows) == 9
     for n_ser, n_loads, _, name in rows:
         assert n_ser <= 2, f"{name}: {n_ser} of {n_loads} loads wait for themselves"
     seen = 0
-    for r in _load_tool("spill_report").report("resize"):
-        if any(k in r["name"] for k in new):
-            seen += 1
-            assert int(r.get("VGPRs Spill", 0)) == 0 and int(r.get("ScratchSize", 0)) == 0, r
+    for u in units:
+        for r in _load_tool("spill_report").report(u):
+            if any(k in r["name"] for k in new):
+                seen += 1
+                assert int(r.get("VGPRs Spill", 0)) == 0 and int(r.get("ScratchSize", 0)) == 0, r
     assert seen == 29

@@ -666,7 +666,7 @@ def components():
 
 
 def tta():
-    """Multi-view prediction through the C ABI (csrc/resize.hip): segk_predict_merge -- mask, colour, class
+    """Multi-view prediction through the C ABI (csrc/predict.hip): segk_predict_merge -- mask, colour, class
     counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
     weights, "prob" merge of logits) against the materialised route it replaces: per view segk_crop_resize to full-size fp32
     logits, torch.flip, softmax and a running weighted sum, then argmax, the confidence and segk_mask_finish.  Beside the
