@@ -128,6 +128,13 @@ class ReduceJob(C.Structure):
                 ("CB", C.c_int), ("Np", C.c_int), ("CAp", C.c_int), ("CBp", C.c_int), ("taps", C.c_int), ("pad_", C.c_int)]
 
 
+class PackEntry(C.Structure):
+    """SegkPackEntry of csrc/segk_internal.h (one tensor of segk_pack_multi's device table, 64 bytes)."""
+    _fields_ = [("w", C.c_void_p), ("dst_fwd", C.c_void_p), ("dst_dgrad", C.c_void_p), ("Cout", C.c_int), ("CA", C.c_int),
+                ("CB", C.c_int), ("Coutp", C.c_int), ("CAp", C.c_int), ("CBp", C.c_int), ("block0", C.c_int), ("kind", C.c_int),
+                ("pad_", C.c_int * 2)]
+
+
 _lib = None
 
 

@@ -11,6 +11,7 @@ channels_last memory format.
 import os
 import sys
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -59,6 +60,35 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _f32c(t):
+    """Detached fp32 contiguous form of a foreign operand (parameter, logits, incoming gradient): the same storage when it
+    already is one -- no copy, no kernel -- and a dtype/layout normalisation otherwise (edge only)."""
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()
+    return t
+
+
+def _i64c(t, n, what):
+    """Detached int64 contiguous labels, one for each of `n` pixels; `what` is the message of the error otherwise."""
+    tg = t.detach()
+    if tg.dtype != torch.int64 or not tg.is_contiguous():
+        tg = tg.long().contiguous()
+    if tg.numel() != n:
+        raise ValueError(what)
+    return tg
+
+
+def _class_weights(cw, C, dev):
+    """Per-class loss weights as an fp32 device vector of C entries (None stays None)."""
+    if cw is None:
+        return None
+    cw = cw.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if cw.numel() != C:
+        raise ValueError("class_weights must have one entry per class")
+    return cw
+
+
 # ------------------------------------------------------------------------------------------------
 # act-tensor helpers
 def new_act(B, C, H, W, dtype, device):
@@ -100,8 +130,7 @@ def to_act(x, dtype):
     if C % 32 == 0 and src.stride(1) == 1 and src.permute(0, 2, 3, 1).is_contiguous():
         # already dense NHWC (e.g. ViT token grids), only the dtype differs: cast in place of a re-layout
         return act_view(src.permute(0, 2, 3, 1).to(dtype), C)
-    if src.dtype != torch.float32 or not src.is_contiguous():
-        src = src.float().contiguous()       # layout/dtype normalisation of a foreign tensor (edge only)
+    src = _f32c(src)
     out = torch.empty((B, H, W, pad32(C)), dtype=dtype, device=x.device)
     _lib.call("segk_nchw_to_nhwc", src.data_ptr(), out.data_ptr(), B, C, H, W, pad32(C), _DT[dtype], _stream())
     return act_view(out, C)
@@ -161,51 +190,72 @@ def invalidate_packed_weights():
     _OPT_EPOCH[0] += 1
 
 
+def _param_version(param):
+    """What a packed copy of `param` was made from; a copy is stale when this differs."""
+    return (param._version, param.data_ptr(), param.device, _OPT_EPOCH[0] if param.requires_grad else -1)
+
+
+# kinds of the tensors segk_pack_multi refreshes (include/segk.h), with what d0, d1 of a PackRecord mean for each
+PACK_CONV3X3 = 0     # Conv2d 3x3 weight [Cout][CA+CB][3][3]: d0, d1 = CA, CB
+PACK_CONVT = 1       # ConvTranspose2d weight [Cin][Cout][2][2]
+PACK_BIAS = 2        # bias -> fp32 [reps][Coutp]: d0 = reps (0: the 4 of a ConvTranspose2d bias, 1: a conv bias)
+PACK_CONV1X1 = 3     # Conv2d 1x1 weight [Cout][Cin][1][1]: d0 = Cin (forward layout only: key_b is None)
+
+
+class PackRecord(NamedTuple):
+    """One entry of PackCache.multi: the copy under key_a (and its data-gradient twin under key_b, or None) of `param`."""
+    kind: int
+    key_b: object
+    param: torch.Tensor
+    d0: int
+    d1: int
+    dtype: torch.dtype
+
+
 class PackCache:
     """Re-packs a parameter into the MFMA layout when its autograd version counter moved, when it was re-allocated,
     or (trainable parameters) when any optimizer has stepped since the copy was made."""
 
     def __init__(self):
-        self._c = {}
-        self.multi = {}      # key_a -> (kind, key_b, param, d0, d1, dtype): what repack_stale() refreshes in one launch
+        self._c = {}         # key -> (version, packed copy)
+        self.multi = {}      # key_a -> PackRecord: what repack_stale() refreshes in one launch
+
+    def _current(self, key, param):
+        """(version of `param` now, the copy under `key` if it was made from that version else None)."""
+        ver = _param_version(param)
+        hit = self._c.get(key)
+        return ver, (None if hit is None or hit[0] != ver else hit[1])
+
+    def _store(self, ver, param, meta, key_a, a, key_b=None, b=None):
+        self._c[key_a] = (ver, a)
+        if key_b is not None:
+            self._c[key_b] = (ver, b)
+        if meta is not None:
+            self.multi[key_a] = PackRecord(meta[0], key_b, param, *meta[1:])
+
+    def get(self, key, param, builder, meta=None):
+        """The packed copy of `param` under `key`, built when missing or stale.  meta=(kind, d0, d1, dtype) registers it
+        for repack_stale()."""
+        ver, hit = self._current(key, param)
+        if hit is None:
+            hit = builder()
+            self._store(ver, param, meta, key, hit)
+        return hit
 
     def get_pair(self, key_a, key_b, param, builder, meta=None):
-        """Two packed copies made by one builder call (returns the first; the second is served by get(key_b)).
-        meta=(kind, d0, d1, dtype) registers the pair for repack_stale() (kind 0: 3x3 weight, d = CA, CB; kind 1:
-        ConvTranspose weight)."""
-        ver = (param._version, param.data_ptr(), param.device, _OPT_EPOCH[0] if param.requires_grad else -1)
-        hit = self._c.get(key_a)
-        if hit is None or hit[0] != ver:
-            a, b = builder()
-            hit = (ver, a)
-            self._c[key_a] = hit
-            self._c[key_b] = (ver, b)
-            if meta is not None:
-                self.multi[key_a] = (meta[0], key_b, param) + tuple(meta[1:])
-        return hit[1]
-
-    def get_registered(self, key, param, builder, meta):
-        """get() that also registers the single copy for repack_stale() (kind 2: ConvTranspose bias operand)."""
-        self.multi[key] = (meta[0], None, param) + tuple(meta[1:])
-        return self.get(key, param, builder)
-
-    def get(self, key, param, builder):
-        ver = (param._version, param.data_ptr(), param.device, _OPT_EPOCH[0] if param.requires_grad else -1)
-        hit = self._c.get(key)
-        if hit is None or hit[0] != ver:
-            hit = (ver, builder())
-            self._c[key] = hit
-        return hit[1]
+        """Two packed copies made by one builder call (returns the first; the second is served by get(key_b))."""
+        ver, hit = self._current(key_a, param)
+        if hit is None:
+            hit, b = builder()
+            self._store(ver, param, meta, key_a, hit, key_b, b)
+        return hit
 
 
 def pack_conv(w, CA, CB, dtype, mode, taps=9):
     Cout = w.shape[0]
     Coutp, CAp, CBp = pad32(Cout), pad32(CA), (pad32(CB) if CB else 0)
     dst = torch.empty(((CAp + CBp) * taps * Coutp,), dtype=dtype, device=w.device)
-    wf = w.detach()
-    if wf.dtype != torch.float32 or not wf.is_contiguous():
-        wf = wf.float().contiguous()
-    _lib.call("segk_pack_conv_weight", wf.data_ptr(), dst.data_ptr(), Cout, CA, CB, Coutp, CAp, CBp, taps, mode,
+    _lib.call("segk_pack_conv_weight", _f32c(w).data_ptr(), dst.data_ptr(), Cout, CA, CB, Coutp, CAp, CBp, taps, mode,
               _DT[dtype], _stream())
     return dst
 
@@ -216,11 +266,8 @@ def pack_conv_both(w, CA, CB, dtype):
     Coutp, CAp, CBp = pad32(Cout), pad32(CA), (pad32(CB) if CB else 0)
     n = (CAp + CBp) * 9 * Coutp
     both = torch.empty((2 * n,), dtype=dtype, device=w.device)
-    wf = w.detach()
-    if wf.dtype != torch.float32 or not wf.is_contiguous():
-        wf = wf.float().contiguous()
-    _lib.call("segk_pack_conv3x3_both", wf.data_ptr(), both.data_ptr(), both[n:].data_ptr(), Cout, CA, CB, Coutp, CAp, CBp,
-              _DT[dtype], _stream())
+    _lib.call("segk_pack_conv3x3_both", _f32c(w).data_ptr(), both.data_ptr(), both[n:].data_ptr(), Cout, CA, CB, Coutp, CAp,
+              CBp, _DT[dtype], _stream())
     return both[:n], both[n:]
 
 
@@ -228,28 +275,30 @@ _PACK_CONVT_CHUNK = [0]
 
 
 def _entry_geometry(kind, param, d0, d1):
-    """(elements of each destination, words 3..6 of the table entry without block0, blocks) of one registered tensor."""
-    if kind == 0:            # Conv2d 3x3 [Cout][CA+CB][3][3]: d0, d1 = CA, CB
-        Cout = param.shape[0]
-        Coutp, CAp, CBp = pad32(Cout), pad32(d0), (pad32(d1) if d1 else 0)
+    """(elements of each destination, the entry's Cout..CBp, blocks) of one registered tensor."""
+    if kind == PACK_CONVT:
+        d0, d1 = param.shape[0], 0
+    Cout = param.shape[1 if kind == PACK_CONVT else 0]
+    Coutp, CAp, CBp = pad32(Cout), pad32(d0), (pad32(d1) if d1 else 0)
+    if kind == PACK_BIAS:
+        return (d0 if d0 > 0 else 4) * Coutp, (Cout, d0, 0, Coutp, 0, 0), 1
+    if kind == PACK_CONV3X3:
         return (CAp + CBp) * 9 * Coutp, (Cout, d0, d1, Coutp, CAp, CBp), (CAp + CBp) // 32 * (Coutp // 32)
-    if kind == 1:            # ConvTranspose2d [Cin][Cout][2][2]
-        Cin, Cout = param.shape[0], param.shape[1]
-        Cinp, Coutp = pad32(Cin), pad32(Cout)
-        if not _PACK_CONVT_CHUNK[0]:
-            _PACK_CONVT_CHUNK[0] = _lib.query("segk_pack_convt_chunk")
-        n = Cinp * 4 * Coutp
-        return n, (Cout, Cin, 0, Coutp, Cinp, 0), (n + _PACK_CONVT_CHUNK[0] - 1) // _PACK_CONVT_CHUNK[0]
-    if kind == 3:            # Conv2d 1x1 weight [Cout][Cin][1][1]: d0 = Cin (forward layout only: key_b is None)
-        Cout = param.shape[0]
-        Coutp, CAp = pad32(Cout), pad32(d0)
-        if not _PACK_CONVT_CHUNK[0]:
-            _PACK_CONVT_CHUNK[0] = _lib.query("segk_pack_convt_chunk")
-        n = CAp * Coutp
-        return n, (Cout, d0, 0, Coutp, CAp, 0), (n + _PACK_CONVT_CHUNK[0] - 1) // _PACK_CONVT_CHUNK[0]
-    Cout = param.shape[0]    # kind 2: bias -> fp32 [reps][Coutp]; d0 = reps (0: the 4 of a ConvTranspose2d bias, 1: a conv bias)
-    reps = d0 if d0 > 0 else 4
-    return reps * pad32(Cout), (Cout, d0, 0, pad32(Cout), 0, 0), 1
+    if not _PACK_CONVT_CHUNK[0]:
+        _PACK_CONVT_CHUNK[0] = _lib.query("segk_pack_convt_chunk")
+    n = CAp * (4 if kind == PACK_CONVT else 1) * Coutp
+    return n, (Cout, d0, 0, Coutp, CAp, 0), (n + _PACK_CONVT_CHUNK[0] - 1) // _PACK_CONVT_CHUNK[0]
+
+
+def _pack_table(sig, params):
+    """Host image of segk_pack_multi's table: one _lib.PackEntry for each row (parameter, forward destination,
+    data-gradient destination or 0 -- addresses -- kind, d0, d1) of `sig`, in launch order -> (the array, total blocks)."""
+    tab, blk = (_lib.PackEntry * len(sig))(), 0
+    for e, (w, dst_fwd, dst_dgrad, kind, d0, d1), param in zip(tab, sig, params):
+        _, (e.Cout, e.CA, e.CB, e.Coutp, e.CAp, e.CBp), nblk = _entry_geometry(kind, param, d0, d1)
+        e.w, e.dst_fwd, e.dst_dgrad, e.block0, e.kind = w, dst_fwd, dst_dgrad, blk, kind
+        blk += nblk
+    return tab, blk
 
 
 def _pack_caches(model):
@@ -288,60 +337,43 @@ def repack_stale(model):
         st["caches"] = _pack_caches(model)
     groups = {}
     for cache in st["caches"]:
-        for key_a, (kind, key_b, param, d0, d1, dtype) in cache.multi.items():
+        for key_a, rec in cache.multi.items():
+            param = rec.param
             ha = cache._c.get(key_a)
-            hb = cache._c.get(key_b) if key_b is not None else None
-            if ha is None or (key_b is not None and hb is None):
+            hb = cache._c.get(rec.key_b) if rec.key_b is not None else None
+            if ha is None or (rec.key_b is not None and hb is None):
                 continue
             if not param.is_cuda or param.dtype != torch.float32 or not param.is_contiguous():
                 continue
-            ver = (param._version, param.data_ptr(), param.device, _OPT_EPOCH[0] if param.requires_grad else -1)
+            ver = _param_version(param)
             if ha[0] == ver and (hb is None or hb[0] == ver):
                 continue
-            n, _, _ = _entry_geometry(kind, param, d0, d1)
-            want = torch.float32 if kind == 2 else dtype
-            if ha[1].numel() != n or ha[1].dtype != want or not ha[1].is_contiguous():
+            n, _, _ = _entry_geometry(rec.kind, param, rec.d0, rec.d1)
+            want = torch.float32 if rec.kind == PACK_BIAS else rec.dtype
+            if any(h is not None and (h[1].numel() != n or h[1].dtype != want or not h[1].is_contiguous()) for h in (ha, hb)):
                 continue
-            if hb is not None and (hb[1].numel() != n or hb[1].dtype != want or not hb[1].is_contiguous()):
-                continue
-            groups.setdefault((dtype, param.device), []).append(
-                (cache, key_a, key_b, ver, param, ha[1], None if hb is None else hb[1], kind, d0, d1))
+            groups.setdefault((rec.dtype, param.device), []).append((cache, key_a, rec, ver, ha[1], None if hb is None else hb[1]))
     for (dtype, dev), items in groups.items():
         if len(items) < 2:
             continue                 # a single tensor goes through its own path
         for c0 in range(0, len(items), 64):
             chunk = items[c0:c0 + 64]
-            sig = tuple((it[4].data_ptr(), it[5].data_ptr(), 0 if it[6] is None else it[6].data_ptr(), it[7], it[8], it[9])
-                        for it in chunk)
+            sig = tuple((rec.param.data_ptr(), a.data_ptr(), _p(b), rec.kind, rec.d0, rec.d1) for _, _, rec, _, a, b in chunk)
             tab = st["tables"].get((dtype, dev, c0))
             if tab is None or tab[0] != sig:
-                import numpy as np
-                words = np.zeros((len(chunk), 8), dtype=np.int64)
-                ints = words.view(np.int32).reshape(len(chunk), 16)
-                blk = 0
-                for i, (_, _, _, _, param, a, b, kind, d0, d1) in enumerate(chunk):
-                    _, dims, nblk = _entry_geometry(kind, param, d0, d1)
-                    words[i, 0], words[i, 1], words[i, 2] = param.data_ptr(), a.data_ptr(), 0 if b is None else b.data_ptr()
-                    ints[i, 6:12] = dims
-                    ints[i, 12], ints[i, 13] = blk, kind
-                    blk += nblk
-                tab = (sig, torch.from_numpy(words).to(dev), blk)
+                entries, blocks = _pack_table(sig, [rec.param for _, _, rec, _, _, _ in chunk])
+                tab = (sig, torch.frombuffer(entries, dtype=torch.int64).to(dev), blocks)
                 st["tables"][(dtype, dev, c0)] = tab
             with torch.cuda.device(dev):
                 _lib.call("segk_pack_multi", tab[1].data_ptr(), len(chunk), tab[2], _DT[dtype], _stream())
-            for cache, key_a, key_b, ver, _, a, b, _, _, _ in chunk:
-                cache._c[key_a] = (ver, a)
-                if key_b is not None:
-                    cache._c[key_b] = (ver, b)
+            for cache, key_a, rec, ver, a, b in chunk:
+                cache._store(ver, rec.param, None, key_a, a, rec.key_b, b)
 
 
 def pack_convt(w, dtype, mode):
     Cin, Cout = w.shape[0], w.shape[1]
     dst = torch.empty((pad32(Cin) * 4 * pad32(Cout),), dtype=dtype, device=w.device)
-    wf = w.detach()
-    if wf.dtype != torch.float32 or not wf.is_contiguous():
-        wf = wf.float().contiguous()
-    _lib.call("segk_pack_convt_weight", wf.data_ptr(), dst.data_ptr(), Cin, Cout, pad32(Cin), pad32(Cout), mode,
+    _lib.call("segk_pack_convt_weight", _f32c(w).data_ptr(), dst.data_ptr(), Cin, Cout, pad32(Cin), pad32(Cout), mode,
               _DT[dtype], _stream())
     return dst
 
@@ -388,16 +420,15 @@ class _Span:
     def __exit__(self, *exc):
         b = torch.cuda.Event(enable_timing=True)
         b.record()
-        r = self.t.rows.setdefault(self.tag, {"ev": [], "flops": 0.0, "bytes": 0.0})
-        r["ev"].append((self.a, b))
-        r["flops"] += self.flops
-        r["bytes"] += self.nbytes
-        if _LEVEL is not None:
-            phase = {"conv3x3_igemm": "dgrad" if _LEVEL[1] else "fwd", "wgrad3x3": "wgrad"}.get(self.tag, "other")
-            r = self.t.levels.setdefault((_LEVEL[0], phase), {"ev": [], "flops": 0.0, "bytes": 0.0})
+        def record(rows, key):
+            r = rows.setdefault(key, {"ev": [], "flops": 0.0, "bytes": 0.0})
             r["ev"].append((self.a, b))
             r["flops"] += self.flops
             r["bytes"] += self.nbytes
+        record(self.t.rows, self.tag)
+        if _LEVEL is not None:
+            phase = {"conv3x3_igemm": "dgrad" if _LEVEL[1] else "fwd", "wgrad3x3": "wgrad"}.get(self.tag, "other")
+            record(self.t.levels, (_LEVEL[0], phase))
 
 
 class _NoSpan:
@@ -474,14 +505,20 @@ def _f32(n, dev):
     return torch.empty((n,), dtype=torch.float32, device=dev)
 
 
+def _device_key(dev):
+    """`dev` as a torch.device that names its index (the key of the per-device tables)."""
+    key = torch.device(dev)
+    if key.type == "cuda" and key.index is None:
+        key = torch.device("cuda", torch.cuda.current_device())
+    return key
+
+
 _ZERO_PAGES = {}
 
 
 def _zero_page(dev):
     """64 zero bytes per device: the halo source of the LDS-DMA weight-gradient kernel."""
-    key = torch.device(dev)
-    if key.type == "cuda" and key.index is None:
-        key = torch.device("cuda", torch.cuda.current_device())
+    key = _device_key(dev)
     z = _ZERO_PAGES.get(key)
     if z is None:
         z = torch.zeros(256, dtype=torch.uint8, device=key)
@@ -604,33 +641,30 @@ def bn_relu_bwd(dy_ptr, z_ptr, dz_ptr, scale, shift, mean, rstd, P, C, dtype, de
     their apply pass discarded, then an apply pass from all-zero partials) -- not a hot path."""
     Cp = pad32(C)
     dgamma, dbeta = _f32(C, dev), _f32(C, dev)
+    bn = (scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), P, Cp, C)    # follows the output pointer
     if frozen:
         nb = _lib.query("segk_bn_bwd_blocks", P, Cp, _DT[dtype])
         part, coef = _f32(nb * Cp * 2, dev), _f32(2 * Cp, dev)
         scratch = torch.empty((P * Cp,), dtype=dtype, device=dev)
-        _lib.call("segk_bn_relu_bwd", dy_ptr, z_ptr, scratch.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                  rstd.data_ptr(), P, Cp, C, part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(),
-                  _DT[dtype], _stream())
+        _lib.call("segk_bn_relu_bwd", dy_ptr, z_ptr, scratch.data_ptr(), *bn, part.data_ptr(), dgamma.data_ptr(),
+                  dbeta.data_ptr(), coef.data_ptr(), _DT[dtype], _stream())
         zero_part = torch.zeros((Cp * 2,), dtype=torch.float32, device=dev)
         unused_g, unused_b = _f32(C, dev), _f32(C, dev)
-        _lib.call("segk_bn_relu_bwd_from_part", dy_ptr, z_ptr, dz_ptr, scale.data_ptr(), shift.data_ptr(),
-                  mean.data_ptr(), rstd.data_ptr(), P, Cp, C, zero_part.data_ptr(), 1, unused_g.data_ptr(), unused_b.data_ptr(),
-                  coef.data_ptr(), _DT[dtype], _stream())
+        _lib.call("segk_bn_relu_bwd_from_part", dy_ptr, z_ptr, dz_ptr, *bn, zero_part.data_ptr(), 1, unused_g.data_ptr(),
+                  unused_b.data_ptr(), coef.data_ptr(), _DT[dtype], _stream())
         return dgamma, dbeta
     if ready is not None:
         part, nb = ready
         coef = _f32(2 * Cp, dev)
         with _span("bn_relu_bwd", 0.0, 3.0 * P * C * _es(dtype)):     # apply only: 2 reads + 1 write
-            _lib.call("segk_bn_relu_bwd_from_part", dy_ptr, z_ptr, dz_ptr, scale.data_ptr(), shift.data_ptr(),
-                      mean.data_ptr(), rstd.data_ptr(), P, Cp, C, part.data_ptr(), nb, dgamma.data_ptr(), dbeta.data_ptr(),
-                      coef.data_ptr(), _DT[dtype], _stream())
+            _lib.call("segk_bn_relu_bwd_from_part", dy_ptr, z_ptr, dz_ptr, *bn, part.data_ptr(), nb, dgamma.data_ptr(),
+                      dbeta.data_ptr(), coef.data_ptr(), _DT[dtype], _stream())
         return dgamma, dbeta
     nb = _lib.query("segk_bn_bwd_blocks", P, Cp, _DT[dtype])
     part, coef = _f32(nb * Cp * 2, dev), _f32(2 * Cp, dev)
     with _span("bn_relu_bwd", 0.0, 5.0 * P * C * _es(dtype)):     # reduce: 2 reads; apply: 2 reads + 1 write
-        _lib.call("segk_bn_relu_bwd", dy_ptr, z_ptr, dz_ptr, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                  rstd.data_ptr(), P, Cp, C, part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(),
-                  _DT[dtype], _stream())
+        _lib.call("segk_bn_relu_bwd", dy_ptr, z_ptr, dz_ptr, *bn, part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                  coef.data_ptr(), _DT[dtype], _stream())
     return dgamma, dbeta
 
 
@@ -651,9 +685,7 @@ def _zero_grad_like(n, dev):
     a copy per layer -- autograd adopts a fresh view as `.grad` without copying it (a tensor shared between parameters
     would be cloned by AccumulateGrad: 18 small copies per U-Net step).  The slices are disjoint, and nothing in the
     training path does more to a gradient than scale or reduce it, which keeps zeros zero."""
-    key = torch.device(dev)
-    if key.type == "cuda" and key.index is None:
-        key = torch.device("cuda", torch.cuda.current_device())
+    key = _device_key(dev)
     pool = _ZERO_POOL.get(key)
     if pool is None or pool[0] != _OPT_EPOCH[0] or pool[2] + n > pool[1].numel():
         pool = [_OPT_EPOCH[0], torch.zeros(max(16384, 4 * n), dtype=torch.float32, device=key), 0]
@@ -693,13 +725,6 @@ def _bump_batch_counters(*bns):
             bn.num_batches_tracked.add_(1)
 
 
-def _param_f32(p):
-    t = p.detach()
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.float().contiguous()
-    return t
-
-
 # ------------------------------------------------------------------------------------------------
 # Building blocks shared by the autograd Functions below.  Everything a backward kernel hands to a later backward
 # kernel (BatchNorm reductions accumulated by the pooling / head backward, channel sums of a concat gradient) stays
@@ -716,15 +741,15 @@ def _convt_fwd(mod, x_t, px, w, b, B, H, W, Cin, Cout, dtype, dev, both=False):
     Cinp, Coutp = pad32(Cin), pad32(Cout)
     if both:      # a backward will follow: both layouts, registered for the one-launch repack
         wp = mod.cache.get_pair(("tf", dtype), ("td", dtype), w, lambda: (pack_convt(w, dtype, 0), pack_convt(w, dtype, 1)),
-                                meta=(1, 0, 0, dtype))
+                                meta=(PACK_CONVT, 0, 0, dtype))
     else:
         wp = mod.cache.get(("tf", dtype), w, lambda: pack_convt(w, dtype, 0))
 
     def bias4():
         t = torch.zeros((4, Coutp), dtype=torch.float32, device=dev)
-        t[:, :Cout] = _param_f32(b)
+        t[:, :Cout] = _f32c(b)
         return t
-    b4 = None if b is None else mod.cache.get_registered(("tb", dtype), b, bias4, meta=(2, 0, 0, dtype))
+    b4 = None if b is None else mod.cache.get(("tb", dtype), b, bias4, meta=(PACK_BIAS, 0, 0, dtype))
     out = torch.empty((B, 2 * H, 2 * W, Coutp), dtype=dtype, device=dev)
     with _span("convt_fwd", 2.0 * B * H * W * Cin * 4 * Cout, B * H * W * (Cin + 4 * Cout) * _es(dtype)):
         _lib.call("segk_convt2x2_fwd", px, wp.data_ptr(), _p(b4), out.data_ptr(), B, H, W, Cinp, Coutp, _DT[dtype],
@@ -762,14 +787,14 @@ def _head_fwd(px, Cp, w, b, B, C, H, W, dtype, dev, bn=None):
     ncls = w.shape[0]
     if ncls > _lib.MAX_CLASSES:
         raise RuntimeError(f"output head supports up to {_lib.MAX_CLASSES} classes, got {ncls}")
-    w2 = _param_f32(w).reshape(ncls, C)
+    w2 = _f32c(w).reshape(ncls, C)
     logits = torch.empty((B, ncls, H, W), dtype=torch.float32, device=dev)
     with _span("head_fwd", 2.0 * B * H * W * C * ncls, B * H * W * (C * _es(dtype) + 4 * ncls)):
         if bn is not None:
-            _lib.call("segk_head_fwd_bn", px, bn[0].data_ptr(), bn[1].data_ptr(), w2.data_ptr(), _param_f32(b).data_ptr(),
+            _lib.call("segk_head_fwd_bn", px, bn[0].data_ptr(), bn[1].data_ptr(), w2.data_ptr(), _f32c(b).data_ptr(),
                       logits.data_ptr(), B, H, W, Cp, C, ncls, _DT[dtype], _stream())
         else:
-            _lib.call("segk_head_fwd", px, w2.data_ptr(), _param_f32(b).data_ptr(), logits.data_ptr(), B, H, W, Cp, C,
+            _lib.call("segk_head_fwd", px, w2.data_ptr(), _f32c(b).data_ptr(), logits.data_ptr(), B, H, W, Cp, C,
                       ncls, _DT[dtype], _stream())
     return logits
 
@@ -779,37 +804,28 @@ def _head_bwd(dlogits, px, Cp, w, B, C, H, W, dtype, dev, bn=None, on_z=False):
     reads: the kernel then also accumulates that BatchNorm's backward reductions over the dy it writes
     (bn_ready = (partials, rows) for bn_relu_bwd).  on_z: px points at the pre-activation z (see _head_fwd)."""
     ncls = w.shape[0]
-    dl = dlogits
-    if dl.dtype != torch.float32 or not dl.is_contiguous():
-        dl = dl.float().contiguous()
-    w2 = _param_f32(w).reshape(ncls, C)
+    dl = _f32c(dlogits)
+    w2 = _f32c(w).reshape(ncls, C)
     dy = torch.empty((B, H, W, Cp), dtype=dtype, device=dev)
     part = _f32(_lib.query("segk_head_part_floats", B * H * W, Cp), dev)
     dw = _grad_buffer(w, w.shape, dev)
     db = _f32(ncls, dev)
     ready = None
     with _span("head_bwd", 4.0 * B * H * W * C * ncls, B * H * W * (2 * C * _es(dtype) + 4 * ncls)):
-        if on_z:
-            sc, sh, mu, rs = bn
-            bnpart, nb = None, 0
+        # the BN entries take (scale, shift, mean, rstd, bnpart) between ncls and the dtype; on z the kernel needs the
+        # BatchNorm to form the activation, with or without the reductions (bnpart null)
+        entry, bn_tail = "segk_head_bwd", ()
+        if on_z or (bn is not None and FUSE_BN_REDUCE):
+            entry = "segk_head_bwd_bn" if on_z else "segk_head_bwd_bnstat"
+            bnpart = None
             if FUSE_BN_REDUCE:
                 nb = _lib.query("segk_head_bwd_blocks", B * H * W)
                 bnpart = _f32(nb * Cp * 2, dev)
                 ready = (bnpart, nb)
-            _lib.call("segk_head_bwd_bn", dl.data_ptr(), px, w2.data_ptr(), dy.data_ptr(), part.data_ptr(),
-                      dw.data_ptr(), db.data_ptr(), B, H, W, Cp, C, ncls, sc.data_ptr(), sh.data_ptr(), mu.data_ptr(),
-                      rs.data_ptr(), _p(bnpart), _DT[dtype], _stream())
-        elif bn is not None and FUSE_BN_REDUCE:
             sc, sh, mu, rs = bn
-            nb = _lib.query("segk_head_bwd_blocks", B * H * W)
-            bnpart = _f32(nb * Cp * 2, dev)
-            _lib.call("segk_head_bwd_bnstat", dl.data_ptr(), px, w2.data_ptr(), dy.data_ptr(), part.data_ptr(),
-                      dw.data_ptr(), db.data_ptr(), B, H, W, Cp, C, ncls, sc.data_ptr(), sh.data_ptr(), mu.data_ptr(),
-                      rs.data_ptr(), bnpart.data_ptr(), _DT[dtype], _stream())
-            ready = (bnpart, nb)
-        else:
-            _lib.call("segk_head_bwd", dl.data_ptr(), px, w2.data_ptr(), dy.data_ptr(), part.data_ptr(), dw.data_ptr(),
-                      db.data_ptr(), B, H, W, Cp, C, ncls, _DT[dtype], _stream())
+            bn_tail = (sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), rs.data_ptr(), _p(bnpart))
+        _lib.call(entry, dl.data_ptr(), px, w2.data_ptr(), dy.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                  B, H, W, Cp, C, ncls, *bn_tail, _DT[dtype], _stream())
     return dy, dw, db, ready
 
 
@@ -894,9 +910,9 @@ class DoubleConvFn(torch.autograd.Function):
         xb_t, pB, CBp = (None, 0, 0) if xb is None else _raw(xb, dtype)
         if training and want_grad:     # a backward will follow: both layouts in one pass per weight
             w1p = mod.cache.get_pair(("w1f", dtype), ("w1d", dtype), w1, lambda: pack_conv_both(w1, CA, CB, dtype),
-                                     meta=(0, CA, CB, dtype))
+                                     meta=(PACK_CONV3X3, CA, CB, dtype))
             w2p = mod.cache.get_pair(("w2f", dtype), ("w2d", dtype), w2, lambda: pack_conv_both(w2, Cout, 0, dtype),
-                                     meta=(0, Cout, 0, dtype))
+                                     meta=(PACK_CONV3X3, Cout, 0, dtype))
         else:
             w1p = mod.cache.get(("w1f", dtype), w1, lambda: pack_conv(w1, CA, CB, dtype, 0))
             w2p = mod.cache.get(("w2f", dtype), w2, lambda: pack_conv(w2, Cout, 0, dtype, 0))
@@ -913,8 +929,8 @@ class DoubleConvFn(torch.autograd.Function):
                           _DT[dtype], _stream())
         else:
             conv3x3(xa_t, pA, CAp, pB, CBp, w1p, z1.data_ptr(), Coutp, 0, 0, B, H, W, dtype, stats=st1, alg=(CA + CB, Cout))
-        sc1, sh1, mu1, rs1 = bn_finalize(st1, tiles1, Cout, P, None if b1 is None else _param_f32(b1), _param_f32(g1),
-                                         _param_f32(be1), bn1.running_mean, bn1.running_var, _bn_momentum(bn1), bn1.eps,
+        sc1, sh1, mu1, rs1 = bn_finalize(st1, tiles1, Cout, P, None if b1 is None else _f32c(b1), _f32c(g1),
+                                         _f32c(be1), bn1.running_mean, bn1.running_var, _bn_momentum(bn1), bn1.eps,
                                          training, dev)
         z2 = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
         st2 = _f32(_lib.query("segk_bn_stats_floats", tiles2, Coutp), dev) if training else None
@@ -930,8 +946,8 @@ class DoubleConvFn(torch.autograd.Function):
         else:
             conv3x3(z1, z1.data_ptr(), Coutp, 0, 0, w2p, z2.data_ptr(), Coutp, 0, 0, B, H, W, dtype, scale=sc1,
                     shift=sh1, stats=st2, alg=(Cout, Cout))
-        sc2, sh2, mu2, rs2 = bn_finalize(st2, tiles2, Cout, P, None if b2 is None else _param_f32(b2), _param_f32(g2),
-                                         _param_f32(be2), bn2.running_mean, bn2.running_var, _bn_momentum(bn2), bn2.eps,
+        sc2, sh2, mu2, rs2 = bn_finalize(st2, tiles2, Cout, P, None if b2 is None else _f32c(b2), _f32c(g2),
+                                         _f32c(be2), bn2.running_mean, bn2.running_var, _bn_momentum(bn2), bn2.eps,
                                          training, dev)
         if training:
             _bump_batch_counters(bn1, bn2)
@@ -1202,13 +1218,13 @@ class Conv1x1Fn(torch.autograd.Function):
         Cinp, Coutp = pad32(Cin), pad32(Cout)
         x_t, px, _ = _raw(x, dtype)
         # both operands are registered for the model's one-launch re-pack after an optimizer step (repack_stale)
-        wp = mod.cache.get_registered(("cf", dtype), w, lambda: pack_conv(w, Cin, 0, dtype, 0, taps=1), meta=(3, Cin, 0, dtype))
+        wp = mod.cache.get(("cf", dtype), w, lambda: pack_conv(w, Cin, 0, dtype, 0, taps=1), meta=(PACK_CONV1X1, Cin, 0, dtype))
 
         def biasp():
             t = torch.zeros((Coutp,), dtype=torch.float32, device=dev)
-            t[:Cout] = _param_f32(b)
+            t[:Cout] = _f32c(b)
             return t
-        bp = None if b is None else mod.cache.get_registered(("cb", dtype), b, biasp, meta=(2, 1, 0, dtype))
+        bp = None if b is None else mod.cache.get(("cb", dtype), b, biasp, meta=(PACK_BIAS, 1, 0, dtype))
         out = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
         _lib.call("segk_conv1x1", px, wp.data_ptr(), _p(bp), out.data_ptr(), B, H, W, Cinp, Coutp, _DT[dtype], _stream())
         ctx.mod, ctx.dtype, ctx.dims = mod, dtype, (B, H, W, Cin, Cout)
@@ -1255,7 +1271,7 @@ class ReconHeadFn(torch.autograd.Function):
         rec = torch.empty((B, Cout, H, W), dtype=torch.float32, device=dev)
         P = B * H * W
         with _span("recon_head_fwd", 2.0 * P * 9 * Cin * Cout, P * (Cin * _es(dtype) + 4 * Cout)):
-            _lib.call("segk_recon_head_fwd", px, _param_f32(w).data_ptr(), 0 if b is None else _param_f32(b).data_ptr(),
+            _lib.call("segk_recon_head_fwd", px, _f32c(w).data_ptr(), 0 if b is None else _f32c(b).data_ptr(),
                       rec.data_ptr(), B, H, W, Cp, Cin, Cout, _DT[dtype], _stream())
         ctx.mod, ctx.dtype, ctx.dims = mod, dtype, (B, H, W, Cin, Cout)
         ctx.has_bias = b is not None
@@ -1269,9 +1285,7 @@ class ReconHeadFn(torch.autograd.Function):
         B, H, W, Cin, Cout = ctx.dims
         dev = x_t.device
         Cinp, Coutp = pad32(Cin), pad32(Cout)
-        g = drec.detach()
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.float().contiguous()
+        g = _f32c(drec)
         dzb = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
         P = B * H * W
         with _span("recon_sigmoid_bwd", 0.0, P * (8.0 * Cout + Coutp * _es(dtype))):
@@ -1293,14 +1307,6 @@ class ReconHeadFn(torch.autograd.Function):
         return None, dx, dw, db
 
 
-def _mse_operand(t, what):
-    _require_cuda(t, what)
-    t = t.detach()
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.float().contiguous()       # dtype/layout normalisation of a foreign tensor (edge only)
-    return t
-
-
 class MSELossFn(torch.autograd.Function):
     """nn.MSELoss(reduction='mean' | 'sum') -- as reference autoencoder/autoencoder.ipynb constructs it and
     utils/training.py:141,234 call it.  Deterministic: fixed per-block fp64 partials and a fixed-order finalize."""
@@ -1309,7 +1315,9 @@ class MSELossFn(torch.autograd.Function):
     def forward(ctx, input, target, mean):
         if input.shape != target.shape:
             raise ValueError(f"MSELoss: input {tuple(input.shape)} and target {tuple(target.shape)} differ in shape")
-        a, b = _mse_operand(input, "MSELoss input"), _mse_operand(target, "MSELoss target")
+        _require_cuda(input, "MSELoss input")
+        _require_cuda(target, "MSELoss target")
+        a, b = _f32c(input), _f32c(target)
         n = a.numel()
         if n == 0:
             raise ValueError("MSELoss of empty tensors")
@@ -1325,7 +1333,7 @@ class MSELossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         a, b = ctx.saved_tensors
-        go = gout.detach().float().reshape(1).contiguous()
+        go = _f32c(gout).reshape(1)
         da = torch.empty_like(a)
         db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         n = a.numel()
@@ -1389,36 +1397,34 @@ class HeadFn(torch.autograd.Function):
         return None, act_view(dy, C), dw, db
 
 
+def _loss_operands(x, target, class_weights, ignore_index, what, noun):
+    """What SegLossFn and ProbLossFn check and allocate alike; `noun` says what x [N,C,H,W] holds -> (x fp32, int64 labels,
+    class weights or None, ignore index or -1, per-block partials, kernel state, loss buffer)."""
+    _require_cuda(x, what)
+    if x.dim() != 4:
+        raise ValueError(f"expected {noun} [N,C,H,W], got {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    if C > _lib.MAX_CLASSES:
+        raise RuntimeError(f"fused loss supports up to {_lib.MAX_CLASSES} classes, got {C}")
+    xf = _f32c(x)
+    tg = _i64c(target, N * H * W, f"target shape {tuple(target.shape)} does not match {noun} {tuple(x.shape)}")
+    cw = _class_weights(class_weights, C, x.device)
+    ign = -1 if ignore_index is None else int(ignore_index)
+    part = _f32(_lib.query("segk_loss_part_floats", N * H * W), x.device)
+    state = _f32(_lib.query("segk_loss_state_floats"), x.device)
+    out = _f32(1, x.device)     # the returned loss lives in a buffer of its own (no copy kernel, no view of saved state)
+    return xf, tg, cw, ign, part, state, out
+
+
 class SegLossFn(torch.autograd.Function):
     """dice_weight * softDice + ce_weight * CrossEntropy in one pass over the logits --
     reference utils/weighted_loss.py:31-98,140-166 and nn.CrossEntropyLoss as called at utils/training.py:47."""
 
     @staticmethod
     def forward(ctx, logits, target, class_weights, ignore_index, smooth, dice_weight, ce_weight):
-        _require_cuda(logits, "segmentation loss")
-        if logits.dim() != 4:
-            raise ValueError(f"expected logits [N,C,H,W], got {tuple(logits.shape)}")
+        lg, tg, cw, ign, part, state, out = _loss_operands(logits, target, class_weights, ignore_index, "segmentation loss",
+                                                           "logits")
         N, C, H, W = logits.shape
-        if C > _lib.MAX_CLASSES:
-            raise RuntimeError(f"fused loss supports up to {_lib.MAX_CLASSES} classes, got {C}")
-        lg = logits.detach()
-        if lg.dtype != torch.float32 or not lg.is_contiguous():
-            lg = lg.float().contiguous()
-        tg = target.detach()
-        if tg.dtype != torch.int64 or not tg.is_contiguous():
-            tg = tg.long().contiguous()
-        if tg.numel() != N * H * W:
-            raise ValueError(f"target shape {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
-        dev = logits.device
-        cw = None
-        if class_weights is not None:
-            cw = class_weights.detach().to(device=dev, dtype=torch.float32).contiguous()
-            if cw.numel() != C:
-                raise ValueError("class_weights must have one entry per class")
-        ign = -1 if ignore_index is None else int(ignore_index)
-        part = _f32(_lib.query("segk_loss_part_floats", N * H * W), dev)
-        state = _f32(_lib.query("segk_loss_state_floats"), dev)
-        out = _f32(1, dev)          # the returned loss lives in a buffer of its own (no copy kernel, no view of saved state)
         with _span("loss_fwd", 0.0, N * H * W * (4.0 * C + 8)):
             _lib.call("segk_loss_fwd", lg.data_ptr(), tg.data_ptr(), _p(cw), N, C, H * W, ign, float(smooth),
                       float(dice_weight), float(ce_weight), part.data_ptr(), state.data_ptr(), out.data_ptr(), _stream())
@@ -1430,7 +1436,7 @@ class SegLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         lg, tg, cw, state = ctx.saved_tensors
         N, C, H, W, ign, dw, cew = ctx.cfg
-        go = gout.detach().float().reshape(1).contiguous()
+        go = _f32c(gout).reshape(1)
         dl = torch.empty_like(lg)
         with _span("loss_bwd", 0.0, N * H * W * (8.0 * C + 8)):
             _lib.call("segk_loss_bwd", lg.data_ptr(), tg.data_ptr(), _p(cw), state.data_ptr(), go.data_ptr(), N, C,
@@ -1445,30 +1451,9 @@ class ProbLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, probs, target, class_weights, ignore_index, smooth, dice_weight, nll_weight, nll_log, eps):
-        _require_cuda(probs, "probability loss")
-        if probs.dim() != 4:
-            raise ValueError(f"expected probabilities [N,C,H,W], got {tuple(probs.shape)}")
+        pr, tg, cw, ign, part, state, out = _loss_operands(probs, target, class_weights, ignore_index, "probability loss",
+                                                           "probabilities")
         N, C, H, W = probs.shape
-        if C > _lib.MAX_CLASSES:
-            raise RuntimeError(f"fused loss supports up to {_lib.MAX_CLASSES} classes, got {C}")
-        pr = probs.detach()
-        if pr.dtype != torch.float32 or not pr.is_contiguous():
-            pr = pr.float().contiguous()
-        tg = target.detach()
-        if tg.dtype != torch.int64 or not tg.is_contiguous():
-            tg = tg.long().contiguous()
-        if tg.numel() != N * H * W:
-            raise ValueError(f"target shape {tuple(target.shape)} does not match probabilities {tuple(probs.shape)}")
-        dev = probs.device
-        cw = None
-        if class_weights is not None:
-            cw = class_weights.detach().to(device=dev, dtype=torch.float32).contiguous()
-            if cw.numel() != C:
-                raise ValueError("class_weights must have one entry per class")
-        ign = -1 if ignore_index is None else int(ignore_index)
-        part = _f32(_lib.query("segk_loss_part_floats", N * H * W), dev)
-        state = _f32(_lib.query("segk_loss_state_floats"), dev)
-        out = _f32(1, dev)
         with _span("loss_fwd", 0.0, N * H * W * (4.0 * C + 8)):
             _lib.call("segk_prob_loss_fwd", pr.data_ptr(), tg.data_ptr(), _p(cw), N, C, H * W, ign, float(smooth),
                       float(dice_weight), float(nll_weight), int(nll_log), float(eps), part.data_ptr(), state.data_ptr(),
@@ -1481,7 +1466,7 @@ class ProbLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         pr, tg, cw, state = ctx.saved_tensors
         N, C, H, W, ign, dw, nw, nll_log, eps = ctx.cfg
-        go = gout.detach().float().reshape(1).contiguous()
+        go = _f32c(gout).reshape(1)
         dp = torch.empty_like(pr)
         with _span("loss_bwd", 0.0, N * H * W * (8.0 * C + 8)):
             _lib.call("segk_prob_loss_bwd", pr.data_ptr(), tg.data_ptr(), _p(cw), state.data_ptr(), go.data_ptr(), N, C,
@@ -1519,16 +1504,10 @@ class DistillFn(torch.autograd.Function):
             _require_cuda(t, "distillation loss (teacher view)")
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != logits.device:
                 raise ValueError("teacher views must be contiguous float32 tensors on the student's device")
-        lg = logits.detach()
-        if lg.dtype != torch.float32 or not lg.is_contiguous():
-            lg = lg.float().contiguous()
+        lg = _f32c(logits)
         tg = None
         if target is not None and ignore_index is not None:
-            tg = target.detach()
-            if tg.dtype != torch.int64 or not tg.is_contiguous():
-                tg = tg.long().contiguous()
-            if tg.numel() != N * H * W:
-                raise ValueError(f"target shape {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+            tg = _i64c(target, N * H * W, f"target shape {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
         dev = logits.device
         ign = 0 if ignore_index is None else int(ignore_index)
         part = _f32(_lib.query("segk_loss_part_floats", N * H * W), dev)
@@ -1548,7 +1527,7 @@ class DistillFn(torch.autograd.Function):
     def backward(ctx, gout, _gstate):
         lg, tg, state = ctx.saved_tensors
         V, N, C, H, W, ign, inv_t, t_sq, min_conf = ctx.cfg
-        go = gout.detach().float().reshape(1).contiguous()
+        go = _f32c(gout).reshape(1)
         dl = torch.empty_like(lg)
         with _span("distill_bwd", 0.0, N * H * W * (4.0 * C * (2 + V) + (8 if tg is not None else 0))):
             _lib.call("segk_distill_bwd", lg.data_ptr(), ctx.views.table.data_ptr(), V, _p(tg), state.data_ptr(), go.data_ptr(),
@@ -1570,8 +1549,7 @@ class PromptMixFn(torch.autograd.Function):
                              f"{tuple(clip_logits.shape)} and {tuple(mask_logit.shape)}")
         if clip_logits.requires_grad:
             raise RuntimeError("prompt remix: the CLIP branch must be frozen (prompt.py:30-31); only the mask gets a gradient")
-        cl = clip_logits.detach().float().contiguous()
-        ml = mask_logit.detach().float().contiguous()
+        cl, ml = _f32c(clip_logits), _f32c(mask_logit)
         out = torch.empty_like(cl)
         with _span("prompt_mix", 0.0, N * H * W * 36.0):
             _lib.call("segk_prompt_mix_fwd", cl.data_ptr(), ml.data_ptr(), out.data_ptr(), N, H * W, _stream())
@@ -1582,7 +1560,7 @@ class PromptMixFn(torch.autograd.Function):
     def backward(ctx, dout):
         cl, ml = ctx.saved_tensors
         N, _, H, W = cl.shape
-        d = dout.detach().float().contiguous()
+        d = _f32c(dout)
         dm = torch.empty_like(ml)
         with _span("prompt_mix", 0.0, N * H * W * 40.0):
             _lib.call("segk_prompt_mix_bwd", cl.data_ptr(), ml.data_ptr(), d.data_ptr(), dm.data_ptr(), N, H * W, _stream())
@@ -1599,14 +1577,7 @@ def confusion_matrix(logits, labels, num_classes, out=None):
     N, C, H, W = logits.shape
     if C != num_classes or C > _lib.MAX_CLASSES:
         raise ValueError(f"expected {num_classes} (<= {_lib.MAX_CLASSES}) class channels, got {C}")
-    lg = logits.detach()
-    if lg.dtype != torch.float32 or not lg.is_contiguous():
-        lg = lg.float().contiguous()
-    tg = labels.detach()
-    if tg.dtype != torch.int64 or not tg.is_contiguous():
-        tg = tg.long().contiguous()
-    if tg.numel() != N * H * W:
-        raise ValueError("label shape does not match logits")
+    lg, tg = _f32c(logits), _i64c(labels, N * H * W, "label shape does not match logits")
     # `out`: a persistent [MAX_CLASSES, MAX_CLASSES] int64 device matrix the counts are ADDED to (no allocation, no sync)
     M = out if out is not None else torch.zeros((_lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=logits.device)
     _lib.call("segk_confusion", lg.data_ptr(), tg.data_ptr(), N, C, H * W, M.data_ptr(), _stream())

@@ -13,7 +13,7 @@ rows past B*T are scratch and never read back.
 import torch
 
 from . import _lib, ops
-from .ops import _DT, _p, _stream, pad32
+from .ops import _DT, _f32c, _p, _stream, pad32
 
 
 def _vision(clip_vit):
@@ -62,11 +62,6 @@ class ClipVisionPlan:
         return self.cache.get(full, attn.q_proj.weight, build)
 
 
-def _f32(p):
-    p = p.detach()
-    return p if (p.dtype == torch.float32 and p.is_contiguous()) else p.float().contiguous()
-
-
 def forward_features(clip_vit, plan, x, skip_indices, dtype):
     """x [B,3,H,W] fp32 CUDA -> (last hidden state grid, [hidden state grids at skip_indices]) as act tensors
     [B,D,G,G] (NHWC storage, compute dtype), CLS dropped (clipunet.py:48-63)."""
@@ -90,9 +85,7 @@ def forward_features(clip_vit, plan, x, skip_indices, dtype):
         raise RuntimeError(f"ClipViTEncoder: {T} tokens but {emb.position_embedding.weight.shape[0]} position embeddings "
                            "(the reference does not interpolate them either)")
     dev, dt, s = x.device, _DT[dtype], _stream()
-    xin = x.detach()
-    if xin.dtype != torch.float32 or not xin.is_contiguous():
-        xin = xin.float().contiguous()
+    xin = _f32c(x)
     M = B * T
     Mp, Np = (M + 15) // 16 * 16, (B * N + 15) // 16 * 16
     Kp = pad32(C * ps * ps)
@@ -120,9 +113,9 @@ def forward_features(clip_vit, plan, x, skip_indices, dtype):
     wp = plan.linear("patch", emb.patch_embedding.weight, dtype)
     with ops._span("vit_gemm", 2.0 * B * N * Kp * D, 0.0):
         _lib.call("segk_linear", patches.data_ptr(), wp.data_ptr(), 0, proj.data_ptr(), Np, Kp, D, 0, dt, s)
-    _lib.call("segk_vit_embed_ln", proj.data_ptr(), _f32(emb.class_embedding).data_ptr(),
-              _f32(emb.position_embedding.weight).data_ptr(), _f32(vm.pre_layrnorm.weight).data_ptr(),
-              _f32(vm.pre_layrnorm.bias).data_ptr(), eps, h.data_ptr(), B, T, D, D, dt, s)
+    _lib.call("segk_vit_embed_ln", proj.data_ptr(), _f32c(emb.class_embedding).data_ptr(),
+              _f32c(emb.position_embedding.weight).data_ptr(), _f32c(vm.pre_layrnorm.weight).data_ptr(),
+              _f32c(vm.pre_layrnorm.bias).data_ptr(), eps, h.data_ptr(), B, T, D, D, dt, s)
 
     def grid():
         out = torch.empty((B, G, G, D), dtype=dtype, device=dev)
@@ -133,8 +126,8 @@ def forward_features(clip_vit, plan, x, skip_indices, dtype):
     states = {0: grid()} if 0 in want else {}
     layers = vm.encoder.layers
     es = 2 if dtype == torch.bfloat16 else 4
-    _lib.call("segk_add_layernorm", h.data_ptr(), 0, _f32(layers[0].layer_norm1.weight).data_ptr(),
-              _f32(layers[0].layer_norm1.bias).data_ptr(), eps, a.data_ptr(), M, D, D, dt, s)
+    _lib.call("segk_add_layernorm", h.data_ptr(), 0, _f32c(layers[0].layer_norm1.weight).data_ptr(),
+              _f32c(layers[0].layer_norm1.bias).data_ptr(), eps, a.data_ptr(), M, D, D, dt, s)
     for li, layer in enumerate(layers):
         at = layer.self_attn
         wqkv, bqkv = plan.fused_qkv(("qkv", li), at, dtype)
@@ -143,16 +136,16 @@ def forward_features(clip_vit, plan, x, skip_indices, dtype):
         with ops._span("vit_attention", 4.0 * B * heads * T * T * hd, M * 4.0 * D * es):
             _lib.call("segk_attention", qkv.data_ptr(), ctx.data_ptr(), B, T, heads, hd, 3 * D, D, float(hd) ** -0.5, dt, s)
         with ops._span("vit_gemm", 2.0 * M * D * D, 0.0):
-            linear_to_o(ctx, plan.linear(("out", li), at.out_proj.weight, dtype), _f32(at.out_proj.bias), D, S_out)
-        add_ln(S_out, _f32(layer.layer_norm2.weight), _f32(layer.layer_norm2.bias))
+            linear_to_o(ctx, plan.linear(("out", li), at.out_proj.weight, dtype), _f32c(at.out_proj.bias), D, S_out)
+        add_ln(S_out, _f32c(layer.layer_norm2.weight), _f32c(layer.layer_norm2.bias))
         with ops._span("vit_gemm", 2.0 * M * D * I, 0.0):
             _lib.call("segk_linear", a.data_ptr(), plan.linear(("fc1", li), layer.mlp.fc1.weight, dtype).data_ptr(),
-                      _f32(layer.mlp.fc1.bias).data_ptr(), f.data_ptr(), Mp, D, I, 1, dt, s)
+                      _f32c(layer.mlp.fc1.bias).data_ptr(), f.data_ptr(), Mp, D, I, 1, dt, s)
         with ops._span("vit_gemm", 2.0 * M * D * I, 0.0):
-            linear_to_o(f, plan.linear(("fc2", li), layer.mlp.fc2.weight, dtype), _f32(layer.mlp.fc2.bias), I, S_fc2)
+            linear_to_o(f, plan.linear(("fc2", li), layer.mlp.fc2.weight, dtype), _f32c(layer.mlp.fc2.bias), I, S_fc2)
         if li + 1 < L:      # residual add fused with the next layer's layer_norm1
             nxt = layers[li + 1]
-            add_ln(S_fc2, _f32(nxt.layer_norm1.weight), _f32(nxt.layer_norm1.bias))
+            add_ln(S_fc2, _f32c(nxt.layer_norm1.weight), _f32c(nxt.layer_norm1.bias))
         else:               # last layer: add only (last_hidden_state is taken before post_layernorm)
             add_ln(S_fc2, None, None)
         if li + 1 in want:

@@ -186,3 +186,36 @@ def test_eval_reconstruction(seg, trace):
     ret = training.evalReconstruction([([imgs[0], imgs[1]], None), ([imgs[2]], None)], m, seg.MSELoss(), 32)
     assert not m.training and np.isfinite(ret[0]) and isinstance(ret[1], np.float64)
     check("evalReconstruction", trace, ret)
+
+
+def test_clip_decoder_steps(seg, trace):
+    """Two steps of forward, CrossEntropyLoss, backward and AdamW(fused=True) on the CLIP decoder, wrapped as in
+    tests/test_gpu_clip.py::test_clip_decoder_one_launch_repack_after_optimizer_step: the backward of Conv1x1Fn, of the
+    stand-alone ConvT2x2Fn and of BilinearFn, and in the second forward the one-launch repack with its kind 2 and 3 entries
+    (segk_pack_multi with its n and total_blocks).  This case of the fixture is a record of the commit BEFORE the fused-op
+    host layer was folded onto one operand path and one packed-weight record."""
+    from image_segmentation_amd import ops
+    dec = seg.UNetDecoder(64, [64, 32, 32, 32, 32]); head = torch.nn.Conv2d(32, 4, 1)
+
+    class Wrap(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.decoder, self.output_layer = dec, head
+
+        def forward(self, x, skips):
+            ops.repack_stale(self)
+            return self.decoder(x, skips, head=self.output_layer)
+    m = Wrap(); fill_module(m, 4100); m.cuda().train()
+    opt = torch.optim.AdamW(m.parameters(), lr=1e-2, fused=True)
+    x = fill((2, 64, 4, 4), 11, -1, 1).cuda()
+    skips = [fill((2, 64, 4, 4), 20 + i, -1, 1).cuda() for i in range(4)]
+    Y = labels((2, 64, 64), 3, 4).cuda()
+    loss_fn, losses = seg.CrossEntropyLoss(), []
+    for _ in range(2):
+        loss = loss_fn(m(x, skips), Y)
+        loss.backward(); opt.step(); opt.zero_grad(set_to_none=True)
+        losses.append(loss.item())
+    assert all(np.isfinite(v) for v in losses)
+    names = [c[0] for c in trace]
+    assert names.count("segk_pack_multi") == 1 and "segk_bilinear_bwd" in names and "segk_convt2x2_dgrad" in names
+    check("clip_decoder_steps", trace, tuple(losses))

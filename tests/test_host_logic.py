@@ -167,6 +167,55 @@ def test_pack_cache_follows_fused_optimizer_steps():
     assert cache.get("q", q, build) != first
 
 
+def test_f32c_is_zero_copy_on_fp32_contiguous_and_normalises_the_rest():
+    """ops._f32c hands a float32 contiguous operand through in its own storage (no copy, no kernel), detached; every other
+    dtype or layout comes back float32 contiguous with the same values."""
+    p = torch.nn.Parameter(fill((5, 7), 3, -1, 1))
+    t = ops._f32c(p)
+    assert t.data_ptr() == p.data_ptr() and t.requires_grad is False and t.shape == p.shape
+    base = fill((6, 4), 4, -1, 1)
+    for src in (base.double(), base.bfloat16(), base.t()):
+        out = ops._f32c(src)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == src.shape and not out.requires_grad
+        assert torch.equal(out, src.float())
+
+
+def test_pack_table_bytes_follow_the_native_entry_layout():
+    """The table ops.repack_stale uploads for segk_pack_multi, one entry of each kind, against struct SegkPackEntry of
+    csrc/segk_internal.h written out here:
+        const float* w; void* dst_fwd; void* dst_dgrad; int Cout, CA, CB, Coutp, CAp, CBp; int block0; int kind; int pad_[2];
+    64 bytes, entries in launch order, block0 the running sum of the entries' block counts (include/segk.h: kind 0
+    (CAp+CBp)/32 * Coutp/32 blocks, kinds 1 and 3 ceil(elements / segk_pack_convt_chunk()), kind 2 one block)."""
+    import ctypes
+    import struct
+    from image_segmentation_amd import _lib
+    E = _lib.PackEntry
+    assert ctypes.sizeof(E) == 64
+    offsets = {"w": 0, "dst_fwd": 8, "dst_dgrad": 16, "Cout": 24, "CA": 28, "CB": 32, "Coutp": 36, "CAp": 40, "CBp": 44,
+               "block0": 48, "kind": 52}
+    assert {f: getattr(E, f).offset for f in offsets} == offsets
+    assert (ops.PACK_CONV3X3, ops.PACK_CONVT, ops.PACK_BIAS, ops.PACK_CONV1X1) == (0, 1, 2, 3)
+    chunk = _lib.query("segk_pack_convt_chunk")
+    assert chunk > 0
+    params = [torch.zeros(40, 24, 3, 3), torch.zeros(24, 40, 2, 2), torch.zeros(40), torch.zeros(40, 24, 1, 1)]
+    A = 0x7F0000000000          # made-up addresses above 2^32: all 64 bits of a pointer have to arrive
+    sig = ((A + 0x100, A + 0x1100, A + 0x2100, 0, 16, 8), (A + 0x3100, A + 0x4100, A + 0x5100, 1, 0, 0),
+           (A + 0x6100, A + 0x7100, 0, 2, 0, 0), (A + 0x8100, 0xFFFFFFFFFFFFFF00, 0, 3, 24, 0))
+    # Cout, CA, CB, Coutp, CAp, CBp and the block count of each, from the rules above (pad to 32: 40 -> 64, 24/16/8 -> 32)
+    dims = [(40, 16, 8, 64, 32, 32), (40, 24, 0, 64, 32, 0), (40, 0, 0, 64, 0, 0), (40, 24, 0, 64, 32, 0)]
+    blocks = [(32 + 32) // 32 * (64 // 32), -(-32 * 4 * 64 // chunk), 1, -(-32 * 64 // chunk)]
+    elements = [(32 + 32) * 9 * 64, 32 * 4 * 64, 4 * 64, 32 * 64]
+    for (_, _, _, kind, d0, d1), p, dm, nb, n in zip(sig, params, dims, blocks, elements):
+        assert ops._entry_geometry(kind, p, d0, d1) == (n, dm, nb)
+    tab, total = ops._pack_table(sig, params)
+    assert total == sum(blocks) and len(tab) == 4
+    want = b"".join(struct.pack("<3Q8i2i", s[0], s[1], s[2], *dm, sum(blocks[:i]), s[3], 0, 0)
+                    for i, (s, dm) in enumerate(zip(sig, dims)))
+    assert bytes(tab) == want
+    assert [e.block0 for e in tab] == [0, blocks[0], blocks[0] + blocks[1], blocks[0] + blocks[1] + 1]
+    assert torch.frombuffer(tab, dtype=torch.int64).numpy().tobytes() == want      # what repack_stale uploads
+
+
 def test_nll_nonlin_recognition():
     from image_segmentation_amd.losses import _log_eps
     assert _log_eps(None) == (0, 0.0)
