@@ -829,6 +829,53 @@ def _head_bwd(dlogits, px, Cp, w, B, C, H, W, dtype, dev, bn=None, on_z=False):
     return dy, dw, db, ready
 
 
+def _grad_refs(g):
+    """(TensorImpl use count or None, Python reference count) of a gradient a backward was handed."""
+    uc = getattr(g, "_use_count", None)
+    return (None if uc is None else uc(), sys.getrefcount(g))
+
+
+class _GradRefsProbeFn(torch.autograd.Function):
+    """Two outputs, each consumed once by a stock op: what _grad_refs reads for a gradient that only the engine and the
+    backward's own frame hold, taken at the same call depth as DoubleConvFn._backward takes it."""
+    seen = None
+
+    @staticmethod
+    def forward(ctx, x):
+        return x * 2.0, x * 3.0
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return _GradRefsProbeFn._backward(ctx, *grads)
+
+    @staticmethod
+    def _backward(ctx, *grads):
+        dy, dpool = grads
+        refs = _grad_refs(dy)
+        _GradRefsProbeFn.seen = refs
+        return dy * 2.0 + dpool * 3.0
+
+
+_UNSHARED_GRAD_REFS = []
+
+
+def _unshared_grad_refs():
+    """_grad_refs of a gradient nobody but the engine holds (measured once, on a four-element CPU graph).  A torch without
+    Tensor._use_count reads (None, n) in a backward and is recorded as (-1, n) here: never equal, every gradient counts as
+    shared and takes the private copy (see DoubleConvFn._backward)."""
+    if not _UNSHARED_GRAD_REFS:
+        with torch.inference_mode(False), torch.enable_grad():
+            x = torch.ones(4, requires_grad=True)
+            a, b = _GradRefsProbeFn.apply(x)
+            (a.sum() + b.sum()).backward()
+        uc, rc = _GradRefsProbeFn.seen
+        _UNSHARED_GRAD_REFS.append((uc if uc is not None else -1, rc))     # no use count to read: nothing compares equal
+    return _UNSHARED_GRAD_REFS[0]
+
+
+_unshared_grad_refs()           # at import, outside any backward: the probe is a backward of its own
+
+
 class BlockCfg:
     """Static (non-tensor) configuration of one DoubleConvFn call."""
     __slots__ = ("mod", "up_mod", "emit_pool")
@@ -865,6 +912,9 @@ class DoubleConvFn(torch.autograd.Function):
     @staticmethod
     def _forward(ctx, cfg, xa, xb, w1, b1, g1, be1, w2, b2, g2, be2, up_x, up_w, up_b, head_w, head_b):
         mod = cfg.mod
+        # an output nobody consumed hands backward None, not a tensor of zeros: with emit_pool a block whose pooled tensor
+        # goes unused then runs no pooling backward over zeros and equals the plain block bit for bit
+        ctx.set_materialize_grads(False)
         dtype = mod.compute_dtype or _compute_dtype
         _require_cuda(xa, "DoubleConvReLU")
         dev = xa.device
@@ -1022,7 +1072,11 @@ class DoubleConvFn(torch.autograd.Function):
             pdy, keep = dy_buf.data_ptr(), dy_buf
         elif cfg.emit_pool:
             dy, dpool = grads
-            rc_skip, rc_pool = sys.getrefcount(dy), sys.getrefcount(dpool)   # before anything below takes references
+            if dy is None and dpool is not None:
+                # the skip output went unused (the autoencoders' encoder blocks): its gradient as the zeros autograd
+                # materialises by default, through the same conversion and accumulating pooling backward as ever
+                dy = torch.zeros((B, Cout, H, W), dtype=dtype, device=dev)
+            refs = _grad_refs(dy)              # before anything below takes references
             if dpool is None:
                 keep, pdy, _ = _raw(dy, dtype)
             else:
@@ -1037,13 +1091,13 @@ class DoubleConvFn(torch.autograd.Function):
                     # else can still see: with a tensor hook on the skip tensor (register_hook: the hook may keep the
                     # tensor it is handed; retain_grad() clones and is safe) the sum goes to a private copy instead.
                     # Autograd itself can hold it too: torch.autograd.grad(loss, [skip]) CAPTURES the very tensor this
-                    # backward is handed (no clone).  Every other holder shows in the tensor's reference counts -- the
-                    # engine's input buffer and this frame account for a TensorImpl use count of 2, a capture makes it 3;
-                    # a hook that outlived the Python skip tensor and stashed its argument raises the Python reference
-                    # count above that of the sibling gradient that arrived in the same tuple.
+                    # backward is handed (no clone).  Every other holder shows in the tensor's reference counts (a capture
+                    # in the TensorImpl use count; a hook that outlived the Python skip tensor and stashed its argument in
+                    # the Python reference count), so both are held against the counts of a gradient nobody else can see,
+                    # measured by _unshared_grad_refs() in this interpreter and this torch.  The sibling gradient is no
+                    # yardstick: hooks that keep both move both counts alike.  Any other value takes the private copy.
                     yo = getattr(ctx, "y_ref", lambda: None)()
-                    uc = getattr(dy, "_use_count", None)
-                    shared = uc is None or uc() > 2 or rc_skip > rc_pool
+                    shared = refs != _unshared_grad_refs()
                     hooked = INPLACE_SKIP_GRAD is False or shared or (yo is not None and bool(yo._backward_hooks))
                     keep, pdy, _ = _raw(dy, dtype)
                     if hooked and keep.data_ptr() == dy.data_ptr():      # zero-copy act tensor: the caller's own storage
