@@ -515,7 +515,9 @@ extern "C" int segk_wgrad_reduce_multi(const segk_reduce_job* jobs, int n, segk_
 extern "C" int segk_wgrad_reduce(const float* slabs, int S, float* grad, int N, int CA, int CB, int Np, int CAp, int CBp,
                                  int taps, segk_stream_t s) {
   hipStream_t st = (hipStream_t)s;
-  SEGK_REQUIRE(slabs && grad && S > 0 && N > 0 && CA > 0 && CB >= 0 && Np >= N && CAp >= CA && CBp >= CB && taps > 0,
+  // the kernels walk a row as taps * (CAp + CBp) / 4 float4 vectors whose four lanes share a tap (as the multi entry requires)
+  SEGK_REQUIRE(slabs && grad && S > 0 && N > 0 && CA > 0 && CB >= 0 && Np >= N && CAp >= CA && CBp >= CB && taps > 0 &&
+                   (CAp + CBp) % 32 == 0,
                "wgrad_reduce: bad arguments");
   if (S > 16) {      // many thin slabs (narrow layers): slab-parallel reduction, one launch
     const int nvec = taps * (CAp + CBp) / 4;

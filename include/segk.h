@@ -139,6 +139,9 @@ int segk_wgrad(const void* dz, const void* srcA, const void* srcB, const float* 
                float* slabs, const void* zeros64, int S, int B, int H, int W, int CD, int CA, int CB, int geo,
                int dtype, segk_stream_t s);   /* zeros64: >= 64 zero bytes in device memory (halo source of the
                                                   LDS-DMA path); NULL selects the register-staged kernel */
+/* slabs [S][Np][taps][CAp+CBp] -> grad [N][CA+CB][taps]: rows n >= N and the padding columns of either source are skipped.
+ * CAp + CBp must be a multiple of 32 (refused otherwise); S <= 16 stages one gradient row of (CA+CB)*taps floats in LDS
+ * (at most 64 KiB), S > 16 takes the slab-parallel form. */
 int segk_wgrad_reduce(const float* slabs, int S, float* grad, int N, int CA, int CB, int Np, int CAp, int CBp,
                       int taps, segk_stream_t s);
 /* Up to four such reductions in ONE launch -- the two weight gradients of a DoubleConv block (unet.py:16,19), the
