@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 320          # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 321          # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
@@ -42,6 +42,7 @@ SIGNATURES = {
     "segk_stem3x3": (_i, [_fp, _fp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_stem3x3_wgrad_slabs": (_i, [_i, _i, _i, _i, _i, _i]),
     "segk_stem3x3_wgrad": (_i, [_fp, _vp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_stem3x3_wgrad_bn": (_i, [_fp, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_conv1x1": (_i, [_vp, _vp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_convt2x2_fwd": (_i, [_vp, _vp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_convt2x2_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -61,6 +62,7 @@ SIGNATURES = {
     "segk_maxpool_bwd_stat_blocks": (_i, [_i, _i, _i, _i, _i]),
     "segk_maxpool2x2_bwd_bnstat": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _vp, _i, _vp]),
     "segk_bn_relu_bwd_from_part": (_i, [_vp, _vp, _vp, _fp, _fp, _fp, _fp, _l, _i, _i, _fp, _i, _fp, _fp, _fp, _i, _vp]),
+    "segk_bn_relu_bwd_stats": (_i, [_vp, _vp, _fp, _fp, _fp, _fp, _l, _i, _i, _fp, _fp, _fp, _fp, _i, _vp]),
     "segk_bilinear_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_bilinear_bwd": (_i, [_vp, _vp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_linear": (_i, [_vp, _vp, _fp, _vp, _l, _i, _i, _i, _i, _vp]),
@@ -89,6 +91,8 @@ SIGNATURES = {
     "segk_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd_bn": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_bn": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),
+    "segk_head_bwd_bn_stats": (_i, [_fp, _vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),
+    "segk_head_bn_bwd_apply": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i, _vp]),
     "segk_head_part_floats": (_i, [_l, _i]),
     "segk_head_bwd": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_blocks": (_i, [_l]),

@@ -62,6 +62,13 @@ int segk_stem3x3_wgrad(const float* x_nchw, const void* dz, float* slabs, int B,
   SEGK_REQUIRE(dtype == SEGK_DT_BF16, "stem3x3_wgrad: bf16 only (dtype %d)", dtype);
   return segk_stem_wgrad_launch(x_nchw, dz, slabs, B, H, W, Cin, Cout, (hipStream_t)s);
 }
+int segk_stem3x3_wgrad_bn(const float* x_nchw, const void* da, const void* z, const float* scale, const float* shift,
+                          const float* mean, const float* rstd, const float* coef, float* slabs, int B, int H, int W, int Cin,
+                          int Cout, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE(dtype == SEGK_DT_BF16, "stem3x3_wgrad_bn: bf16 only (dtype %d)", dtype);
+  const float* bn[4] = {scale, shift, mean, rstd};
+  return segk_stem_wgrad_bn_launch(x_nchw, da, z, bn, coef, slabs, B, H, W, Cin, Cout, (hipStream_t)s);
+}
 int segk_stem3x3(const float* x_nchw, const float* w_oihw, void* z, void* x_nhwc, float* stats, int B, int H, int W, int Cin,
                  int Cout, int dtype, segk_stream_t s) {
   SEGK_REQUIRE(dtype == SEGK_DT_BF16, "stem3x3: bf16 only (dtype %d)", dtype);

@@ -355,11 +355,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     unpack16<T>(rz, fz);
     unpack16<T>(rd, fd);
 #pragma unroll
-    for (int j = 0; j < E::VEC; ++j) {
-      const float g = (fmaf(fz[j], sc[j], sh[j]) > 0.f) ? fd[j] : 0.f;
-      const float xh = (fz[j] - mu[j]) * rs[j];
-      fd[j] = sc[j] * (g - c1[j] - xh * c2[j]);
-    }
+    for (int j = 0; j < E::VEC; ++j) fd[j] = bn_relu_bwd_dz(fz[j], fd[j], sc[j], sh[j], mu[j], rs[j], c1[j], c2[j]);
     *(uint4*)(dz + off) = pack16<T>(fd);
   };
   // APF pixels (2 APF loads) per thread in flight, all issued before the first store (dz may be dy or z: in place allowed,
@@ -779,6 +775,15 @@ extern "C" int segk_bn_relu_apply_pool(const void* z, void* y, void* pooled, con
   return 0;
 }
 
+// partial rows [nb][C][2] -> dgamma, dbeta, coef: the finalize step of every BatchNorm backward form
+int segk_bn_bwd_finalize_launch(const float* part, int nb, int C, int C_real, long P, float* dgamma, float* dbeta, float* coef,
+                                hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C / 32), dim3(1024), 0, st, part, nb, C, C_real, (double)P, dgamma, dbeta,
+                     coef);
+  SEGK_CHECK_LAUNCH("bn_bwd_finalize");
+  return 0;
+}
+
 int segk_bn_bwd_blocks(long P, int C, int dtype) {
   if (P <= 0 || C <= 0 || C % 32 != 0) return 0;      // nonsense input: no blocks (the launch entries refuse it)
   const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
@@ -840,6 +845,32 @@ extern "C" int segk_bn_relu_bwd_from_part(const void* dy, const void* z, void* d
   return dtype == SEGK_DT_BF16
              ? bn_bwd_from_part_t<bf16_t>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, nb, dgamma, dbeta, coef, st)
              : bn_bwd_from_part_t<float>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, nb, dgamma, dbeta, coef, st);
+}
+
+// reduce + finalize only (no apply pass: the consumer of dz forms it in registers, segk_stem3x3_wgrad_bn)
+template <typename T>
+static int bn_bwd_stats_t(const void* dy, const void* z, const float* scale, const float* shift, const float* mean,
+                          const float* rstd, long P, int C, int C_real, float* part, float* dgamma, float* dbeta, float* coef,
+                          hipStream_t st) {
+  using E = ET<T>;
+  int cvb, rows, gy;
+  lane_geometry(C, E::VEC, &cvb, &rows, &gy);
+  const int gx = segk_bn_bwd_blocks(P, C, sizeof(T) == 2 ? SEGK_DT_BF16 : SEGK_DT_F32);
+  const size_t lds = (size_t)rows * cvb * 2 * E::VEC * sizeof(float);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(gx, gy), dim3(256), lds, st, (const T*)dy, (const T*)z, scale, shift,
+                     mean, rstd, P, C, cvb, rows, part);
+  SEGK_CHECK_LAUNCH("bn_bwd_reduce");
+  return segk_bn_bwd_finalize_launch(part, gx, C, C_real, P, dgamma, dbeta, coef, st);
+}
+extern "C" int segk_bn_relu_bwd_stats(const void* dy, const void* z, const float* scale, const float* shift, const float* mean,
+                                      const float* rstd, long P, int C, int C_real, float* part, float* dgamma, float* dbeta,
+                                      float* coef, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("bn_relu_bwd_stats", dtype);
+  hipStream_t st = (hipStream_t)s;
+  SEGK_REQUIRE(dy && z && scale && shift && mean && rstd && part && dgamma && dbeta && coef, "bn_bwd_stats: null pointer");
+  SEGK_REQUIRE(P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_bwd_stats: bad shape");
+  return dtype == SEGK_DT_BF16 ? bn_bwd_stats_t<bf16_t>(dy, z, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st)
+                               : bn_bwd_stats_t<float>(dy, z, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st);
 }
 
 extern "C" int segk_bn_relu_bwd(const void* dy, const void* z, void* dz, const float* scale, const float* shift,

@@ -87,6 +87,15 @@ template <typename T> __device__ __forceinline__ float to_float(T v);
 template <> __device__ __forceinline__ float to_float<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_float<bf16_t>(bf16_t v) { return (float)v; }
 
+// BatchNorm + ReLU backward, one element: dz = scale * (g - c1 - xhat * c2) with g = d where the ReLU was active,
+// xhat = (z - mean) * rstd and (c1, c2) = (sum g, sum g * xhat) / N.  Stated ONCE: bn_bwd_apply_kernel and the kernels that
+// form dz in registers (head_bn_bwd_apply_kernel, stem_wgrad_kernel<BN>) must agree bit for bit.
+__device__ __forceinline__ float bn_relu_bwd_dz(float z, float d, float sc, float sh, float mu, float rs, float c1, float c2) {
+  const float g = (fmaf(z, sc, sh) > 0.f) ? d : 0.f;
+  const float xh = (z - mu) * rs;
+  return sc * (g - c1 - xh * c2);
+}
+
 // Conv epilogue helper: the 16 fp32 results one lane holds of a 32x32 accumulator fragment (one output channel,
 // pixel rows (r & 3) + 8 (r >> 2) of the fragment) -> running per-channel (sum, sum of squares) for
 // training-mode BatchNorm, and stores into the [pixel][channel] LDS staging tile (row pitch OP bytes).

@@ -144,7 +144,8 @@ template <> struct HeadVec<bf16_t> {
   static __device__ __forceinline__ Raw pack(const float* f) { return pack_n(f, std::integral_constant<int, HV>{}); }
 };
 
-template <typename T, int NC, bool ZIN>
+// STORE = false: everything but the store of dy (segk_head_bwd_bn_stats: head_bn_bwd_apply_kernel below re-forms dy per element)
+template <typename T, int NC, bool ZIN, bool STORE = true>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dlog, const T* __restrict__ y,
                                                        const float* __restrict__ w, T* __restrict__ dy,
                                                        float* __restrict__ part, long P, long HW, int Cp, int C,
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
           aw[k][j] = fmaf(dl[k], f[j], aw[k][j]);
         }
       }
-      *(Raw*)(dy + (size_t)p * Cp + cv * HV) = HeadVec<T>::pack(o);
+      if constexpr (STORE) *(Raw*)(dy + (size_t)p * Cp + cv * HV) = HeadVec<T>::pack(o);
       if (stat) {
 #pragma unroll
         for (int j = 0; j < HV; ++j) {
@@ -334,6 +335,69 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
   if (lane != 0) return;
   if (c == C) db[k] = (float)s;
   else dw[(size_t)k * C + c] = (float)s;
+}
+
+// BatchNorm + ReLU backward apply pass of the block in front of the head WITHOUT a stored dy (the 64-channel gradient at full
+// resolution is larger than the Infinity Cache: written, read back once, dropped).  dy[p][c] = sum_k dl[p][k] * W[k][c] is
+// re-formed per element exactly as head_bwd_kernel forms it (k ascending from 0.f, the same compiled class count, rounded to T
+// like the stored tensor), then bn_relu_bwd_dz: dz is bit-identical to segk_head_bwd_bn + segk_bn_relu_bwd_from_part.
+// A thread owns one channel vector and walks pixels; the vector is head_bwd_kernel's (bf16: four channels, 8 bytes), not the
+// 16 bytes of bn_bwd_apply_kernel: beside six BatchNorm constants per channel the NC weights per channel make 8 channels
+// 138 registers (3 waves per SIMD; 268 MB took 173 us, no faster than the stored apply pass), 4 channels about 80.
+// One pixel in flight per thread: a two-pixel form measured 256 against 253 us for statistics + apply at B = 32, 64 ch x 256^2
+// (same box, 2 us spread; profiles/end_fusion_kbench.txt) -- like bn_bwd_apply_kernel, a pass that writes as much as it reads
+// gains nothing from more loads in flight.
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const float* __restrict__ dlog, const T* __restrict__ z,
+                                                                const float* __restrict__ w, T* __restrict__ dz,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const float* __restrict__ coef, long P, long HW, int Cp, int C,
+                                                                int ncls, int cvb, int rows) {
+  constexpr int V = HeadVec<T>::HV;
+  using Raw = typename HeadVec<T>::Raw;
+  const int cx = threadIdx.x % cvb, ry = threadIdx.x / cvb;
+  const int cv = blockIdx.y * cvb + cx;
+  if (cv >= Cp / V || ry >= rows) return;
+  float sc[V], sh[V], mu[V], rs[V], c1[V], c2[V], wr[NC][V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const int c = cv * V + j;
+    sc[j] = scale[c]; sh[j] = shift[c]; mu[j] = mean[c]; rs[j] = rstd[c];
+    c1[j] = coef[2 * c]; c2[j] = coef[2 * c + 1];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) wr[k][j] = (k < ncls && c < C) ? w[(size_t)k * C + c] : 0.f;
+  }
+  auto pixel = [&](long p, const float (&dl)[NC], const Raw raw) {
+    float fz[V], o[V];
+    HeadVec<T>::unpack(raw, fz);
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = fmaf(dl[k], wr[k][j], o[j]);
+    HeadVec<T>::unpack(HeadVec<T>::pack(o), o);      // the value the stored dy would have held
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = bn_relu_bwd_dz(fz[j], o[j], sc[j], sh[j], mu[j], rs[j], c1[j], c2[j]);
+    *(Raw*)(dz + (size_t)p * Cp + cv * V) = HeadVec<T>::pack(o);
+  };
+  // the (image, offset) of the thread's pixel is carried along instead of divided out per pixel, as in head_bwd_kernel
+  const long step = (long)gridDim.x * rows;
+  long p = (long)blockIdx.x * rows + ry, b = 0, r = 0;
+  if (p < P) split_hw(p, HW, b, r);
+  for (; p < P; p += step) {
+    const Raw raw = *(const Raw*)(z + (size_t)p * Cp + cv * V);
+    float dl[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {   // unconditional loads (class index clamped), selected afterwards
+      const float v = dlog[(b * ncls + (k < ncls ? k : ncls - 1)) * HW + r];
+      dl[k] = (k < ncls) ? v : 0.f;
+    }
+    pixel(p, dl, raw);
+    r += step;
+    while (r >= HW) { r -= HW; ++b; }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -666,7 +730,7 @@ extern "C" int segk_head_fwd_bn(const void* z, const float* scale, const float* 
 
 template <typename T>
 static int head_bwd_t(const float* dlog, const void* y, const float* w, void* dy, float* part, float* dw, float* db,
-                      long P, long HW, int Cp, int C, int ncls, const float* const* bn, float* bnpart, bool zin,
+                      long P, long HW, int Cp, int C, int ncls, const float* const* bn, float* bnpart, bool zin, bool store,
                       hipStream_t st) {
   constexpr int HV = HeadVec<T>::HV;
   const int cvec = Cp / HV;
@@ -676,13 +740,16 @@ static int head_bwd_t(const float* dlog, const void* y, const float* w, void* dy
   const size_t lds = (size_t)rows * cvb * (MAXC * HV + MAXC) * sizeof(float);
   // gy > 1 (more than 64 channel vectors: above 256 channels): blockIdx.y slices the channels; every slice walks the
   // block's pixels and writes its own columns of the partial rows (tests/test_gpu_kernels.py at 288 and 512 channels)
-  auto launch_z = [&](auto NCc, auto ZINc) {
+  auto launch_z = [&](auto NCc, auto ZINc, auto STOREc) {
     constexpr int NC = decltype(NCc)::value;
-    return segk_launch_lds<head_bwd_kernel<T, NC, decltype(ZINc)::value>>(
+    return segk_launch_lds<head_bwd_kernel<T, NC, decltype(ZINc)::value, decltype(STOREc)::value>>(
         "head_bwd", 96 * 1024, dim3(nb, gy), dim3(256), lds, st, dlog, (const T*)y, w, (T*)dy, part, P, HW, Cp, C, ncls, cvb, rows,
         bn ? bn[0] : nullptr, bn ? bn[1] : nullptr, bn ? bn[2] : nullptr, bn ? bn[3] : nullptr, bnpart);
   };
-  auto launch = [&](auto NCc) { return zin ? launch_z(NCc, std::true_type{}) : launch_z(NCc, std::false_type{}); };
+  auto launch = [&](auto NCc) {      // the form without the store exists on the pre-activation input only
+    if (!store) return launch_z(NCc, std::true_type{}, std::false_type{});
+    return zin ? launch_z(NCc, std::true_type{}, std::true_type{}) : launch_z(NCc, std::false_type{}, std::true_type{});
+  };
   const int rc = ncls <= 2 ? launch(std::integral_constant<int, 2>{})
                : ncls == 3 ? launch(std::integral_constant<int, 3>{})
                : ncls == 4 ? launch(std::integral_constant<int, 4>{})
@@ -693,11 +760,13 @@ static int head_bwd_t(const float* dlog, const void* y, const float* w, void* dy
   return 0;
 }
 
-// bnpart: also reduce the BatchNorm backward partials of the layer in front; zin: y is that layer's pre-activation
+// bnpart: also reduce the BatchNorm backward partials of the layer in front; zin: y is that layer's pre-activation;
+// store = 0 (zin only): dy is not written (null)
 static int head_bwd(const float* dlog, const void* y, const float* w, void* dy, float* part, float* dw, float* db, int B, int H,
                     int W, int Cp, int C, int ncls, const float* bn_scale, const float* bn_shift, const float* bn_mean,
-                    const float* bn_rstd, float* bnpart, int zin, int dtype, hipStream_t st) {
-  SEGK_REQUIRE(dlog && y && w && dy && part && dw && db && B > 0 && H > 0 && W > 0, "head_bwd: bad arguments");
+                    const float* bn_rstd, float* bnpart, int zin, int store, int dtype, hipStream_t st) {
+  SEGK_REQUIRE(dlog && y && w && (dy || !store) && part && dw && db && B > 0 && H > 0 && W > 0, "head_bwd: bad arguments");
+  SEGK_REQUIRE(store || zin, "head_bwd: the form without dy reads the pre-activation");
   SEGK_REQUIRE(ncls >= 1 && ncls <= MAXC && Cp % 32 == 0 && C > 0 && C <= Cp, "head_bwd: bad channels/classes");
   SEGK_REQUIRE_DTYPE("head_bwd", dtype);
   SEGK_REQUIRE(!(bnpart || zin) || (bn_scale && bn_shift && bn_mean && bn_rstd),
@@ -706,13 +775,13 @@ static int head_bwd(const float* dlog, const void* y, const float* w, void* dy, 
   SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
   const float* bn[4] = {bn_scale, bn_shift, bn_mean, bn_rstd};
   const float* const* bnp = (bnpart || zin) ? bn : nullptr;
-  return dtype == SEGK_DT_BF16 ? head_bwd_t<bf16_t>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, st)
-                               : head_bwd_t<float>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, st);
+  return dtype == SEGK_DT_BF16 ? head_bwd_t<bf16_t>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, store != 0, st)
+                               : head_bwd_t<float>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, store != 0, st);
 }
 extern "C" int segk_head_bwd(const float* dlogits, const void* y, const float* w, void* dy, float* part, float* dw, float* db,
                              int B, int H, int W, int Cp, int C, int ncls, int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("head_bwd", dtype);
-  return head_bwd(dlogits, y, w, dy, part, dw, db, B, H, W, Cp, C, ncls, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dtype,
+  return head_bwd(dlogits, y, w, dy, part, dw, db, B, H, W, Cp, C, ncls, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, dtype,
                   (hipStream_t)s);
 }
 extern "C" int segk_head_bwd_blocks(long P) { return segk_head_blocks(P); }
@@ -722,15 +791,61 @@ extern "C" int segk_head_bwd_bnstat(const float* dlogits, const void* y, const f
                                     segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("head_bwd_bnstat", dtype);
   SEGK_REQUIRE(bnpart, "head_bwd_bnstat: null partials");
-  return head_bwd(dlogits, y, w, dy, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 0, dtype,
+  return head_bwd(dlogits, y, w, dy, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 0, 1, dtype,
                   (hipStream_t)s);
 }
 extern "C" int segk_head_bwd_bn(const float* dlogits, const void* z, const float* w, void* dy, float* part, float* dw, float* db,
                                 int B, int H, int W, int Cp, int C, int ncls, const float* scale, const float* shift,
                                 const float* mean, const float* rstd, float* bnpart, int dtype, segk_stream_t s) {
   SEGK_REQUIRE(scale && shift && mean && rstd, "head_bwd_bn: null BatchNorm vectors");
-  return head_bwd(dlogits, z, w, dy, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 1, dtype,
+  return head_bwd(dlogits, z, w, dy, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 1, 1, dtype,
                   (hipStream_t)s);
+}
+extern "C" int segk_head_bwd_bn_stats(const float* dlogits, const void* z, const float* w, float* part, float* dw, float* db, int B,
+                                      int H, int W, int Cp, int C, int ncls, const float* scale, const float* shift,
+                                      const float* mean, const float* rstd, float* bnpart, int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("head_bwd_bn_stats", dtype);
+  SEGK_REQUIRE(scale && shift && mean && rstd && bnpart, "head_bwd_bn_stats: null BatchNorm vectors / partials");
+  return head_bwd(dlogits, z, w, nullptr, part, dw, db, B, H, W, Cp, C, ncls, scale, shift, mean, rstd, bnpart, 1, 0, dtype,
+                  (hipStream_t)s);
+}
+
+template <typename T>
+static int head_bn_bwd_apply_t(const float* dlog, const void* z, const float* w, void* dz, const float* const* bn,
+                               const float* coef, long P, long HW, int Cp, int C, int ncls, hipStream_t st) {
+  const int cvec = Cp / HeadVec<T>::HV;       // the block geometry of head_bwd_t
+  const int cvb = cvec < 64 ? cvec : 64;
+  const int rows = 256 / cvb, gy = cdiv(cvec, cvb);
+  long ga = (P + rows - 1) / rows;
+  if (ga > 4096) ga = 4096;
+  auto launch = [&](auto NCc) {      // the compiled class counts of head_bwd_t: the sum over k runs over the same terms
+    constexpr int NC = decltype(NCc)::value;
+    hipLaunchKernelGGL((head_bn_bwd_apply_kernel<T, NC>), dim3((int)ga, gy), dim3(256), 0, st, dlog, (const T*)z, w, (T*)dz, bn[0],
+                       bn[1], bn[2], bn[3], coef, P, HW, Cp, C, ncls, cvb, rows);
+  };
+  if (ncls <= 2) launch(std::integral_constant<int, 2>{});
+  else if (ncls == 3) launch(std::integral_constant<int, 3>{});
+  else if (ncls == 4) launch(std::integral_constant<int, 4>{});
+  else launch(std::integral_constant<int, MAXC>{});
+  SEGK_CHECK_LAUNCH("head_bn_bwd_apply");
+  return 0;
+}
+extern "C" int segk_head_bn_bwd_apply(const float* dlogits, const void* z, const float* w, void* dz, const float* scale,
+                                      const float* shift, const float* mean, const float* rstd, int B, int H, int W, int Cp,
+                                      int C, int ncls, const float* bnpart, int nb, float* dgamma, float* dbeta, float* coef,
+                                      int dtype, segk_stream_t s) {
+  SEGK_REQUIRE_DTYPE("head_bn_bwd_apply", dtype);
+  hipStream_t st = (hipStream_t)s;
+  SEGK_REQUIRE(dlogits && z && w && dz && dz != z && scale && shift && mean && rstd && bnpart && dgamma && dbeta && coef &&
+                   B > 0 && H > 0 && W > 0 && nb > 0,
+               "head_bn_bwd_apply: bad arguments");
+  SEGK_REQUIRE(ncls >= 1 && ncls <= MAXC && Cp % 32 == 0 && C > 0 && C <= Cp, "head_bn_bwd_apply: bad channels/classes");
+  const long P = (long)B * H * W, HW = (long)H * W;
+  SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
+  if (const int rc = segk_bn_bwd_finalize_launch(bnpart, nb, Cp, C, P, dgamma, dbeta, coef, st)) return rc;
+  const float* bn[4] = {scale, shift, mean, rstd};
+  return dtype == SEGK_DT_BF16 ? head_bn_bwd_apply_t<bf16_t>(dlogits, z, w, dz, bn, coef, P, HW, Cp, C, ncls, st)
+                               : head_bn_bwd_apply_t<float>(dlogits, z, w, dz, bn, coef, P, HW, Cp, C, ncls, st);
 }
 
 // ---- prompt model remix (prompt_based/prompt.py:33-56), 4 CLIP classes x 1 mask channel, fp32 NCHW ----

@@ -44,6 +44,11 @@ int segk_stem_launch(const float* x, const float* w, void* z, void* xn, float* s
 int segk_stem_wgrad_slabs(int B, int H, int W, int Cin, int Cout, int dtype);
 int segk_stem_wgrad_launch(const float* x, const void* dz, float* slabs, int B, int H, int W, int Cin, int Cout,
                            hipStream_t st);
+int segk_stem_wgrad_bn_launch(const float* x, const void* da, const void* z, const float* const* bn, const float* coef,
+                              float* slabs, int B, int H, int W, int Cin, int Cout, hipStream_t st);
+// the finalize step of the BatchNorm backward (bn_pool.hip): partial rows [nb][C][2] -> dgamma, dbeta, coef
+int segk_bn_bwd_finalize_launch(const float* part, int nb, int C, int C_real, long P, float* dgamma, float* dbeta, float* coef,
+                                hipStream_t st);
 // register-stationary streaming kernel for the short-K ConvTranspose forward (convt_stream.hip)
 int segk_convt_stream_ok(int B, int H, int W, int Cin, int Cout, int dtype);
 int segk_convt_stream_launch(const void* x, const void* wp, const float* bias4, void* out, int B, int H, int W, int Cin,

@@ -187,12 +187,49 @@ __global__ __launch_bounds__(STEM_WAVES * 64, 4) void stem_stream_kernel(const f
 // from the NCHW fp32 image (8 consecutive x positions of one (channel, tap) = 32 contiguous bytes per lane), two
 // 32x32x16 MFMAs per step accumulate the whole 64 x 32 gradient in 32 registers; the eight waves of a workgroup add up
 // through LDS in a fixed order and write one slab per workgroup for segk_wgrad_reduce (taps = 1, CA = 9 Cin).
+//
+// BN: dz is not stored anywhere.  `dz` points at the gradient da of the block's hidden activation and `zpre` at the first
+// conv's pre-activation z; the lane forms its 16 dz values with bn_relu_bwd_dz (the element formula of bn_bwd_apply_kernel,
+// rounded to bf16 where that kernel stores) on the way into the LDS slot.  Six BatchNorm constants for 16 channels do not fit
+// beside 32 accumulators under the 128-register bound: they are read from an LDS table [6][64] filled once per workgroup.
+// Everything behind the LDS store is the same code, so the slabs equal those of the two-kernel sequence bit for bit.
 struct __attribute__((packed, aligned(4))) F4U { float v[4]; };    // 16-byte load at 4-byte alignment
 
+template <bool BN>
 __global__ __launch_bounds__(STEM_WAVES * 64, 2) void stem_wgrad_kernel(const float* __restrict__ x, const bf16_t* __restrict__ dz,
+                                                                        const bf16_t* __restrict__ zpre,
+                                                                        const float* __restrict__ bn_scale,
+                                                                        const float* __restrict__ bn_shift,
+                                                                        const float* __restrict__ bn_mean,
+                                                                        const float* __restrict__ bn_rstd,
+                                                                        const float* __restrict__ bn_coef,
                                                                         float* __restrict__ slabs, int B, int H, int W, int Cin,
                                                                         long nblk) {
   __shared__ __attribute__((aligned(16))) char lds[4 * 64 * 32 * 4];       // 32 KB: dz slots (2 KB per wave), then the reduction
+  __shared__ __attribute__((aligned(16))) float bnt[BN ? 6 * 64 : 4];      // BN: scale, shift, mean, rstd, c1, c2 of 64 channels
+  if constexpr (BN) {
+    const int t = threadIdx.x, c = t & 63;
+    if (t < 6 * 64) {
+      const int q = t >> 6;
+      bnt[t] = q == 0 ? bn_scale[c] : q == 1 ? bn_shift[c] : q == 2 ? bn_mean[c] : q == 3 ? bn_rstd[c] : bn_coef[2 * c + (q - 4)];
+    }
+    __syncthreads();
+  }
+  // BN: eight consecutive channels from c0 of one pixel, gradient g and pre-activation z -> dz, packed like the stored tensor
+  auto bn_dz8 = [&](const uint4 g, const uint4 z, const int c0) {
+    float fg[8], fz[8], k[6][8];
+    unpack16<bf16_t>(g, fg);
+    unpack16<bf16_t>(z, fz);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const float4 a = *(const float4*)(bnt + q * 64 + c0), b = *(const float4*)(bnt + q * 64 + c0 + 4);
+      k[q][0] = a.x; k[q][1] = a.y; k[q][2] = a.z; k[q][3] = a.w;
+      k[q][4] = b.x; k[q][5] = b.y; k[q][6] = b.z; k[q][7] = b.w;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) fg[e] = bn_relu_bwd_dz(fz[e], fg[e], k[0][e], k[1][e], k[2][e], k[3][e], k[4][e], k[5][e]);
+    return pack16<bf16_t>(fg);
+  };
   typedef __attribute__((address_space(3))) s16x4* lds_v4;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -225,8 +262,11 @@ __global__ __launch_bounds__(STEM_WAVES * 64, 2) void stem_wgrad_kernel(const fl
     const long b = row / H;
     const int y = (int)(row - b * H);
     // ---- dz: 16 pixels x 64 channels -> LDS, natural [block][pixel][64 B]
-    const bf16_t* dp = dz + ((size_t)row * W + x0 + lp) * 64 + lc4 * 8;
-    const uint4 d0 = *(const uint4*)dp, d1 = *(const uint4*)(dp + 32);
+    const size_t dofs = ((size_t)row * W + x0 + lp) * 64 + lc4 * 8;
+    const bf16_t* dp = dz + dofs;
+    uint4 d0 = *(const uint4*)dp, d1 = *(const uint4*)(dp + 32);
+    uint4 z0 = make_uint4(0, 0, 0, 0), z1 = z0;
+    if constexpr (BN) { z0 = *(const uint4*)(zpre + dofs); z1 = *(const uint4*)(zpre + dofs + 32); }
     // ---- im2col column j, pixels x0 + 8 hh .. + 7 of image row y + dy
     float v[8];
     const int xs = x0 + 8 * hh + dx;
@@ -240,6 +280,7 @@ __global__ __launch_bounds__(STEM_WAVES * 64, 2) void stem_wgrad_kernel(const fl
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (rok && (unsigned)(xs + e) < (unsigned)W) ? src[e] : 0.f;
     }
+    if constexpr (BN) { d0 = bn_dz8(d0, z0, lc4 * 8); d1 = bn_dz8(d1, z1, 32 + lc4 * 8); }
     *(uint4*)(slot + lp * 64 + lc4 * 16) = d0;
     *(uint4*)(slot + 1024 + lp * 64 + lc4 * 16) = d1;
     const u32x4 fbv = {pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])};
@@ -318,8 +359,23 @@ int segk_stem_wgrad_launch(const float* x, const void* dz, float* slabs, int B, 
   const int g = segk_stem_wgrad_slabs(B, H, W, Cin, Cout, SEGK_DT_BF16);
   SEGK_REQUIRE(g > 0, "stem_wgrad: shape not served (bf16, 1..3 input channels, 64 output channels, W a multiple of 16)");
   const long nblk = (long)B * H * (W / 16);
-  hipLaunchKernelGGL(stem_wgrad_kernel, dim3(g), dim3(STEM_WAVES * 64), 0, st, x, (const bf16_t*)dz, slabs, B, H, W, Cin, nblk);
+  hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(g), dim3(STEM_WAVES * 64), 0, st, x, (const bf16_t*)dz, (const bf16_t*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, slabs, B, H, W, Cin, nblk);
   SEGK_CHECK_LAUNCH("stem_wgrad");
+  return 0;
+}
+
+// the same with dz formed in registers from da and z (bn = scale, shift, mean, rstd; coef from the BatchNorm backward finalize)
+int segk_stem_wgrad_bn_launch(const float* x, const void* da, const void* z, const float* const* bn, const float* coef,
+                              float* slabs, int B, int H, int W, int Cin, int Cout, hipStream_t st) {
+  SEGK_REQUIRE(x && da && z && bn[0] && bn[1] && bn[2] && bn[3] && coef && slabs, "stem_wgrad_bn: null pointer");
+  const int g = segk_stem_wgrad_slabs(B, H, W, Cin, Cout, SEGK_DT_BF16);
+  SEGK_REQUIRE(g > 0, "stem_wgrad_bn: shape not served (bf16, 1..3 input channels, 64 output channels, W a multiple of 16)");
+  const long nblk = (long)B * H * (W / 16);
+  hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(g), dim3(STEM_WAVES * 64), 0, st, x, (const bf16_t*)da, (const bf16_t*)z, bn[0],
+                     bn[1], bn[2], bn[3], coef, slabs, B, H, W, Cin, nblk);
+  SEGK_CHECK_LAUNCH("stem_wgrad_bn");
   return 0;
 }
 

@@ -173,6 +173,16 @@ INPLACE_SKIP_GRAD = True   # the pooling backward accumulates into the incoming 
 FUSE_BN_REDUCE = True    # pooling / head backward also accumulate the producing block's BN2 backward reductions
 # a block followed by the output head hands it the pre-activation: BN+ReLU happen inside the head kernels
 HEAD_ON_Z = os.environ.get("SEGK_HEAD_ON_Z", "1") != "0"       # the env switch is for same-box A/B runs of bench.py
+# The two ends of the full-resolution level (up4.BN2 behind the head, down1.BN1 in front of the stem's weight gradient): a
+# gradient tensor of at least this many bytes is never stored -- its one consumer re-forms it in registers
+# (segk_head_bwd_bn_stats + segk_head_bn_bwd_apply; segk_bn_relu_bwd_stats + segk_stem3x3_wgrad_bn), bit-identical.  Below it
+# the stored form runs.  One value per end, each the smallest MEASURED size at which that end's unstored sequence is faster
+# than the stored one by more than the spread of the stored one's repeats (tools/kbench.py ends,
+# profiles/end_fusion_kbench.txt): END_FUSION_MIN_BYTES[end], so a test sets both with one monkeypatch.
+# Stored - unstored in us at 16.8 / 67.1 / 134.2 / 268.4 MB (spread of the stored form 0.4-2.6 us):
+#   head  -16.7   -8.9  +18.7   +41.0    a tensor the Infinity Cache holds costs no HBM traffic, re-forming it costs arithmetic
+#   stem   +9.3  +21.5  +56.7  +103.9    (16.8 MB is the smallest size measured; the 256 KB of the recorded launch trace is below)
+END_FUSION_MIN_BYTES = {"head": 128 << 20, "stem": 16 << 20}
 _OPT_EPOCH = [0]
 
 
@@ -668,6 +678,18 @@ def bn_relu_bwd(dy_ptr, z_ptr, dz_ptr, scale, shift, mean, rstd, P, C, dtype, de
     return dgamma, dbeta
 
 
+def bn_relu_bwd_stats(dy_ptr, z_ptr, scale, shift, mean, rstd, P, C, dtype, dev):
+    """-> (dgamma, dbeta, coef): the reduce + finalize steps of bn_relu_bwd alone, for a consumer that forms dz itself."""
+    Cp = pad32(C)
+    dgamma, dbeta = _f32(C, dev), _f32(C, dev)
+    nb = _lib.query("segk_bn_bwd_blocks", P, Cp, _DT[dtype])
+    part, coef = _f32(nb * Cp * 2, dev), _f32(2 * Cp, dev)
+    with _span("bn_relu_bwd", 0.0, 2.0 * P * C * _es(dtype)):     # reduce: 2 reads
+        _lib.call("segk_bn_relu_bwd_stats", dy_ptr, z_ptr, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                  P, Cp, C, part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), _DT[dtype], _stream())
+    return dgamma, dbeta, coef
+
+
 def channel_sum(ptr, P, C, dtype, dev):
     Cp = pad32(C)
     nb = _lib.query("segk_bn_bwd_blocks", P, Cp, _DT[dtype])
@@ -827,6 +849,31 @@ def _head_bwd(dlogits, px, Cp, w, B, C, H, W, dtype, dev, bn=None, on_z=False):
         _lib.call(entry, dl.data_ptr(), px, w2.data_ptr(), dy.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
                   B, H, W, Cp, C, ncls, *bn_tail, _DT[dtype], _stream())
     return dy, dw, db, ready
+
+
+def _head_bwd_unstored(dlogits, pz, Cp, w, B, C, H, W, dtype, dev, bn):
+    """-> (dz NHWC buffer, dw, db, dgamma, dbeta): _head_bwd on the pre-activation followed by bn_relu_bwd(ready=...), without
+    the gradient of the block output in memory: the first kernel only reduces, the second re-forms each element from dlogits
+    and w on its way through the BatchNorm backward.  Same values, bit for bit."""
+    ncls = w.shape[0]
+    dl = _f32c(dlogits)
+    w2 = _f32c(w).reshape(ncls, C)
+    P = B * H * W
+    part = _f32(_lib.query("segk_head_part_floats", P, Cp), dev)
+    dw = _grad_buffer(w, w.shape, dev)
+    db = _f32(ncls, dev)
+    nb = _lib.query("segk_head_bwd_blocks", P)
+    bnpart, coef = _f32(nb * Cp * 2, dev), _f32(2 * Cp, dev)
+    dgamma, dbeta = _f32(C, dev), _f32(C, dev)
+    dz = torch.empty((B, H, W, Cp), dtype=dtype, device=dev)
+    bnp = tuple(t.data_ptr() for t in bn)
+    with _span("head_bwd", 4.0 * P * C * ncls, P * (C * _es(dtype) + 4 * ncls)):
+        _lib.call("segk_head_bwd_bn_stats", dl.data_ptr(), pz, w2.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                  B, H, W, Cp, C, ncls, *bnp, bnpart.data_ptr(), _DT[dtype], _stream())
+    with _span("bn_relu_bwd", 2.0 * P * C * ncls, P * (2 * C * _es(dtype) + 4 * ncls)):     # z read, dz written, dlogits read
+        _lib.call("segk_head_bn_bwd_apply", dl.data_ptr(), pz, w2.data_ptr(), dz.data_ptr(), *bnp, B, H, W, Cp, C, ncls,
+                  bnpart.data_ptr(), nb, dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), _DT[dtype], _stream())
+    return dz, dw, db, dgamma, dbeta
 
 
 def _grad_refs(g):
@@ -1065,7 +1112,14 @@ class DoubleConvFn(torch.autograd.Function):
         ready = None
         d_head_w = d_head_b = None
         keep = None
-        if ctx.has_head:
+        dz2 = None
+        # the ends of the full-resolution level: a gradient with one cheap consumer is formed there instead of stored
+        grad_bytes = P * Coutp * _es(dtype)
+        end_fusion = not frozen and dtype == torch.bfloat16
+        if ctx.has_head and ctx.head_on_z and FUSE_BN_REDUCE and end_fusion and grad_bytes >= END_FUSION_MIN_BYTES["head"]:
+            dz2, d_head_w, d_head_b, dg2, dbe2 = _head_bwd_unstored(grads[0], z2.data_ptr(), Coutp, head_w, B, Cout, H, W, dtype,
+                                                                    dev, (sc2, sh2, mu2, rs2))
+        elif ctx.has_head:
             src = z2 if ctx.head_on_z else y
             dy_buf, d_head_w, d_head_b, ready = _head_bwd(grads[0], src.data_ptr(), Coutp, head_w, B, Cout, H, W, dtype, dev,
                                                           bn=(sc2, sh2, mu2, rs2), on_z=ctx.head_on_z)
@@ -1119,9 +1173,10 @@ class DoubleConvFn(torch.autograd.Function):
             keep, pdy, _ = _raw(grads[0], dtype)
 
         # ---- second conv: BN2+ReLU backward, data gradient, weight gradient
-        dz2 = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
-        dg2, dbe2 = bn_relu_bwd(pdy, z2.data_ptr(), dz2.data_ptr(), sc2, sh2, mu2, rs2, P, Cout, dtype, dev, ready=ready,
-                                frozen=frozen)
+        if dz2 is None:
+            dz2 = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
+            dg2, dbe2 = bn_relu_bwd(pdy, z2.data_ptr(), dz2.data_ptr(), sc2, sh2, mu2, rs2, P, Cout, dtype, dev, ready=ready,
+                                    frozen=frozen)
         del keep
         w2d = mod.cache.get(("w2d", dtype), w2, lambda: pack_conv(w2, Cout, 0, dtype, 1))
         da1 = torch.empty((B, H, W, Coutp), dtype=dtype, device=dev)
@@ -1137,13 +1192,19 @@ class DoubleConvFn(torch.autograd.Function):
         rb = ReduceBatch(dev)        # the ConvTranspose weight gradient and its bias gradient's column sums: one launch
         del slabs, dz2
 
-        # ---- first conv (dz1 overwrites da1 in place: da1 is private to this function)
-        dg1, dbe1 = bn_relu_bwd(da1.data_ptr(), z1.data_ptr(), da1.data_ptr(), sc1, sh1, mu1, rs1, P, Cout, dtype, dev,
-                                frozen=frozen)
+        # ---- first conv (dz1 overwrites da1 in place: da1 is private to this function).  The stem without a data gradient:
+        # dz1 has the weight gradient as its one consumer, which forms it from da1 and z1 itself (only the reductions run here)
+        has_up = ctx.up_dims is not None
+        coef1 = None
+        if (ctx.stem_raw and end_fusion and grad_bytes >= END_FUSION_MIN_BYTES["stem"]
+                and not (need[1] or need[2] or has_up)):
+            dg1, dbe1, coef1 = bn_relu_bwd_stats(da1.data_ptr(), z1.data_ptr(), sc1, sh1, mu1, rs1, P, Cout, dtype, dev)
+        else:
+            dg1, dbe1 = bn_relu_bwd(da1.data_ptr(), z1.data_ptr(), da1.data_ptr(), sc1, sh1, mu1, rs1, P, Cout, dtype, dev,
+                                    frozen=frozen)
         dz1 = da1
         dxa = dxb = None
         dxb_buf, chan_sum = None, None
-        has_up = ctx.up_dims is not None
         if need[1] or need[2] or has_up:
             w1d = mod.cache.get(("w1d", dtype), w1, lambda: pack_conv(w1, CA, CB, dtype, 1))
             dxa_buf = torch.empty((B, H, W, CAp), dtype=dtype, device=dev)
@@ -1163,9 +1224,15 @@ class DoubleConvFn(torch.autograd.Function):
         if ctx.stem_raw:        # the stem: im2col gather from the NCHW fp32 batch, slabs in OIHW column order (k = ci*9 + tap)
             S = _lib.query("segk_stem3x3_wgrad_slabs", B, H, W, CA, Cout, _DT[dtype])
             slabs = _f32(S * 64 * 32, dev)
-            with _span("wgrad3x3", 2.0 * P * 9 * CA * Cout, P * (Cout * _es(dtype) + 4 * CA) + 4.0 * 9 * CA * Cout):
-                _lib.call("segk_stem3x3_wgrad", xa_t.data_ptr(), dz1.data_ptr(), slabs.data_ptr(), B, H, W, CA, Cout,
-                          _DT[dtype], _stream())
+            if coef1 is not None:       # da1 and z1 in, dz1 in registers only
+                with _span("wgrad3x3", 2.0 * P * 9 * CA * Cout, P * (2 * Cout * _es(dtype) + 4 * CA) + 4.0 * 9 * CA * Cout):
+                    _lib.call("segk_stem3x3_wgrad_bn", xa_t.data_ptr(), da1.data_ptr(), z1.data_ptr(), sc1.data_ptr(),
+                              sh1.data_ptr(), mu1.data_ptr(), rs1.data_ptr(), coef1.data_ptr(), slabs.data_ptr(), B, H, W, CA,
+                              Cout, _DT[dtype], _stream())
+            else:
+                with _span("wgrad3x3", 2.0 * P * 9 * CA * Cout, P * (Cout * _es(dtype) + 4 * CA) + 4.0 * 9 * CA * Cout):
+                    _lib.call("segk_stem3x3_wgrad", xa_t.data_ptr(), dz1.data_ptr(), slabs.data_ptr(), B, H, W, CA, Cout,
+                              _DT[dtype], _stream())
             dw1 = wgrad_to_param(slabs, S, w1.shape, Cout, 9 * CA, 0, 1, dev, param=w1)
         else:
             slabs, S = wgrad(dz1.data_ptr(), Coutp, pA, CAp, pB, CBp, B, H, W, 0, dtype, dev, alg=(Cout, CA + CB))

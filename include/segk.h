@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 320
-#define SEGK_ENTRY_COUNT 98
+#define SEGK_ABI_VERSION 321
+#define SEGK_ENTRY_COUNT 102
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -103,6 +103,14 @@ int segk_stem3x3(const float* x_nchw, const float* w_oihw, void* z, void* x_nhwc
 int segk_stem3x3_wgrad_slabs(int B, int H, int W, int Cin, int Cout, int dtype);
 int segk_stem3x3_wgrad(const float* x_nchw, const void* dz, float* slabs, int B, int H, int W, int Cin, int Cout, int dtype,
                        segk_stream_t s);
+/* The same weight gradient with dz never stored (unet/unet.py:16-18, first conv + BatchNorm + ReLU of down1: the stem has no
+ * data gradient, so dz has this one consumer): da NHWC bf16 [B,H,W,64] is the gradient of the hidden activation, z the first
+ * conv's pre-activation, coef the [64][2] output of segk_bn_relu_bwd_stats; dz = scale * (g - c1 - xhat * c2) is formed per
+ * element with the formula of segk_bn_relu_bwd and rounded to bf16 as that entry stores it: the slabs are bit-identical to
+ * segk_bn_relu_bwd + segk_stem3x3_wgrad. */
+int segk_stem3x3_wgrad_bn(const float* x_nchw, const void* da, const void* z, const float* scale, const float* shift,
+                          const float* mean, const float* rstd, const float* coef, float* slabs, int B, int H, int W, int Cin,
+                          int Cout, int dtype, segk_stream_t s);
 int segk_conv_tiles(int B, int H, int W, int Cin, int Cout, int dtype);   /* padded CA+CB and CO1+CO2 of the call */
 /* floats to allocate for `stats`: the [tiles][Cp][2] partials plus the scratch segk_bn_finalize reduces through */
 int segk_bn_stats_floats(int tiles, int Cp);
@@ -205,6 +213,12 @@ int segk_maxpool2x2_bwd_bnstat(const void* x, const void* dy, void* dx, int B, i
 int segk_bn_relu_bwd_from_part(const void* dy, const void* z, void* dz, const float* scale, const float* shift,
                                const float* mean, const float* rstd, long P, int Cp, int C, const float* part, int nb,
                                float* dgamma, float* dbeta, float* coef, int dtype, segk_stream_t s);
+
+/* The reduce and finalize steps of segk_bn_relu_bwd alone (unet/unet.py:17-18 of down1): dgamma, dbeta and coef [Cp][2] as that
+ * entry returns them, no dz -- for a consumer that forms dz itself (segk_stem3x3_wgrad_bn).  part: segk_bn_bwd_blocks() rows. */
+int segk_bn_relu_bwd_stats(const void* dy, const void* z, const float* scale, const float* shift, const float* mean,
+                           const float* rstd, long P, int Cp, int C, float* part, float* dgamma, float* dbeta, float* coef,
+                           int dtype, segk_stream_t s);
 
 /* ---- bilinear resize, align_corners=False (clip/clipunet.py:99-100: skip features 14x14 -> decoder grid) ----
  * x [B,IH,IW,Cp] -> y [B,OH,OW,Cp]; backward is a deterministic gather dy -> dx */
@@ -430,6 +444,19 @@ int segk_head_fwd_bn(const void* z, const float* scale, const float* shift, cons
 int segk_head_bwd_bn(const float* dlogits, const void* z, const float* w, void* dy, float* part, float* dw, float* db,
                      int B, int H, int W, int Cp, int C, int ncls, const float* scale, const float* shift,
                      const float* mean, const float* rstd, float* bnpart, int dtype, segk_stream_t s);
+
+/* The output layer's backward without a stored gradient of the block output (unet.py:20-21 of up4 behind :91,105; that
+ * gradient is Wt . dlogits, three multiply-adds per channel, and has one consumer).  segk_head_bwd_bn_stats is segk_head_bwd_bn
+ * minus the store of dy: the dW / db partials and the BatchNorm partial rows bnpart are the same values in the same order.
+ * segk_head_bn_bwd_apply finishes bnpart (nb = segk_head_bwd_blocks(P) rows) into dgamma, dbeta, coef like
+ * segk_bn_relu_bwd_from_part and writes dz [B,H,W,Cp], re-forming each dy element from dlogits and w exactly as
+ * segk_head_bwd_bn computes and rounds it: dz is bit-identical to the two-entry sequence.  dz must not alias z. */
+int segk_head_bwd_bn_stats(const float* dlogits, const void* z, const float* w, float* part, float* dw, float* db, int B, int H,
+                           int W, int Cp, int C, int ncls, const float* scale, const float* shift, const float* mean,
+                           const float* rstd, float* bnpart, int dtype, segk_stream_t s);
+int segk_head_bn_bwd_apply(const float* dlogits, const void* z, const float* w, void* dz, const float* scale, const float* shift,
+                           const float* mean, const float* rstd, int B, int H, int W, int Cp, int C, int ncls,
+                           const float* bnpart, int nb, float* dgamma, float* dbeta, float* coef, int dtype, segk_stream_t s);
 
 /* ---- per-pixel CrossEntropy + soft Dice (training.py:47; utils/weighted_loss.py:31-98,140-166) ----
  * logits NCHW fp32 [N,C,HW], labels int64 [N,HW].  state (segk_loss_state_floats() floats):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -286,6 +286,71 @@ def stem():
     tw = timeit(lambda: _lib.call("segk_stem3x3_wgrad", x.data_ptr(), dz.data_ptr(), slabs.data_ptr(), B, H, W, Cin, Cout, 1, st), 30)
     P = B * H * W
     print(f"stem fwd {tf:7.1f} us ({P*(Cin*4+Cout*2)/tf/1e3:7.1f} GB/s)   wgrad {tw:7.1f} us ({P*(Cin*4+Cout*2)/tw/1e3:7.1f} GB/s)")
+
+
+def ends():
+    """The two ends of the full-resolution level with the stored gradient and without it (ops.END_FUSION_MIN_BYTES is read off
+    this table): head end = segk_head_bwd_bn + segk_bn_relu_bwd_from_part against segk_head_bwd_bn_stats + segk_head_bn_bwd_apply,
+    stem end = segk_bn_relu_bwd + segk_stem3x3_wgrad against segk_bn_relu_bwd_stats + segk_stem3x3_wgrad_bn, at gradient
+    tensors of 16, 67, 134 and 268 MB (B = 2, 8, 16, 32 at 64 channels, 256 x 256; the last is the bench shape).  Seven repeats
+    of `iters` launches each: median, and the spread (max - min) of the repeats.  No sequence overwrites its inputs: z and the
+    incoming gradient g keep their seeded values through every launch (the stored forms write dy / dz to buffers of their own;
+    the in-place apply of DoubleConvFn._backward moves the same bytes)."""
+    C, H, W, ncls, Cin = 64, 256, 256, 3, 3
+    dt = torch.bfloat16
+    st = ops._stream()
+    iters = 20
+    print(f"{'end':5s} {'MB':>6s} {'stored us':>10s} {'spread':>7s} {'unstored us':>12s} {'spread':>7s} {'gain us':>8s}")
+    for B in (2, 8, 16, 32):
+        P = B * H * W
+        z = torch.randn((P, C), device="cuda").to(dt)
+        g = torch.randn((P, C), device="cuda").to(dt)
+        dz = torch.empty_like(z); dy = torch.empty_like(z)
+        sc = torch.rand(C, device="cuda") + 0.5; sh = torch.rand(C, device="cuda") - 0.5
+        mu = torch.zeros(C, device="cuda"); rs = torch.ones(C, device="cuda")
+        bn = (sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), rs.data_ptr())
+        coef = torch.empty(2 * C, device="cuda"); dga = torch.empty(C, device="cuda"); dbe = torch.empty(C, device="cuda")
+        # head end
+        w = torch.randn((ncls, C), device="cuda") / 8
+        dl = torch.randn((B, ncls, H, W), device="cuda") / P
+        part = torch.empty(_lib.query("segk_head_part_floats", P, C), device="cuda")
+        nb = _lib.query("segk_head_bwd_blocks", P)
+        bnpart = torch.empty(nb * C * 2, device="cuda"); dw = torch.empty((ncls, C), device="cuda"); db = torch.empty(ncls, device="cuda")
+
+        def head_stored():
+            _lib.call("segk_head_bwd_bn", dl.data_ptr(), z.data_ptr(), w.data_ptr(), dy.data_ptr(), part.data_ptr(), dw.data_ptr(),
+                      db.data_ptr(), B, H, W, C, C, ncls, *bn, bnpart.data_ptr(), 1, st)
+            _lib.call("segk_bn_relu_bwd_from_part", dy.data_ptr(), z.data_ptr(), dz.data_ptr(), *bn, P, C, C, bnpart.data_ptr(), nb,
+                      dga.data_ptr(), dbe.data_ptr(), coef.data_ptr(), 1, st)
+
+        def head_unstored():
+            _lib.call("segk_head_bwd_bn_stats", dl.data_ptr(), z.data_ptr(), w.data_ptr(), part.data_ptr(), dw.data_ptr(),
+                      db.data_ptr(), B, H, W, C, C, ncls, *bn, bnpart.data_ptr(), 1, st)
+            _lib.call("segk_head_bn_bwd_apply", dl.data_ptr(), z.data_ptr(), w.data_ptr(), dz.data_ptr(), *bn, B, H, W, C, C, ncls,
+                      bnpart.data_ptr(), nb, dga.data_ptr(), dbe.data_ptr(), coef.data_ptr(), 1, st)
+        # stem end
+        x = torch.rand((B, Cin, H, W), device="cuda")
+        S = _lib.query("segk_stem3x3_wgrad_slabs", B, H, W, Cin, C, 1)
+        slabs = torch.empty(S * 64 * 32, device="cuda")
+        rpart = torch.empty(_lib.query("segk_bn_bwd_blocks", P, C, 1) * C * 2, device="cuda")
+
+        def stem_stored():
+            _lib.call("segk_bn_relu_bwd", g.data_ptr(), z.data_ptr(), dz.data_ptr(), *bn, P, C, C, rpart.data_ptr(), dga.data_ptr(),
+                      dbe.data_ptr(), coef.data_ptr(), 1, st)
+            _lib.call("segk_stem3x3_wgrad", x.data_ptr(), dz.data_ptr(), slabs.data_ptr(), B, H, W, Cin, C, 1, st)
+
+        def stem_unstored():
+            _lib.call("segk_bn_relu_bwd_stats", g.data_ptr(), z.data_ptr(), *bn, P, C, C, rpart.data_ptr(), dga.data_ptr(),
+                      dbe.data_ptr(), coef.data_ptr(), 1, st)
+            _lib.call("segk_stem3x3_wgrad_bn", x.data_ptr(), g.data_ptr(), z.data_ptr(), *bn, coef.data_ptr(), slabs.data_ptr(),
+                      B, H, W, Cin, C, 1, st)
+        for name, old, new in (("head", head_stored, head_unstored), ("stem", stem_stored, stem_unstored)):
+            to, tn = [], []
+            for _ in range(7):                          # interleaved, so drift of the box lands on both alike
+                to.append(timeit(old, iters)); tn.append(timeit(new, iters))
+            to.sort(); tn.sort()
+            print(f"{name:5s} {P * C * 2 / 1e6:6.1f} {to[3]:10.1f} {to[-1] - to[0]:7.1f} {tn[3]:12.1f} {tn[-1] - tn[0]:7.1f} "
+                  f"{to[3] - tn[3]:8.1f}", flush=True)
 
 
 def pack():
@@ -935,6 +1000,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "pack":
         pack()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "ends":
+        ends()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "stem":
         stem()
