@@ -21,19 +21,100 @@ def _check_targets(outputs, targets):
     raise ValueError(f"Unsupported target shape {targets.shape} for CE. Expected [N, H, W] or [N, 1, H, W].")
 
 
-class CrossEntropyLoss(nn.Module):
-    """nn.CrossEntropyLoss(weight=None, ignore_index=-100, reduction='mean') for [N,C,H,W] logits."""
+def _check_smoothing(label_smoothing):
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
+    return eps
 
-    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -100, reduction: str = "mean"):
+
+class CrossEntropyLoss(nn.Module):
+    """nn.CrossEntropyLoss(weight=None, ignore_index=-100, reduction='mean', label_smoothing=0.0) for [N,C,H,W] logits.
+    label_smoothing == 0 is the fused CrossEntropy + Dice kernel's path; a non-zero value runs on the hard-pixel loss kernels."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -100, reduction: str = "mean",
+                 label_smoothing: float = 0.0):
         super().__init__()
         if reduction != "mean":
             raise NotImplementedError("only reduction='mean' (the reference's setting) is implemented")
         self.weight = weight
         self.ignore_index = ignore_index
+        self.label_smoothing = _check_smoothing(label_smoothing)
 
     def forward(self, outputs, targets):
         ign = self.ignore_index if self.ignore_index is not None and self.ignore_index >= 0 else None
+        if self.label_smoothing != 0.0:
+            return ops.HardLossFn.apply(outputs, targets, self.weight, ign, self.label_smoothing, 0.0, None)[0]
         return ops.SegLossFn.apply(outputs, targets, self.weight, ign, 0.0, 0.0, 1.0)
+
+
+class HardPixelLoss(nn.Module):
+    """Class-weighted CrossEntropy that can also weight PIXELS, mean over the kept pixels:
+      label_smoothing  eps in [0, 1): nn.CrossEntropyLoss's smoothing;
+      gamma            0 or in [1, 8]: the focal modulation (1 - p_t)^gamma on each pixel's loss;
+      thresh, min_kept, min_fraction   bootstrapped / OHEM selection: keep the pixels whose CrossEntropy (unweighted,
+                       unsmoothed) is at least -log(thresh), and at least the max(min_kept, ceil(min_fraction * n)) hardest of
+                       the n labelled pixels of the batch (ties at the last one all kept).  All three at their defaults: every
+                       labelled pixel.
+    The selection is an exact k-th largest on the device: no sort, no per-pixel float tensor, no host sync; under
+    DistributedDataParallel every rank selects over its own batch.  After a call `.last` holds device tensors (no sync):
+    "n" (labelled pixels) and "n_kept" as int32, "threshold" (the smallest kept CrossEntropy allowed) as float32.
+    Targets [N,H,W] or [N,1,H,W] class indices."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: Optional[int] = -100, label_smoothing: float = 0.0,
+                 gamma: float = 0.0, thresh: Optional[float] = None, min_kept: int = 0, min_fraction: float = 0.0):
+        super().__init__()
+        self.weight = weight
+        self.ignore_index = ignore_index
+        self.label_smoothing = _check_smoothing(label_smoothing)
+        self.gamma = float(gamma)
+        if not (self.gamma == 0.0 or 1.0 <= self.gamma <= 8.0):
+            raise ValueError(f"gamma must be 0 or lie in [1, 8], got {gamma}")
+        if thresh is not None and not 0.0 < float(thresh) <= 1.0:
+            raise ValueError(f"thresh must lie in (0, 1], got {thresh}")
+        if int(min_kept) != min_kept or min_kept < 0 or min_kept >= 2 ** 31:
+            raise ValueError(f"min_kept must be a non-negative integer, got {min_kept}")
+        if not 0.0 <= float(min_fraction) <= 1.0:
+            raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction}")
+        self.thresh = None if thresh is None else float(thresh)
+        self.min_kept = int(min_kept)
+        self.min_fraction = float(min_fraction)
+        self.last = {}
+
+    def selection(self):
+        """None when every labelled pixel is kept, else (theta, min_kept, q16) as segk_hard_loss_fwd takes them: theta =
+        -log(thresh) in float64, rounded once to fp32 by the call; q16 = round(min_fraction * 2^16)."""
+        if self.thresh is None and self.min_kept == 0 and self.min_fraction == 0.0:
+            return None
+        import math
+        theta = math.inf if self.thresh is None else -math.log(self.thresh) + 0.0
+        return theta, self.min_kept, int(round(self.min_fraction * 65536.0))
+
+    def forward(self, outputs, targets):
+        _check_targets(outputs, targets)
+        ign = self.ignore_index if self.ignore_index is not None and self.ignore_index >= 0 else None
+        loss, state = ops.HardLossFn.apply(outputs, targets, self.weight, ign, self.label_smoothing, self.gamma, self.selection())
+        counts = state[6:8].view(torch.int32)
+        self.last = {"n": counts[0], "n_kept": counts[1], "threshold": state[4]}
+        return loss
+
+
+class FocalLoss(HardPixelLoss):
+    """Focal loss (Lin et al. 2017) on [N,C,H,W] logits: mean of (1 - p_t)^gamma * CrossEntropy over the labelled pixels."""
+
+    def __init__(self, gamma: float = 2.0, weight: Optional[torch.Tensor] = None, ignore_index: Optional[int] = -100,
+                 label_smoothing: float = 0.0):
+        super().__init__(weight=weight, ignore_index=ignore_index, label_smoothing=label_smoothing, gamma=gamma)
+
+
+class OhemCrossEntropyLoss(HardPixelLoss):
+    """Bootstrapped (online hard example mining) CrossEntropy: the mean over the pixels the model gets wrong (probability of
+    the label below `thresh`), and at least the max(min_kept, ceil(min_fraction * n)) hardest."""
+
+    def __init__(self, thresh: Optional[float] = 0.7, min_kept: int = 0, min_fraction: float = 0.0,
+                 weight: Optional[torch.Tensor] = None, ignore_index: Optional[int] = -100, label_smoothing: float = 0.0):
+        super().__init__(weight=weight, ignore_index=ignore_index, label_smoothing=label_smoothing, thresh=thresh,
+                         min_kept=min_kept, min_fraction=min_fraction)
 
 
 class MSELoss(nn.Module):
@@ -77,8 +158,10 @@ class WeightedDiceCELoss(nn.Module):
     def __init__(self, dice_weight: float = 1.0, ce_weight: float = 1.0, ignore_index: Optional[int] = None,
                  class_weights: Optional[torch.Tensor] = None, smooth_dice: float = 1e-5, ce_kwargs={}):
         super().__init__()
-        if ce_kwargs:
-            raise NotImplementedError("extra nn.CrossEntropyLoss kwargs are not supported by the fused kernel")
+        if set(ce_kwargs) - {"label_smoothing"}:
+            raise NotImplementedError("extra nn.CrossEntropyLoss kwargs are not supported by the fused kernel "
+                                      "(label_smoothing is the one that is)")
+        self.label_smoothing = _check_smoothing(ce_kwargs.get("label_smoothing", 0.0))
         self.dice_weight = dice_weight
         self.ce_weight = ce_weight
         self.ignore_index = ignore_index
@@ -87,6 +170,10 @@ class WeightedDiceCELoss(nn.Module):
 
     def forward(self, outputs, targets):
         _check_targets(outputs, targets)
+        if self.label_smoothing != 0.0:      # Dice alone on the fused kernel, the smoothed CrossEntropy on the hard-pixel kernels
+            dice = ops.SegLossFn.apply(outputs, targets, self.class_weights, self.ignore_index, self.smooth_dice, 1.0, 0.0)
+            ce = ops.HardLossFn.apply(outputs, targets, self.class_weights, self.ignore_index, self.label_smoothing, 0.0, None)[0]
+            return self.dice_weight * dice + self.ce_weight * ce
         return ops.SegLossFn.apply(outputs, targets, self.class_weights, self.ignore_index, self.smooth_dice,
                                    self.dice_weight, self.ce_weight)
 

@@ -1656,6 +1656,46 @@ class DistillFn(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
+HARD_HIST_WORDS = 5136      # SEGK_HARD_HIST_WORDS
+
+
+class HardLossFn(torch.autograd.Function):
+    """Label-smoothed, class-weighted CrossEntropy with an optional focal modulation (1 - p_t)^gamma and an optional selection
+    of the hardest pixels, mean over the kept ones.  select: None, or (theta, min_kept, q16) -- theta =
+    -log(thresh) as a float (inf: no threshold), q16 = round(min_fraction * 65536).  Returns (loss, state): the loss in a buffer
+    of its own and the kernel's state [loss, S, 0, D, tau, word of tau, n, n_kept, 0 ...] (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, class_weights, ignore_index, label_smoothing, gamma, select):
+        lg, tg, cw, ign, part, state, out = _loss_operands(logits, target, class_weights, ignore_index, "hard-pixel loss",
+                                                           "logits")
+        N, C, H, W = logits.shape
+        P, dev = N * H * W, logits.device
+        sel = select is not None
+        theta, min_kept, q16 = (float(select[0]), int(select[1]), int(select[2])) if sel else (0.0, 0, 0)
+        keys = torch.empty(P, dtype=torch.int32, device=dev) if sel else None       # uint32 words, saved for backward
+        hist = torch.empty(HARD_HIST_WORDS, dtype=torch.int32, device=dev) if sel else None
+        cfg = (N, C, H, W, ign, float(label_smoothing), float(gamma), int(sel))
+        with _span("hard_loss_fwd", 0.0, P * ((4.0 * C + 8) * (2 if sel else 1) + (16 if sel else 0))):
+            _lib.call("segk_hard_loss_fwd", lg.data_ptr(), tg.data_ptr(), _p(cw), N, C, H * W, ign, cfg[5], cfg[6], cfg[7], theta,
+                      min_kept, q16, _p(keys), _p(hist), part.data_ptr(), state.data_ptr(), out.data_ptr(), _stream())
+        ctx.cfg = cfg
+        ctx.save_for_backward(lg, tg, cw, keys, state)
+        ctx.mark_non_differentiable(state)
+        return out.view(()), state
+
+    @staticmethod
+    def backward(ctx, gout, _gstate):
+        lg, tg, cw, keys, state = ctx.saved_tensors
+        N, C, H, W, ign, eps, gamma, sel = ctx.cfg
+        go = _f32c(gout).reshape(1)
+        dl = torch.empty_like(lg)
+        with _span("hard_loss_bwd", 0.0, N * H * W * (8.0 * C + 8 + (4 if sel else 0))):
+            _lib.call("segk_hard_loss_bwd", lg.data_ptr(), tg.data_ptr(), _p(cw), _p(keys), state.data_ptr(), go.data_ptr(), N, C,
+                      H * W, ign, eps, gamma, sel, dl.data_ptr(), _stream())
+        return dl, None, None, None, None, None, None
+
+
 class PromptMixFn(torch.autograd.Function):
     """final_probs of the prompt model (reference prompt_based/prompt.py:35-56): softmax of the frozen 4-class CLIP-UNet
     logits remixed with the sigmoid of the mask U-Net's logit; gradient flows to the mask logit only (prompt.py:30-31)."""

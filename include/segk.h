@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 321
-#define SEGK_ENTRY_COUNT 102
+#define SEGK_ABI_VERSION 322
+#define SEGK_ENTRY_COUNT 104
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -501,6 +501,40 @@ int segk_distill_fwd(const float* student, const void* teachers_dev, int V, cons
 int segk_distill_bwd(const float* student, const void* teachers_dev, int V, const int64_t* labels, const float* state,
                      const float* grad_out, int N, int C, int H, int W, int ignore_index, float inv_T, float T_sq, float min_conf,
                      float* dstudent, segk_stream_t s);
+
+/* ---- hard-pixel losses: label smoothing, focal modulation, OHEM selection ----------------------------
+ * logits fp32 [N,C,HW], 1 <= C <= 8; labels int64 [N,HW]; N HW < 2^31; class_weights [C] or NULL (all 1); ignore_index < 0: none.
+ * A pixel COUNTS when 0 <= y < C and y != ignore_index; n = the counted pixels.  Per counted pixel, in fp32, classes in order:
+ * m = max z, e_k = expf(z_k - m), se = sum e_k, lse = logf(se), nl_k = lse - (z_k - m), p_k = e_k * (1 / se);
+ *   key   kappa = nl_t, a negative value clamped to 0, a NaN kept;
+ *   ce    = sum_k a_k nl_k with a_k = [k = t] ((1 - eps) w_t) + (eps / C) w_k, eps = label_smoothing in [0, 1); for eps == 0
+ *           exactly w_t nl_t, segk_loss_fwd's term;
+ *   l     = powf(u, gamma) ce with u = sum_{k != t} p_k, gamma == 0 or in [1, 8] (gamma == 0: l = ce, no powf).
+ * select != 0 keeps the pixels with kappa >= tau = min(theta, k-th largest key), k = min(n, max(min_kept, ceil(f n))) with
+ * f = min_frac_q16 / 65536 and the ceiling as (n q + 65535) >> 16 in 64-bit integers (k == 0: tau = theta); theta >= 0 is
+ * -log(thresh), +inf for none; ties at the k-th key are all kept and a NaN key orders above +inf.  select == 0 keeps every
+ * counted pixel.  loss = (float)(S / D), S = sum of l and D = sum of w_t over the kept pixels, summed in segk_loss_fwd's order
+ * and finished in float64 by the block that arrives last; D == 0: NaN when n == 0, else exactly 0.  With everything off
+ * state[0] carries segk_loss_fwd's bits (dice_weight 0, ce_weight 1).
+ * keys [N HW] uint32, needed iff select != 0 and saved for backward: bits(kappa) + 1 of a counted pixel, 0x7FC00001 for a NaN
+ * key, 0 for a pixel that does not count (non-negative floats order as their bits).  hist: SEGK_HARD_HIST_WORDS uint32 of
+ * scratch, 16-byte aligned, needed iff select != 0, zeroed by the entry on the stream.  part: segk_loss_part_floats(N HW),
+ * state: segk_loss_state_floats() floats: [0] loss, [1] S, [3] D, [4] tau, [5] the word of tau, [6] n, [7] the kept pixels
+ * ([5..7] as uint32 bits; select == 0: tau = 0, word 1), the rest 0.  loss_out (may be NULL): a copy of state[0].
+ * The selection is exact (three histogram passes over the words, 11 + 11 + 10 bits): no sort, no host sync, no float atomics.
+ * Every scalar and every host-visible pointer is validated (-2 before any launch). */
+#define SEGK_HARD_HIST_WORDS 5136   /* 2048 + 2048 + 1024 bins and 16 control words; a constant, not a query */
+int segk_hard_loss_fwd(const float* logits, const int64_t* labels, const float* class_weights, int N, int C, long HW,
+                       int ignore_index, float label_smoothing, float gamma, int select, float theta, int min_kept,
+                       int min_frac_q16, uint32_t* keys, uint32_t* hist, float* part, float* state, float* loss_out,
+                       segk_stream_t s);
+/* dlogits_j = (grad_out[0] / D) g_j at kept pixels (saved word >= the word in state[5]), g_j = mod (A p_j - a_j) - gamma
+ * powf(u, gamma - 1) p_t ([j = t] - p_j) ce with A = sum_k a_k and mod = powf(u, gamma) (second term absent for gamma == 0);
+ * gamma == 0 and eps == 0: segk_loss_bwd's grad_out ((w_t / D) (p_j - [j = t])).  Exactly 0 at every other pixel and
+ * everywhere when D == 0.  Same scalars as the forward call; keys NULL iff select == 0. */
+int segk_hard_loss_bwd(const float* logits, const int64_t* labels, const float* class_weights, const uint32_t* keys,
+                       const float* state, const float* grad_out, int N, int C, long HW, int ignore_index,
+                       float label_smoothing, float gamma, int select, float* dlogits, segk_stream_t s);
 
 /* ---- prompt model (prompt_based/prompt.py:33-56; utils/weighted_loss.py:170-343) ---------------------------
  * remix of the frozen 4-class CLIP-UNet softmax with the sigmoid of the 1-channel mask U-Net, fp32 NCHW:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill, hardloss)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -216,6 +216,43 @@ def distill():
             ttb = timeit(torch_both, 20) - ttf
             print(f"distill    C={C} V={V}  fwd {tf:7.1f} us ({P*4*C*(1+V)/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({P*4*C*(2+V)/tb/1e3:7.1f} GB/s)"
                   f"   value {val:.6f}   torch fwd {ttf:7.1f} us  bwd {ttb:7.1f} us  value {float(torch_fwd()):.6f}")
+
+
+def hardloss():
+    """Hard-pixel loss forward / backward (segk_hard_loss_fwd / _bwd) through the C ABI at the bench batch, 32 x 3 x 256 x 256, beside
+    segk_loss_fwd / _bwd (CrossEntropy) in the same run: everything off; gamma = 2 with label_smoothing = 0.1; the selection on
+    (thresh 0.7, min_fraction 0.25).  Bytes: forward P (4 C + 8), backward P (8 C + 8); the selection adds P (4 + 3 * 4 + 4 C + 8)
+    forward (the words written once and read three times, one more pass over logits and labels) and 4 P backward."""
+    import math
+    N, C, H, W = 32, 3, 256, 256
+    P = N * H * W
+    lg = torch.randn((N, C, H, W), device="cuda")
+    tg = torch.randint(0, C, (N, H, W), device="cuda")
+    part = torch.empty(_lib.query("segk_loss_part_floats", P), device="cuda")
+    state = torch.empty(_lib.query("segk_loss_state_floats"), device="cuda")
+    out = torch.empty(1, device="cuda"); go = torch.ones(1, device="cuda"); dl = torch.empty_like(lg)
+    keys = torch.empty(P, dtype=torch.int32, device="cuda")
+    hist = torch.empty(ops.HARD_HIST_WORDS, dtype=torch.int32, device="cuda")
+    st = ops._stream()
+    iters = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 50
+    f = lambda: _lib.call("segk_loss_fwd", lg.data_ptr(), tg.data_ptr(), None, N, C, H * W, -1, 1e-5, 0.0, 1.0,
+                          part.data_ptr(), state.data_ptr(), out.data_ptr(), st)
+    b = lambda: _lib.call("segk_loss_bwd", lg.data_ptr(), tg.data_ptr(), None, state.data_ptr(), go.data_ptr(), N, C,
+                          H * W, -1, 0.0, 1.0, dl.data_ptr(), st)
+    tf = timeit(f, iters); tb = timeit(b, iters)
+    fb, bb = P * (4 * C + 8), P * (8 * C + 8)
+    print(f"loss ce                    fwd {tf:7.1f} us ({fb/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({bb/tb/1e3:7.1f} GB/s)   value {float(out):.6f}")
+    theta = -math.log(0.7)
+    for name, eps, gamma, sel in (("all off", 0.0, 0.0, 0), ("gamma 2, smoothing 0.1", 0.1, 2.0, 0), ("selection on", 0.0, 0.0, 1)):
+        f = lambda: _lib.call("segk_hard_loss_fwd", lg.data_ptr(), tg.data_ptr(), None, N, C, H * W, -1, eps, gamma, sel, theta, 0,
+                              16384, keys.data_ptr(), hist.data_ptr(), part.data_ptr(), state.data_ptr(), out.data_ptr(), st)
+        b = lambda: _lib.call("segk_hard_loss_bwd", lg.data_ptr(), tg.data_ptr(), None, keys.data_ptr() if sel else None,
+                              state.data_ptr(), go.data_ptr(), N, C, H * W, -1, eps, gamma, sel, dl.data_ptr(), st)
+        tf = timeit(f, iters); tb = timeit(b, iters)
+        nf, nbw = fb + (P * (16 + 4 * C + 8) if sel else 0), bb + (4 * P if sel else 0)
+        counts = state[6:8].view(torch.int32).tolist()
+        print(f"hard {name:22s}fwd {tf:7.1f} us ({nf/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({nbw/tb/1e3:7.1f} GB/s)   value {float(out):.6f}"
+              f"   n {counts[0]} kept {counts[1]}")
 
 
 def head():
@@ -1015,6 +1052,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "recon":
         recon()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "hardloss":
+        hardloss()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "distill":
         distill()
