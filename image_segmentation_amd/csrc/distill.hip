@@ -9,18 +9,10 @@
 // A pixel counts when (labels == NULL or label != ignore_index) and max_k q1_k >= min_conf.
 // One pass forward (block partials -> the last arriver finishes them in float64, ticket.hpp), one pass backward that forms q
 // again through the same teacher_mix() -- no per-pixel buffer, no float atomics, one fixed order of additions.
-#include <type_traits>
-#include "common.hpp"
+#include "class_pixels.hpp"
 #include "segk_internal.h"
-#include "ticket.hpp"
-#include "../../include/segk.h"
-
-int segk_loss_blocks(long P);          // head_loss.hip: rows of the partial buffer segk_loss_part_floats(P) sizes
 
 namespace {
-constexpr int MAXC = SEGK_MAX_CLASSES;
-constexpr int DT = 1024;               // threads of a forward block (segk_loss_blocks counts 4 pixels per thread and pass)
-constexpr int DROWS = 256;             // most partial rows (segk_loss_blocks' cap)
 constexpr int DP = 4;                  // words per partial row: [0] sum KL (float), [1] n, [2] n_agree (uint32 bits), [3] unused
 constexpr float TINYF = 1.17549435e-38f;   // 2^-126
 
@@ -30,7 +22,9 @@ static_assert(sizeof(segk_teacher_desc) == 32, "segk_teacher_desc is 32 bytes (i
 template <int NC> constexpr int fwd_pif() { return NC <= 4 ? 4 : 2; }
 template <int NC> constexpr int bwd_pif() { return NC <= 4 ? 2 : 1; }
 
-// p = softmax(a) over the NC compiled classes (padded entries are -inf and come out as 0); returns max and sum through m, S
+// p = softmax(a) over the NC compiled classes (padded entries are -inf and come out as 0); returns max and sum through m, S.
+// Not class_max / class_exp (class_pixels.hpp): the maximum starts at a[0], not at -inf, and expf takes the padding unmasked --
+// a NaN in class 0 gives other bits
 template <int NC>
 __device__ __forceinline__ void softmax_nc(const float (&a)[NC], float (&p)[NC], float& m, float& S) {
   m = a[0];
@@ -117,32 +111,27 @@ __device__ __forceinline__ bool confident(const float (&q1)[NC], int C, float mi
   return mx >= min_conf;
 }
 
-// runs in the block that arrived last: NB <= DROWS rows of [sum KL, n, n_agree] -> state, loss_out.  One row per thread, all
-// loads in flight at once; a wave butterfly and four wave rows in float64 / uint64: one fixed order
+// runs in the block that arrived last: NB <= LROWS rows of [sum KL, n, n_agree] -> state, loss_out.  One row per thread, all
+// loads in flight at once; a wave butterfly and four wave rows in float64 / uint64: one fixed order.  Not sum_partial_rows
+// (class_pixels.hpp): that walk adds the rows in another order, which could change the last bit of sum KL
 __device__ __forceinline__ void distill_finalize_block(const float* __restrict__ part, int NB, float Tsq,
                                                        float* __restrict__ state, float* __restrict__ loss_out) {
-  __shared__ double skl[DROWS / 64];
-  __shared__ unsigned long long scn[DROWS / 64], sag[DROWS / 64];
+  __shared__ double skl[LROWS / 64];
+  __shared__ unsigned long long scn[LROWS / 64], sag[LROWS / 64];
   const int t = threadIdx.x;
-  if (t < DROWS) {
+  if (t < LROWS) {
     const int row = t < NB ? t : NB - 1;                         // unconditional loads of a clamped row
     const float f0 = part[row * DP];
     const unsigned u1 = __float_as_uint(part[row * DP + 1]), u2 = __float_as_uint(part[row * DP + 2]);
-    double kl = t < NB ? (double)f0 : 0.0;
-    unsigned long long cn = t < NB ? u1 : 0u, ag = t < NB ? u2 : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      kl += __shfl_xor(kl, o);
-      cn += __shfl_xor(cn, o);
-      ag += __shfl_xor(ag, o);
-    }
+    const double kl = wave_sum(t < NB ? (double)f0 : 0.0);
+    const unsigned long long cn = wave_sum<unsigned long long>(t < NB ? u1 : 0u), ag = wave_sum<unsigned long long>(t < NB ? u2 : 0u);
     if ((t & 63) == 0) { skl[t >> 6] = kl; scn[t >> 6] = cn; sag[t >> 6] = ag; }
   }
   __syncthreads();
   if (t != 0) return;
   double kl = 0.0;
   unsigned long long cn = 0, ag = 0;
-  for (int w = 0; w < DROWS / 64; ++w) { kl += skl[w]; cn += scn[w]; ag += sag[w]; }   // fixed order
+  for (int w = 0; w < LROWS / 64; ++w) { kl += skl[w]; cn += scn[w]; ag += sag[w]; }   // fixed order
   // a gate or an ignore mask that passes nothing: exactly 0, not 0 / 0 (the backward pass then writes exact zeros)
   const float soft = cn > 0 ? (float)((double)Tsq * kl / (double)cn) : 0.f;
   state[0] = soft;
@@ -154,14 +143,12 @@ __device__ __forceinline__ void distill_finalize_block(const float* __restrict__
 }
 
 template <int NC, bool TEMP, bool LAB>
-__global__ __launch_bounds__(DT) void distill_fwd_kernel(const float* __restrict__ student,
+__global__ __launch_bounds__(LT) void distill_fwd_kernel(const float* __restrict__ student,
                                                          const segk_teacher_desc* __restrict__ tab, int V,
                                                          const long long* __restrict__ labels, long P, long HW, int C, int H,
                                                          int W, int ignore_index, float invT, float Tsq, float min_conf,
                                                          float* __restrict__ part, float* __restrict__ state,
                                                          float* __restrict__ loss_out, unsigned* __restrict__ ticket) {
-  __shared__ float shk[DT / 64];
-  __shared__ unsigned shn[DT / 64], sha[DT / 64];
   __shared__ int last;
   float akl = 0.f;
   unsigned cnt = 0, agree = 0;
@@ -172,12 +159,9 @@ __global__ __launch_bounds__(DT) void distill_fwd_kernel(const float* __restrict
     long long y[PIF];
 #pragma unroll
     for (int u = 0; u < PIF; ++u) {
-      const unsigned pp = (unsigned)(p + u * step);
-      const unsigned bb = pp / (unsigned)HW;                     // one 32-bit division per pixel (P < 2^31)
-      b[u] = (long)bb;
-      r[u] = (long)pp - (long)bb * HW;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) s[u][k] = student[(b[u] * C + (k < C ? k : C - 1)) * HW + r[u]];
+      const long pp = p + u * step;
+      split_hw(pp, HW, b[u], r[u]);
+      load_classes<NC>(student, b[u], r[u], C, HW, s[u]);        // selected at first use
       if constexpr (LAB) y[u] = labels[pp];
       else y[u] = 0;
     }
@@ -207,30 +191,12 @@ __global__ __launch_bounds__(DT) void distill_fwd_kernel(const float* __restrict
     }
   };
   constexpr int PIF = fwd_pif<NC>();
-  const long step = (long)gridDim.x * DT;
-  long p = (long)blockIdx.x * DT + threadIdx.x;
+  const long step = (long)gridDim.x * LT;
+  long p = (long)blockIdx.x * LT + threadIdx.x;
   for (; p + (PIF - 1) * step < P; p += PIF * step) pixels(std::integral_constant<int, PIF>{}, p, step);
   for (; p < P; p += step) pixels(std::integral_constant<int, 1>{}, p, step);
-  // wave sums by butterfly, the wave rows through LDS, one partial row per block
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    akl += __shfl_xor(akl, o);
-    cnt += __shfl_xor(cnt, o);
-    agree += __shfl_xor(agree, o);
-  }
-  if ((threadIdx.x & 63) == 0) { shk[threadIdx.x >> 6] = akl; shn[threadIdx.x >> 6] = cnt; sha[threadIdx.x >> 6] = agree; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s2 = 0.f;
-    unsigned n2 = 0, a2 = 0;
-#pragma unroll
-    for (int w = 0; w < DT / 64; ++w) { s2 += shk[w]; n2 += shn[w]; a2 += sha[w]; }   // fixed order
-    float* row = part + (size_t)blockIdx.x * DP;
-    row[0] = s2;
-    row[1] = __uint_as_float(n2);
-    row[2] = __uint_as_float(a2);
-    row[3] = 0.f;
-  }
+  const float v[DP] = {wave_sum(akl), __uint_as_float(wave_sum(cnt)), __uint_as_float(wave_sum(agree)), 0.f};
+  write_partial_row<DP, 0x6u>(v, part + (size_t)blockIdx.x * DP);
   if (last_arriver(ticket, gridDim.x, &last)) distill_finalize_block(part, (int)gridDim.x, Tsq, state, loss_out);
 }
 
@@ -250,12 +216,9 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restric
     long long y[PIF];
 #pragma unroll
     for (int u = 0; u < PIF; ++u) {
-      const unsigned pp = (unsigned)(p + u * step);
-      const unsigned bb = pp / (unsigned)HW;
-      b[u] = (long)bb;
-      r[u] = (long)pp - (long)bb * HW;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) s[u][k] = student[(b[u] * C + (k < C ? k : C - 1)) * HW + r[u]];
+      const long pp = p + u * step;
+      split_hw(pp, HW, b[u], r[u]);
+      load_classes<NC>(student, b[u], r[u], C, HW, s[u]);        // selected at first use
       if constexpr (LAB) y[u] = labels[pp];
       else y[u] = 0;
     }
@@ -290,11 +253,7 @@ int by_variant(int C, bool temp, bool lab, F&& launch) {
     return lab ? launch(NCc, TEMPc, std::true_type{}) : launch(NCc, TEMPc, std::false_type{});
   };
   auto by_temp = [&](auto NCc) { return temp ? by_lab(NCc, std::true_type{}) : by_lab(NCc, std::false_type{}); };
-  if (C == 1) return by_temp(std::integral_constant<int, 1>{});
-  if (C == 2) return by_temp(std::integral_constant<int, 2>{});
-  if (C == 3) return by_temp(std::integral_constant<int, 3>{});
-  if (C == 4) return by_temp(std::integral_constant<int, 4>{});
-  return by_temp(std::integral_constant<int, MAXC>{});
+  return dispatch_each_nc(C, by_temp);
 }
 
 int check_common(const char* name, const void* student, const void* tab, int V, int N, int C, int H, int W, float invT, float Tsq,
@@ -326,12 +285,12 @@ extern "C" int segk_distill_fwd(const float* student, const void* teachers_dev, 
                ((uintptr_t)labels & 7) == 0, "distill_fwd: misaligned buffer");
   const long HW = (long)H * W, P = (long)N * HW;
   const int nb = segk_loss_blocks(P);                            // nb * DP <= segk_loss_part_floats(P)
-  SEGK_REQUIRE(nb >= 1 && nb <= DROWS, "distill_fwd: bad block count %d", nb);
+  SEGK_REQUIRE(nb >= 1 && nb <= LROWS, "distill_fwd: bad block count %d", nb);
   unsigned* const ticket = segk_ticket_slot(1, st);
   SEGK_REQUIRE(ticket != nullptr, "distill_fwd: no ticket array");
   const int rc = by_variant(C, inv_T != 1.0f, labels != nullptr, [&](auto NCc, auto TEMPc, auto LABc) {
     hipLaunchKernelGGL((distill_fwd_kernel<decltype(NCc)::value, decltype(TEMPc)::value, decltype(LABc)::value>), dim3(nb),
-                       dim3(DT), 0, st, student, (const segk_teacher_desc*)teachers_dev, V, (const long long*)labels, P, HW, C, H,
+                       dim3(LT), 0, st, student, (const segk_teacher_desc*)teachers_dev, V, (const long long*)labels, P, HW, C, H,
                        W, ignore_index, inv_T, T_sq, min_conf, part, state, loss_out, ticket);
     return 0;
   });

@@ -11,20 +11,12 @@
 // Selection: an exact k-th largest key by a three-level radix select (11 + 11 + 10 bits) over one 32-bit word per pixel
 // (bits(kappa) + 1, 0x7FC00001 for a NaN key, 0 for a pixel that does not count): histograms in LDS, one integer atomic per
 // non-zero bin and block, the block that arrives last (ticket.hpp) scans from the top bin down.  No sort, no host sync, no float
-// atomics; the loss sums take loss_fwd_kernel's order (head_loss.hip) and are finished in float64 by the last arriver.
-#include <type_traits>
-#include "common.hpp"
+// atomics; the loss sums take loss_fwd_kernel's order (loss.hip) through the same code (class_pixels.hpp) and are finished in
+// float64 by the last arriver.
+#include "class_pixels.hpp"
 #include "segk_internal.h"
-#include "ticket.hpp"
-#include "../../include/segk.h"
-
-int segk_loss_blocks(long P);          // head_loss.hip: rows of the partial buffer segk_loss_part_floats(P) sizes
-int segk_loss_state_floats(void);
 
 namespace {
-constexpr int MAXC = SEGK_MAX_CLASSES;
-constexpr int HT = 1024;               // threads of a forward block (segk_loss_blocks counts 4 pixels per thread and pass)
-constexpr int HROWS = 256;             // most partial rows (segk_loss_blocks' cap)
 constexpr int HP = 4;                  // words per partial row: [0] sum l, [1] sum w_t (float), [2] n, [3] n_kept (uint32 bits)
 constexpr int L0 = 2048, L1 = 2048, L2 = 1024;   // bins of the three levels: word >> 21, (word >> 10) & 2047, word & 1023
 constexpr int CTRL = L0 + L1 + L2;     // control words behind the histograms:
@@ -38,19 +30,11 @@ enum { C_PRE0 = 0,                     //   level-0 bin of the k-th word
 static_assert(CTRL + 16 == SEGK_HARD_HIST_WORDS, "histogram scratch of include/segk.h");
 constexpr unsigned NAN_WORD = 0x7FC00001u;
 
-__device__ __forceinline__ void split_hw(long p, long HW, long& b, long& r) {   // one 32-bit division (P < 2^31)
-  const unsigned bb = (unsigned)p / (unsigned)HW;
-  b = (long)bb;
-  r = p - (long)bb * HW;
-}
-
 template <int NC>
 __device__ __forceinline__ void fetch(const float* __restrict__ logits, const long long* __restrict__ labels, long p, long HW,
                                       int C, float (&raw)[NC], long long& y) {
   long b, r; split_hw(p, HW, b, r);
-#pragma unroll
-  for (int k = 0; k < NC; ++k)     // unconditional loads (class index clamped), selected afterwards (pixel_terms)
-    raw[k] = logits[(b * C + (k < C ? k : C - 1)) * HW + r];
+  load_classes<NC>(logits, b, r, C, HW, raw);     // selected at first use (pixel_terms)
   y = labels[p];
 }
 // between the loads of the pixels in flight and their first use: the scheduler otherwise pairs each load with the select that
@@ -67,19 +51,17 @@ struct Px {
 template <int NC>
 __device__ __forceinline__ void pixel_terms(const float (&raw)[NC], long long y, int C, int ignore_index, const float (&w)[NC],
                                             Px<NC>& o) {
-  float z[NC], m = -INFINITY;
+  float z[NC];
 #pragma unroll
-  for (int k = 0; k < NC; ++k) { z[k] = (k < C) ? raw[k] : -INFINITY; m = fmaxf(m, z[k]); }
-  float se = 0.f;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) { o.p[k] = (k < C) ? expf(z[k] - m) : 0.f; se += o.p[k]; }
+  for (int k = 0; k < NC; ++k) z[k] = (k < C) ? raw[k] : -INFINITY;
+  const float m = class_max(z), se = class_exp(z, m, C, o.p);
   const float inv = 1.f / se, lse = logf(se);
   o.counted = y >= 0 && y < C && y != ignore_index;
   o.nlt = 0.f; o.wt = 0.f; o.pt = 0.f;
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
     o.p[k] *= inv;
-    o.nl[k] = lse - (z[k] - m);     // -log softmax = log(sum exp) - (logit - max)
+    o.nl[k] = neg_log_softmax(lse, z[k], m);
     if (o.counted && y == k) { o.nlt = o.nl[k]; o.wt = w[k]; o.pt = o.p[k]; }
   }
 }
@@ -122,12 +104,12 @@ __device__ __forceinline__ void load_weights(const float* __restrict__ cw, int C
 }
 
 // ---- the block that arrived last: bin of the k-th largest word ----------------------------------------------------------
-// hist: NB (<= 2048) counters other blocks added to (read past this CU's L1).  Every thread of the HT-thread block calls;
+// hist: NB (<= 2048) counters other blocks added to (read past this CU's L1).  Every thread of the LT-thread block calls;
 // k = rank(total of the counters) says which word is wanted (0: none; else 1 <= k <= total); returns the bin of the k-th
 // largest word and its rank inside that bin, counted from the bin's top (>= 1), and the total.
 template <typename F>
 __device__ __forceinline__ void select_bin(unsigned* hist, int NB, F&& rank, unsigned& bin, unsigned& rem, unsigned& total) {
-  __shared__ unsigned wtot[HT / 64], res[2];
+  __shared__ unsigned wtot[LT / 64], res[2];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   // thread t owns bins 2t, 2t + 1; a suffix sum over the threads (wave shuffles, then the 16 wave totals)
   const int i0 = 2 * t < NB ? 2 * t : 0;
@@ -146,7 +128,7 @@ __device__ __forceinline__ void select_bin(unsigned* hist, int NB, F&& rank, uns
   __syncthreads();
   unsigned above_waves = 0, tot = 0;
 #pragma unroll
-  for (int q = 0; q < HT / 64; ++q) {
+  for (int q = 0; q < LT / 64; ++q) {
     const unsigned x = wtot[q];
     tot += x;
     above_waves += q > wv ? x : 0u;
@@ -166,19 +148,19 @@ __device__ __forceinline__ void select_bin(unsigned* hist, int NB, F&& rank, uns
 // LDS histogram -> one integer atomic per non-zero bin
 __device__ __forceinline__ void flush_hist(const unsigned* lh, unsigned* gh, int NB) {
   __syncthreads();
-  for (int i = threadIdx.x; i < NB; i += HT)
+  for (int i = threadIdx.x; i < NB; i += LT)
     if (lh[i]) atomicAdd(gh + i, lh[i]);
 }
 
 // pass 1 of the selection: the words, the level-0 histogram, then (last arriver) n, k and the level-0 bin
 template <int NC>
-__global__ __launch_bounds__(HT) void hard_key_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+__global__ __launch_bounds__(LT) void hard_key_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
                                                       long P, long HW, int C, int ignore_index, unsigned theta_word,
                                                       unsigned min_kept, unsigned q16, unsigned* __restrict__ keys,
                                                       unsigned* hist, unsigned* __restrict__ ticket) {
   __shared__ unsigned lh[L0];
   __shared__ int last;
-  for (int i = threadIdx.x; i < L0; i += HT) lh[i] = 0;
+  for (int i = threadIdx.x; i < L0; i += LT) lh[i] = 0;
   __syncthreads();
   float w[NC];
 #pragma unroll
@@ -194,8 +176,8 @@ __global__ __launch_bounds__(HT) void hard_key_kernel(const float* __restrict__ 
   };
   // four pixels in flight in every pass: past the end the loads are clamped to the last pixel and the result is dropped (no
   // float sum depends on the order here, so the tail needs no loop of its own)
-  const long step = (long)gridDim.x * HT;
-  for (long p = (long)blockIdx.x * HT + threadIdx.x; p < P; p += 4 * step) {
+  const long step = (long)gridDim.x * LT;
+  for (long p = (long)blockIdx.x * LT + threadIdx.x; p < P; p += 4 * step) {
     float r0[NC], r1[NC], r2[NC], r3[NC];
     long long y0, y1, y2, y3;
     const long last_p = P - 1;
@@ -232,7 +214,7 @@ __global__ __launch_bounds__(HT) void hard_key_kernel(const float* __restrict__ 
 
 // passes 2 and 3: histogram of the next bits over the words that share the prefix found so far
 template <int LEVEL>
-__global__ __launch_bounds__(HT) void hard_refine_kernel(const unsigned* __restrict__ keys, long P, unsigned theta_word,
+__global__ __launch_bounds__(LT) void hard_refine_kernel(const unsigned* __restrict__ keys, long P, unsigned theta_word,
                                                          unsigned* hist, unsigned* __restrict__ ticket) {
   constexpr int NB = LEVEL == 1 ? L1 : L2;
   constexpr int SH = LEVEL == 1 ? 21 : 10;          // the bits above this level's
@@ -243,13 +225,13 @@ __global__ __launch_bounds__(HT) void hard_refine_kernel(const unsigned* __restr
   if (ctrl[C_DONE]) return;
   const unsigned prefix = ctrl[LEVEL == 1 ? C_PRE0 : C_PRE1], k = ctrl[LEVEL == 1 ? C_REM0 : C_REM1];
   unsigned* const gh = hist + (LEVEL == 1 ? L0 : L0 + L1);
-  for (int i = threadIdx.x; i < NB; i += HT) lh[i] = 0;
+  for (int i = threadIdx.x; i < NB; i += LT) lh[i] = 0;
   __syncthreads();
   auto word = [&](unsigned v) {
     if (v != 0u && (v >> SH) == prefix) atomicAdd(&lh[LEVEL == 1 ? (v >> 10) & 2047u : v & 1023u], 1u);
   };
-  const long step = (long)gridDim.x * HT;
-  long p = (long)blockIdx.x * HT + threadIdx.x;
+  const long step = (long)gridDim.x * LT;
+  long p = (long)blockIdx.x * LT + threadIdx.x;
   for (; p + 3 * step < P; p += 4 * step) {
     const unsigned v0 = keys[p], v1 = keys[p + step], v2 = keys[p + 2 * step], v3 = keys[p + 3 * step];
     word(v0); word(v1); word(v2); word(v3);
@@ -270,37 +252,12 @@ __global__ __launch_bounds__(HT) void hard_refine_kernel(const unsigned* __restr
   }
 }
 
-// runs in the block that arrived last: NB <= HROWS rows of [sum l, sum w_t, n, n_kept] -> state, loss_out.  The walk over the
-// rows and the order of the float64 additions are loss_finalize_block's (head_loss.hip): with everything off, the same bits
+// runs in the block that arrived last: NB <= LROWS rows of [sum l, sum w_t, n, n_kept] -> state, loss_out.  The walk over the
+// rows is loss_finalize_block's (sum_partial_rows): with everything off, the same bits
 __device__ __forceinline__ void hard_finalize_block(const float* __restrict__ part, int NB, unsigned tau_word, int nstate,
                                                     float* __restrict__ state, float* __restrict__ loss_out) {
-  __shared__ double tot[HP];
-  __shared__ double sh[HT / 32][32];
-  constexpr int RG = HT / 32, FL = HROWS / RG;
-  const int t = threadIdx.x, cx = t & 31, ry = t >> 5;
-  double acc = 0.0;
-  if (cx < HP) {
-    float v[FL];
-#pragma unroll
-    for (int u = 0; u < FL; ++u) {   // unconditional loads of a clamped row
-      const int r = ry + RG * u < NB ? ry + RG * u : NB - 1;
-      v[u] = part[(unsigned)r * HP + cx];
-    }
-#pragma unroll
-    for (int u = 0; u < FL; ++u) {
-      const double d = cx < 2 ? (double)v[u] : (double)__float_as_uint(v[u]);
-      acc += (ry + RG * u < NB) ? d : 0.0;
-    }
-  }
-  sh[ry][cx] = acc;
-  __syncthreads();
-  if (t < HP) {
-    double s = 0.0;
-    for (int r = 0; r < RG; ++r) s += sh[r][t];   // fixed order
-    tot[t] = s;
-  }
-  __syncthreads();
-  if (t != 0) return;
+  const double* tot = sum_partial_rows<HP>(part, NB, [](float v, int cx) { return cx < 2 ? (double)v : (double)__float_as_uint(v); });
+  if (threadIdx.x != 0) return;
   const double S = tot[0], D = tot[1];
   const unsigned n = (unsigned)tot[2], nk = (unsigned)tot[3];
   // no weight kept: NaN when no pixel counts at all (torch's rule), else exactly 0 (an empty kept set, zero weights)
@@ -321,14 +278,12 @@ __device__ __forceinline__ void hard_finalize_block(const float* __restrict__ pa
 // unconditional clamped loads, wave butterfly, LDS rows, one partial row per block, the last arriver finishes.
 // PLAIN: gamma == 0 and label_smoothing == 0.  SEL: a pixel is kept when its word >= the word of tau (hist's control block)
 template <int NC, bool PLAIN, bool SEL>
-__global__ __launch_bounds__(HT) void hard_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+__global__ __launch_bounds__(LT) void hard_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
                                                       const float* __restrict__ cw, long P, long HW, int C, int ignore_index,
                                                       float eps, float gamma, const unsigned* __restrict__ keys,
                                                       const unsigned* __restrict__ hist, float* __restrict__ part, int nstate,
                                                       float* __restrict__ state, float* __restrict__ loss_out,
                                                       unsigned* __restrict__ ticket) {
-  __shared__ float shs[HT / 64], shd[HT / 64];
-  __shared__ unsigned shn[HT / 64], shk[HT / 64];
   __shared__ int last;
   unsigned tau_word = 1u;              // every counted pixel
   if constexpr (SEL) tau_word = hist[CTRL + C_TAU];
@@ -353,8 +308,8 @@ __global__ __launch_bounds__(HT) void hard_fwd_kernel(const float* __restrict__ 
       kept += 1u;
     }
   };
-  const long step = (long)gridDim.x * HT;
-  long p = (long)blockIdx.x * HT + threadIdx.x;
+  const long step = (long)gridDim.x * LT;
+  long p = (long)blockIdx.x * LT + threadIdx.x;
   for (; p + 3 * step < P; p += 4 * step) {
     float r0[NC], r1[NC], r2[NC], r3[NC];
     long long y0, y1, y2, y3;
@@ -379,14 +334,11 @@ __global__ __launch_bounds__(HT) void hard_fwd_kernel(const float* __restrict__ 
     loads_issued();
     pixel(r0, y0, k0);
   }
-  // wave sums by butterfly, the wave rows through LDS, one partial row per block
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o);
-    a1 += __shfl_xor(a1, o);
-    cnt += __shfl_xor(cnt, o);
-    kept += __shfl_xor(kept, o);
-  }
+  // wave sums, the wave rows through LDS, one partial row per block.  Not write_partial_row (class_pixels.hpp): the instance
+  // <8, false, true> sits at the 128 registers a 1024-thread block may have and spilled one of them through it
+  __shared__ float shs[LT / 64], shd[LT / 64];
+  __shared__ unsigned shn[LT / 64], shk[LT / 64];
+  a0 = wave_sum(a0); a1 = wave_sum(a1); cnt = wave_sum(cnt); kept = wave_sum(kept);
   if ((threadIdx.x & 63) == 0) {
     shs[threadIdx.x >> 6] = a0; shd[threadIdx.x >> 6] = a1; shn[threadIdx.x >> 6] = cnt; shk[threadIdx.x >> 6] = kept;
   }
@@ -395,7 +347,7 @@ __global__ __launch_bounds__(HT) void hard_fwd_kernel(const float* __restrict__ 
     float s2 = 0.f, d2 = 0.f;
     unsigned n2 = 0, k2 = 0;
 #pragma unroll
-    for (int q = 0; q < HT / 64; ++q) { s2 += shs[q]; d2 += shd[q]; n2 += shn[q]; k2 += shk[q]; }   // fixed order
+    for (int q = 0; q < LT / 64; ++q) { s2 += shs[q]; d2 += shd[q]; n2 += shn[q]; k2 += shk[q]; }   // fixed order
     float* row = part + (size_t)blockIdx.x * HP;
     row[0] = s2;
     row[1] = d2;
@@ -423,9 +375,7 @@ __global__ __launch_bounds__(256) void hard_bwd_kernel(const float* __restrict__
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
     long b, r; split_hw(p, HW, b, r);
     float raw[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k)     // unconditional loads (class index clamped), selected afterwards (pixel_terms)
-      raw[k] = logits[(b * C + (k < C ? k : C - 1)) * HW + r];
+    load_classes<NC>(logits, b, r, C, HW, raw);     // selected at first use (pixel_terms)
     const long long y = labels[p];
     unsigned word = 0;
     if constexpr (SEL) word = keys[p];
@@ -465,13 +415,6 @@ __global__ __launch_bounds__(256) void hard_bwd_kernel(const float* __restrict__
   }
 }
 
-// kernels are compiled for 2, 4 and MAXC classes (the smallest that holds C), as in head_loss.hip
-template <typename F>
-void by_nc(int C, F&& launch) {
-  if (C <= 2) launch(std::integral_constant<int, 2>{});
-  else if (C <= 4) launch(std::integral_constant<int, 4>{});
-  else launch(std::integral_constant<int, MAXC>{});
-}
 template <typename F>
 void by_mode(bool plain, bool sel, F&& launch) {
   if (plain) { if (sel) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
@@ -516,7 +459,7 @@ extern "C" int segk_hard_loss_fwd(const float* logits, const int64_t* labels, co
                min_frac_q16);
   const long P = (long)N * HW;
   const int nb = segk_loss_blocks(P);                            // nb * HP <= segk_loss_part_floats(P)
-  SEGK_REQUIRE(nb >= 1 && nb <= HROWS, "hard_loss_fwd: bad block count %d", nb);
+  SEGK_REQUIRE(nb >= 1 && nb <= LROWS, "hard_loss_fwd: bad block count %d", nb);
   const int nstate = segk_loss_state_floats();
   const bool plain = gamma == 0.f && label_smoothing == 0.f, sel = select != 0;
   unsigned* const tickets = segk_ticket_slot(sel ? 4 : 1, st);
@@ -528,19 +471,19 @@ extern "C" int segk_hard_loss_fwd(const float* logits, const int64_t* labels, co
       SEGK_FAIL(-3, "hard_loss_fwd: cannot zero the histogram scratch");
     const float th = theta + 0.f;                                // -0 -> +0
     const unsigned theta_word = __builtin_bit_cast(unsigned, th) + 1u;
-    by_nc(C, [&](auto NCc) {
-      hipLaunchKernelGGL((hard_key_kernel<decltype(NCc)::value>), dim3(nb), dim3(HT), 0, st, logits, lab, P, HW, C, ignore_index,
+    dispatch_loss_nc(C, [&](auto NCc) {
+      hipLaunchKernelGGL((hard_key_kernel<decltype(NCc)::value>), dim3(nb), dim3(LT), 0, st, logits, lab, P, HW, C, ignore_index,
                          theta_word, (unsigned)min_kept, (unsigned)min_frac_q16, keys, hist, tickets);
     });
     SEGK_CHECK_LAUNCH("hard_loss_fwd (keys)");
-    hipLaunchKernelGGL(hard_refine_kernel<1>, dim3(nb), dim3(HT), 0, st, keys, P, theta_word, hist, tickets + 1);
-    hipLaunchKernelGGL(hard_refine_kernel<2>, dim3(nb), dim3(HT), 0, st, keys, P, theta_word, hist, tickets + 2);
+    hipLaunchKernelGGL(hard_refine_kernel<1>, dim3(nb), dim3(LT), 0, st, keys, P, theta_word, hist, tickets + 1);
+    hipLaunchKernelGGL(hard_refine_kernel<2>, dim3(nb), dim3(LT), 0, st, keys, P, theta_word, hist, tickets + 2);
     SEGK_CHECK_LAUNCH("hard_loss_fwd (select)");
   }
-  by_nc(C, [&](auto NCc) {
+  dispatch_loss_nc(C, [&](auto NCc) {
     by_mode(plain, sel, [&](auto PLAINc, auto SELc) {
       hipLaunchKernelGGL((hard_fwd_kernel<decltype(NCc)::value, decltype(PLAINc)::value, decltype(SELc)::value>), dim3(nb),
-                         dim3(HT), 0, st, logits, lab, class_weights, P, HW, C, ignore_index, label_smoothing, gamma, keys, hist,
+                         dim3(LT), 0, st, logits, lab, class_weights, P, HW, C, ignore_index, label_smoothing, gamma, keys, hist,
                          part, nstate, state, loss_out, tickets + (sel ? 3 : 0));
     });
   });
@@ -563,7 +506,7 @@ extern "C" int segk_hard_loss_bwd(const float* logits, const int64_t* labels, co
   long g = (P + 255) / 256;
   if (g > 4096) g = 4096;
   const bool plain = gamma == 0.f && label_smoothing == 0.f, sel = select != 0;
-  by_nc(C, [&](auto NCc) {
+  dispatch_loss_nc(C, [&](auto NCc) {
     by_mode(plain, sel, [&](auto PLAINc, auto SELc) {
       hipLaunchKernelGGL((hard_bwd_kernel<decltype(NCc)::value, decltype(PLAINc)::value, decltype(SELc)::value>), dim3((int)g),
                          dim3(256), 0, st, logits, (const long long*)labels, class_weights, keys, state, grad_out, P, HW, C,

@@ -13,7 +13,7 @@
 #pragma once
 #include <type_traits>
 
-#include "../../include/segk.h"
+#include "class_pixels.hpp"
 #include "segk_internal.h"
 
 // ---- index and blend: ATen's area_pixel_compute_source_index (align_corners=False), its two-tap blend, and "nearest" --------
@@ -296,10 +296,4 @@ inline int check_output_alignment(const char* name, bool merged, const void* mas
 
 // The kernels are compiled for 1, 2, 3, 4 and SEGK_MAX_CLASSES classes: f(integral_constant<smallest that holds C>)
 template <typename F>
-inline auto dispatch_classes(int C, F f) {
-  if (C == 1) return f(std::integral_constant<int, 1>{});
-  if (C == 2) return f(std::integral_constant<int, 2>{});
-  if (C == 3) return f(std::integral_constant<int, 3>{});
-  if (C == 4) return f(std::integral_constant<int, 4>{});
-  return f(std::integral_constant<int, SEGK_MAX_CLASSES>{});
-}
+inline auto dispatch_classes(int C, F f) { return dispatch_each_nc(C, f); }

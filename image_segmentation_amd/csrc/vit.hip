@@ -19,19 +19,12 @@
 //   vit_tokens_to_grid   drop CLS, residual stream -> NHWC feature grid [B,G,G,D] (clipunet.py:48-63)
 // The residual stream stays fp32 in both compute modes (it is 2.4 MB per image batch of 16); GEMM operands are
 // the compute dtype.
-#include "common.hpp"
+#include "class_pixels.hpp"      // wave_sum
 #include "segk_internal.h"
-#include "../../include/segk.h"
 
 namespace {
 
 constexpr int LN_MAXPER = 32;   // channels per lane: D <= 2048
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void vit_patchify_kernel(const float* __restrict__ x, T* __restrict__ rows, int B, int C,

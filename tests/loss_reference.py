@@ -1,8 +1,8 @@
-"""float64 references, analytic gradients, launch arithmetic and derived error bounds for the kernels of csrc/head_loss.hip
+"""float64 references, analytic gradients, launch arithmetic and derived error bounds for the kernels of csrc/head.hip and csrc/loss.hip
 (output head, CrossEntropy + soft Dice, probability-mode Dice + NLL, prompt remix), shared by tests/test_loss_reference_host.py
 and tests/test_gpu_head_loss_matrix.py.  CPU torch only.  Nothing here is taken from what the kernels return.
 
-Semantics (restated from oracle/losses_ref.py, oracle/prompt_ref.py and the header comment of head_loss.hip), on logits or
+Semantics (restated from oracle/losses_ref.py, oracle/prompt_ref.py and the header comment of loss.hip), on logits or
 probabilities x [N, C, HW] and labels y [N, HW]:
 
   p        = softmax(x) over C, or x itself in probability mode

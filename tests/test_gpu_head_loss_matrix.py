@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every kernel of csrc/head_loss.hip through the C ABI against float64 (tests/loss_reference.py), at every class
+"""GPU (-m gpu): every kernel of csrc/head.hip and csrc/loss.hip through the C ABI against float64 (tests/loss_reference.py), at every class
 count 1..8 -- the kernels are compiled per class count (head 2 / 3 / 4 / 8, loss 2 / 4 / 8) and C = 1, 5, 6, 7 run the
 "clamped class index, selected afterwards" loads -- and at pixel counts chosen from the launch arithmetic rather than from the
 models.  Outputs and partial buffers are NaN-filled with guard elements behind them, so an unwritten or over-written element shows.

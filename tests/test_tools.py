@@ -82,7 +82,7 @@ def test_streaming_and_finalize_kernels_keep_their_loads_in_flight():
            "bn_bwd_reduce_kernel", "loss_fwd_kernel", "loss_bwd_kernel", "head_fwd_kernel", "wgrad_reduce_kernel",
            "wgrad_reduce_wide_kernel")       # (stem_wgrad keeps conditional loads on its image-border path: measured faster)
     seen = set()
-    for unit in ("bn_pool", "head_loss", "pack", "stem"):
+    for unit in ("bn_pool", "head", "loss", "pack", "stem"):
         for n_ser, n_loads, _, name in ser.scan(unit):
             for h in hot:
                 if h in name or h[:-7] in name:        # (mangled names of template kernels carry the stem only)
@@ -90,7 +90,7 @@ def test_streaming_and_finalize_kernels_keep_their_loads_in_flight():
                     assert n_ser <= 2, f"{name}: {n_ser} of {n_loads} loads wait for themselves"
     assert len(seen) >= 9, seen
     rep = _load_tool("spill_report")
-    for unit in ("bn_pool", "head_loss", "pack", "stem"):
+    for unit in ("bn_pool", "head", "loss", "pack", "stem"):
         for r in rep.report(unit):
             assert int(r.get("VGPRs Spill", 0)) == 0 and int(r.get("ScratchSize", 0)) == 0, (unit, r)
 
