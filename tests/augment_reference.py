@@ -6,10 +6,15 @@ every pixel is computed with integers.  Not a test module: tests/test_augment_ho
 
     image, label = augment(img_u8_hwc, label_u8, plan, T, label_lut, label_fill)      # uint8 [T,T,3], int64 [T,T]
     image, label = merge(img1, lab1, img2, lab2, T)
-    counts, weights = class_weights(list_of_label_arrays, C, ignore_index, unimportant, normalize_target_sum)"""
+    counts, weights = class_weights(list_of_label_arrays, C, ignore_index, unimportant, normalize_target_sum)
+    counts = label_hist(labels, C, ignore); classes = rgb_classes(rgb_u8_n3)       # the two class-count entries
+
+The end of the file holds the launch arithmetic of label_hist_kernel and the case table of tests/test_gpu_label_count_matrix.py."""
 import math
 
 import numpy as np
+
+from oracle.fill import u01
 
 RESIZE, CENTER_CROP, RANDOM_CROP, ROTATION, MASKING, GRAYSCALE, LAPLACE, BLUR, CONTRAST = range(9)
 U64 = np.uint64
@@ -285,14 +290,24 @@ def merge(img1, lab1, img2, lab2, T=256, label_lut=None):
 
 
 # ---------------------------------------------------------------------------------------------- class weights
+def label_hist(labels, C, ignore=None):
+    """utils.py:168-173: drop the ignore value first, then clamp to 0..C-1, then count -> int64 [C]"""
+    v = np.asarray(labels).astype(np.int64).ravel()
+    if ignore is not None:
+        v = v[v != ignore]
+    return np.bincount(np.clip(v, 0, C - 1), minlength=C)
+
+
+def rgb_classes(rgb):
+    """uint8 [n,3] -> uint8 [n] (segk_rgb_label_to_classes)"""
+    return rgb_to_classes(np.asarray(rgb)).astype(np.uint8)
+
+
 def class_weights(labels, C, ignore_index=None, unimportant=None, normalize_target_sum=-1.0):
     """utils.py:166-198 -> (counts int64 [C], weights float32 [C])"""
     counts = np.zeros(C, np.int64)
     for lab in labels:
-        v = np.asarray(lab).astype(np.int64).ravel()
-        if ignore_index is not None:
-            v = v[v != ignore_index]
-        counts += np.bincount(np.clip(v, 0, C - 1), minlength=C)
+        counts += label_hist(lab, C, ignore_index)
     freq = counts.astype(np.float64) / float(counts.sum())
     w = 1.0 / (freq + 1e-6)
     if unimportant:
@@ -303,3 +318,69 @@ def class_weights(labels, C, ignore_index=None, unimportant=None, normalize_targ
     for v in w:                                     # a plain left-to-right float64 sum
         tot += float(v)
     return counts, (w / tot * target).astype(np.float32)
+
+
+# ---- class counts: launch arithmetic and the case table of tests/test_gpu_label_count_matrix.py ------------------------------
+HIST_MAX_BLOCKS, HIST_PER_BLOCK, HIST_PER_PASS = 1024, 4096, 1024
+
+
+def hist_launch(n):
+    """label_hist_kernel -> (workgroups, passes of the longest-running workgroup's loop).  A workgroup takes 1024 labels per pass
+    and the grid is sized for four passes, up to 1024 workgroups; beyond 1024 * 4096 labels a fifth pass begins."""
+    blocks = min((n + HIST_PER_BLOCK - 1) // HIST_PER_BLOCK, HIST_MAX_BLOCKS)
+    return blocks, (n + blocks * HIST_PER_PASS - 1) // (blocks * HIST_PER_PASS)
+
+
+HIST_N = [1, 3, 4, 5, 1023, 1024, 1025, 4096, 4097, 1024 * 4096, 1024 * 4096 + 1, 1024 * 4096 + 4097]
+HIST_CLASSES = [1, 2, 4, 21, 256]
+HIST_BAD = [-5, None, 2 ** 40, -2 ** 63]            # None: the class count C itself, one past the last class
+
+
+def hist_cases():
+    """(elem_bytes, n, C, ignore | None): C and the ignore mode walk the n values with strides of their own -- none, a value inside
+    0..C-1, 255 with C = 4, and -100 (int64 only; uint8 takes the inside value again)"""
+    out = []
+    for d, eb in enumerate((1, 8)):
+        for i, n in enumerate(HIST_N):
+            C = HIST_CLASSES[(i + 2 * d) % 5]
+            mode = (i + i // 4 + d) % 4
+            if mode == 2:
+                C, ign = 4, 255
+            elif mode == 3 and eb == 8:
+                ign = -100
+            else:
+                ign = None if mode == 0 else (i + d) % C
+            out.append((eb, n, C, ign))
+    return out
+
+
+def hist_labels(eb, n_max):
+    """the master array every case is a prefix of: values 0..255; int64 also holds -100 and the values of HIST_BAD at strides of
+    their own (the class count stands in as 300, above every C)"""
+    v = np.minimum((u01(n_max, 77 + eb).astype(np.float64) * 256).astype(np.int64), 255)
+    if eb == 1:
+        return v.astype(np.uint8)
+    v[2::29] = -100
+    for i, bad in enumerate(HIST_BAD):
+        v[1 + i::31 + 2 * i] = 300 if bad is None else bad
+    return v
+
+
+def hist_case_labels(master, n, C):
+    """the first n labels of the master array with the stand-in 300 replaced by C"""
+    v = master[:n]
+    return v if v.dtype == np.uint8 else np.where(v == 300, C, v)
+
+
+RGB_N =[1, 255, 256, 257, 65537]
+RGB_COLOURS = [(0, 0, 0), (255, 255, 255), (128, 0, 0), (0, 128, 0),                       # the four named colours
+               (0, 0, 128), (0, 128, 128), (255, 255, 254),                                # near misses
+               (1, 0, 0), (0, 1, 0), (0, 0, 1), (254, 255, 255), (255, 254, 255), (129, 0, 0), (127, 0, 0), (128, 1, 0),
+               (128, 0, 1), (0, 129, 0), (0, 127, 0), (1, 128, 0), (0, 128, 1), (128, 128, 0), (128, 128, 128)]
+
+
+def rgb_pixels(n):
+    """uint8 [n,3]: the colours above in a fixed shuffle"""
+    idx = np.minimum((u01(n, 99).astype(np.float64) * len(RGB_COLOURS)).astype(np.int64), len(RGB_COLOURS) - 1)
+    idx[:min(n, len(RGB_COLOURS))] = np.arange(min(n, len(RGB_COLOURS)))
+    return np.array(RGB_COLOURS, dtype=np.uint8)[idx]

@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import recon_reference as R
 from oracle.fill import fill, fill_module
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,16 @@ def _head_case(seg, dtype, B, H, W, Cin, Cout, seed, wscale=None, bias=None):
 SHAPES = [(1, 7, 13), (2, 32, 48), (3, 37, 61)]
 
 
+def assert_head_forward(rec, xa, wp, bp, dtype, Cin):
+    """per output within the derived gate of tests/recon_reference.py (gamma_m S / 4 + 4 d_sig on the operands the kernel
+    consumes) and, where that is looser, within the flat 1e-5 this test has always held"""
+    rec64, S, z = R.head(xa.detach().float().cpu().permute(0, 2, 3, 1), wp.detach().cpu(), bp.detach().cpu(), dtype)
+    gate = torch.clamp(R.head_bound(S, z, Cin), max=1e-5)
+    err = (rec.detach().cpu().double() - rec64).abs()
+    print(f"head forward {dtype} Cin={Cin}: max err {err.max().item():.3e}, max err / gate {(err / gate).max().item():.4f}")
+    assert bool(torch.isfinite(rec).all()) and bool((err <= gate).all()), float((err / gate).max())
+
+
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("Cin", [32, 64, 96])
 @pytest.mark.parametrize("Cout", [1, 3, 4, 11])
@@ -70,6 +81,7 @@ def test_head_fp32_forward_backward_vs_float64(seg, shape, Cin, Cout):
     r64 = torch.sigmoid(F.conv2d(x64, w64, b64, padding=1))
     r64.backward(drec.double())
     assert (rec.detach().cpu().double() - r64.detach()).abs().max().item() < 1e-5
+    assert_head_forward(rec, xa, wp, bp, "fp32", Cin)
     for mine, ref in ((xa.grad, x64.grad), (wp.grad, w64.grad), (bp.grad, b64.grad)):
         err = (mine.detach().float().cpu().double() - ref).abs().max().item()
         assert err <= 1e-4 * ref.abs().max().item() + 1e-12, (err, ref.abs().max().item())
@@ -88,6 +100,7 @@ def test_head_bf16_forward_vs_float64_on_rounded_operands(seg, shape, Cin, Cout)
     w64 = wp.detach().cpu().bfloat16().double()
     r64 = torch.sigmoid(F.conv2d(x64, w64, bp.detach().cpu().double(), padding=1))
     assert (rec.detach().cpu().double() - r64).abs().max().item() < 1e-5
+    assert_head_forward(rec, xa, wp, bp, "bf16", Cin)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
