@@ -21,4 +21,5 @@ from .components import components, Components, Clean, mask_finish              
 from .calibration import (Reliability, reliability, TemperatureFit, fit_temperature, refine_temperature,            # noqa: F401
                           default_temperatures, inverse_temperatures, fit_from_counts)
 from .distill import Teacher, TeacherViews, DistillLoss, teacher_table, TEACHER_DESC                                 # noqa: F401
-from .training import train_loop_distill                                                                            # noqa: F401
+from .training import train_loop, eval_loop, train_loop_distill                                                      # noqa: F401
+from .optim import AdamW                                                                                            # noqa: F401

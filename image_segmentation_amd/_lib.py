@@ -10,11 +10,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 322         # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 323         # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
+OPTIM_CHUNK = 4096       # SEGK_OPTIM_CHUNK
+OPTIM_MAX_GROUPS = 1024  # SEGK_OPTIM_MAX_GROUPS
+# flags of segk_optim_grad_norm (CLIP, SKIP_NONFINITE) and of segk_optim_adamw (NORMED, SKIP_NONFINITE, EMA_WARMUP, SWAP)
+OPTIM_CLIP, OPTIM_SKIP_NONFINITE, OPTIM_NORMED, OPTIM_EMA_WARMUP, OPTIM_SWAP = 1, 2, 1, 4, 8
 
 _vp, _fp, _i, _l, _f, _d = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
@@ -124,6 +128,8 @@ SIGNATURES = {
     "segk_rgb_label_to_classes": (_i, [_vp, _vp, _l, _vp]),
     "segk_perturb_point": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "segk_perturb_blur": (_i, [_vp, _i, _i, _i, _vp]),
+    "segk_optim_grad_norm": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _d, _i, _i, _vp]),
+    "segk_optim_adamw": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
 }
 
 
@@ -139,6 +145,19 @@ class PackEntry(C.Structure):
     _fields_ = [("w", C.c_void_p), ("dst_fwd", C.c_void_p), ("dst_dgrad", C.c_void_p), ("Cout", C.c_int), ("CA", C.c_int),
                 ("CB", C.c_int), ("Coutp", C.c_int), ("CAp", C.c_int), ("CBp", C.c_int), ("block0", C.c_int), ("kind", C.c_int),
                 ("pad_", C.c_int * 2)]
+
+
+class OptimRec(C.Structure):
+    """segk_optim_rec of include/segk.h (one tensor of the optimizer table, 64 bytes)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("shadow", C.c_void_p),
+                ("numel", C.c_int64), ("block0", C.c_int32), ("group", C.c_int32), ("pad_", C.c_int32 * 2)]
+
+
+class OptimGroup(C.Structure):
+    """segk_optim_group of include/segk.h (the per-step scalars of one param group, 64 bytes)."""
+    _fields_ = [("lr", C.c_float), ("decay", C.c_float), ("omb1", C.c_float), ("b2", C.c_float), ("omb2", C.c_float),
+                ("eps", C.c_float), ("omd", C.c_float), ("ema_decay", C.c_float), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("pad_", C.c_int32 * 4)]
 
 
 _lib = None

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 322
-#define SEGK_ENTRY_COUNT 104
+#define SEGK_ABI_VERSION 323
+#define SEGK_ENTRY_COUNT 106
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -697,6 +697,61 @@ int segk_mse_fwd(const float* a, const float* b, float* part, int part_floats, f
  * the device.  db (may be NULL) = -da, the gradient of the target. */
 int segk_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, long n, int mean,
                  segk_stream_t s);
+
+/* ---- optimizer step: global-norm clipping + AdamW + weight EMA ------------------------------------------------------------
+ * Replaces the notebooks' `optimizer = torch.optim.AdamW(model.parameters(), weight_decay=0.01)` cell and its
+ * optimizer.step() (utils/training.py), plus what trainers compose around it (clip_grad_norm_, an EMA of the weights).
+ * The arithmetic is defined in DESIGN.md section 3.13 (float32, every operation rounded once).
+ *
+ * table: device array of n records sorted by block0; tensor i owns ceil(numel / SEGK_OPTIM_CHUNK) consecutive blocks from
+ * block0, total_blocks is their sum (tensors of 0 elements are left out).  All tensors are dense fp32.  The 16-byte vector
+ * path runs where every pointer of a record is 16-byte aligned, a per-element path elsewhere.
+ * groups: device array of ngroups records, uploaded by the host every step (lr may move between steps).
+ * state: 32 + 2 * (8 + 16 * ngroups) bytes of device memory that persist across steps:
+ *   { double norm; float clip; int32 finite; int32 skipped; int32 pad[3] } then two slots { int32 t; int32 pad;
+ *   double pow[ngroups][2] } (beta1^t, beta2^t as running products).  A step reads slot `parity` and writes slot parity ^ 1:
+ *   the host flips parity with every step it launches.  Initial content: clip 1, finite 1, slot pow 1.0, everything else 0.
+ * The table, the groups and the state must stay valid until the launch has run. */
+#define SEGK_OPTIM_CHUNK 4096            /* elements per block */
+#define SEGK_OPTIM_MAX_GROUPS 1024
+#define SEGK_OPTIM_CLIP 1                /* grad_norm: clip = min(1, max_norm / (norm + 1e-6)); otherwise clip = 1 */
+#define SEGK_OPTIM_SKIP_NONFINITE 2      /* both: a step whose gradients hold an inf or a NaN writes nothing */
+#define SEGK_OPTIM_NORMED 1              /* adamw: segk_optim_grad_norm ran for this step (same parity) on this stream */
+#define SEGK_OPTIM_EMA_WARMUP 4          /* adamw: d = min(ema_decay, (1 + t) / (10 + t)) in float32 instead of omd */
+#define SEGK_OPTIM_SWAP 8                /* adamw: exchange p and shadow of every record that has one; nothing else is read */
+typedef struct {
+  float* p;                          /* parameter */
+  const float* g;                    /* its gradient */
+  float* m;                          /* exp_avg */
+  float* v;                          /* exp_avg_sq */
+  float* shadow;                     /* EMA of p, or NULL */
+  int64_t numel;
+  int32_t block0;                    /* first block of this tensor in the launch */
+  int32_t group;                     /* index into groups */
+  int32_t pad_[2];
+} segk_optim_rec;                    /* 64 bytes */
+typedef struct {
+  float lr;                          /* float32(lr) */
+  float decay;                       /* float32(1 - lr * weight_decay), formed in float64 */
+  float omb1, b2, omb2;              /* float32(1 - beta1), float32(beta2), float32(1 - beta2) */
+  float eps;
+  float omd;                         /* float32(1 - ema_decay), formed in float64 */
+  float ema_decay;                   /* float32(ema_decay): read with SEGK_OPTIM_EMA_WARMUP only */
+  double beta1, beta2;               /* multipliers of the running products */
+  int32_t pad_[4];
+} segk_optim_group;                  /* 64 bytes */
+/* Sum of squares of every gradient of the table in float64 with a fixed assignment of elements to threads and fixed
+ * reduction trees (no float atomics: identical gradients give identical bits, run to run and rank to rank).  part: scratch of
+ * total_blocks doubles.  The last block to arrive writes state->norm, clip (rounded once to float32) and finite, and the next
+ * slot of the step state: t + 1 and pow * beta when the step will be applied (finite, or no SEGK_OPTIM_SKIP_NONFINITE), a
+ * copy and skipped + 1 otherwise. */
+int segk_optim_grad_norm(const segk_optim_rec* table, int n, int total_blocks, const segk_optim_group* groups, int ngroups,
+                         void* state, double* part, double max_norm, int flags, int parity, segk_stream_t s);
+/* One pass per element: reads g, p, m, v (and shadow), writes p, m, v (and shadow).  With SEGK_OPTIM_NORMED the gradient is
+ * scaled by state->clip and the step state is read from slot parity ^ 1; without it every block derives t + 1 and pow * beta
+ * from slot parity and block 0 stores them to slot parity ^ 1.  SEGK_OPTIM_SWAP: groups and state may be NULL. */
+int segk_optim_adamw(const segk_optim_rec* table, int n, int total_blocks, const segk_optim_group* groups, int ngroups,
+                     void* state, int flags, int parity, segk_stream_t s);
 
 /* ---- diagnostics (not on the product path) ---------------------------------------------------------
  * The shader clock held under a dense bf16 MFMA load: `blocks` workgroups of four waves (one per SIMD) run `iters` rounds of

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill, hardloss)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill, hardloss, optim)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1010,7 +1010,86 @@ def calib():
     print(f"written to {path}")
 
 
+def optim():
+    """The optimizer step through the C ABI (csrc/optim.hip) on the U-Net's own parameter list (shapes of
+    seg.unet(3, 3); no model run): segk_optim_adamw alone, + segk_optim_grad_norm, + the EMA, against the stock compositions
+    on the same tensors in this process -- torch.optim.AdamW(fused=True) alone, + clip_grad_norm_, + _foreach_lerp_.
+    Alternating order, seven rounds of 20 steps each: median and min..max of the time per step.  Written to
+    profiles/optim_kbench.txt (or the file given with --out)."""
+    import image_segmentation_amd as seg
+    from image_segmentation_amd import optim as O
+    shapes = [tuple(p.shape) for p in seg.unet(3, 3).parameters()]
+    g = torch.Generator(device="cuda").manual_seed(0)
+    ps = [torch.randn(s, device="cuda", generator=g) * 0.05 for s in shapes]
+    gs = [torch.randn(s, device="cuda", generator=g) * 1e-3 for s in shapes]
+    ms, vs, ss = ([torch.zeros_like(p) for p in ps] for _ in range(3))
+    numel = sum(p.numel() for p in ps)
+    st = ops._stream()
+    group = {"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.01}
+    groups = torch.frombuffer(bytearray(O.group_scalars(group, 0.999)), dtype=torch.uint8).cuda()
+    state = torch.frombuffer(bytearray(O.state_bytes(0, [(1.0, 1.0)])), dtype=torch.uint8).cuda()
+
+    def table(ema):
+        tab, blocks = O.build_table([(p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), s.data_ptr() if ema else 0,
+                                      p.numel(), 0) for p, gr, m, v, s in zip(ps, gs, ms, vs, ss)])
+        return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).cuda(), blocks
+    (t0, blocks), (t1, _) = table(False), table(True)
+    part = torch.empty(blocks, dtype=torch.float64, device="cuda")
+    parity = [0]
+
+    def mine(tab, clip):
+        def f():
+            if clip:
+                _lib.call("segk_optim_grad_norm", tab.data_ptr(), len(ps), blocks, groups.data_ptr(), 1, state.data_ptr(),
+                          part.data_ptr(), 1.0, _lib.OPTIM_CLIP, parity[0], st)
+            _lib.call("segk_optim_adamw", tab.data_ptr(), len(ps), blocks, groups.data_ptr(), 1, state.data_ptr(),
+                      _lib.OPTIM_NORMED if clip else 0, parity[0], st)
+            parity[0] ^= 1
+        return f
+    params = [torch.nn.Parameter(p.clone()) for p in ps]
+    for p, gr in zip(params, gs):
+        p.grad = gr.clone()
+    stock_opt = torch.optim.AdamW(params, weight_decay=0.01, fused=True)
+    shadows = [p.detach().clone() for p in params]
+
+    def stock(clip, ema):
+        def f():
+            if clip:
+                torch.nn.utils.clip_grad_norm_(params, 1.0)
+            stock_opt.step()
+            if ema:
+                torch._foreach_lerp_(shadows, [p.detach() for p in params], 1e-3)
+        return f
+    fns = {"segk_optim_adamw": mine(t0, False), "torch AdamW(fused)": stock(False, False),
+           "segk grad_norm + adamw": mine(t0, True), "torch clip_grad_norm_ + AdamW(fused)": stock(True, False),
+           "segk grad_norm + adamw + EMA": mine(t1, True), "torch clip + AdamW(fused) + _foreach_lerp_": stock(True, True)}
+    ts = {k: [] for k in fns}
+    for _ in range(7):
+        for k, fn in fns.items():
+            ts[k].append(timeit(fn, 20))
+    lines = [f"optim: {len(ps)} tensors, {numel} parameters ({numel * 4 / 1e6:.1f} MB each of p, g, m, v, shadow), {blocks} blocks of "
+             f"{O.CHUNK} elements; us per step, median [min..max] of 7 rounds x 20 steps, alternating"]
+    moved = {"segk_optim_adamw": 7, "torch AdamW(fused)": 7, "segk grad_norm + adamw": 8, "torch clip_grad_norm_ + AdamW(fused)": 10,
+             "segk grad_norm + adamw + EMA": 10, "torch clip + AdamW(fused) + _foreach_lerp_": 13}
+    for k, t in ts.items():
+        med = sorted(t)[3]
+        lines.append(f"  {k:44s} {med:9.1f} us [{min(t):.1f}..{max(t):.1f}]  {moved[k]:2d} x {numel * 4 / 1e6:.0f} MB -> "
+                     f"{moved[k] * numel * 4 / med / 1e6:.2f} TB/s")
+    clk = ops.clock_probe()
+    lines.append(f"  clock probe: median {clk['median_ghz']} GHz; build {_lib.build_id()}")
+    print("\n".join(lines))
+    path = os.path.join(ROOT, "profiles", "optim_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "optim":
+        optim()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "calib":
         calib()
         sys.exit(0)
