@@ -1,34 +1,21 @@
-// BatchNorm2d (train/eval) finalisation, BN+ReLU apply, BN backward reductions, MaxPool2d(2,2)
-// forward/backward on NHWC tensors.  HBM-bound streaming kernels: every thread owns one 16-byte
-// channel vector (fixed channels -> per-channel constants live in registers) and walks pixels, so a
-// row of threads reads/writes whole contiguous pixel rows (coalesced 16 B per lane).
+// BatchNorm2d (train/eval) finalisation, BN+ReLU apply, BN backward reductions, MaxPool2d(2,2) forward/backward on NHWC
+// tensors.  HBM-bound streaming kernels: every thread owns one 16-byte channel vector (fixed channels -> per-channel constants
+// live in registers) and walks pixels, so a row of threads reads/writes whole contiguous pixel rows (coalesced 16 B per lane).
+// The lane map, the pixel walk, the block row reduce, the float64 sum of partial rows, the statistics finish and the 2x2 window
+// are stated once, in channel_lanes.hpp.
 //
 // Reference semantics: torch.nn.BatchNorm2d as instantiated at unet/unet.py:17,20 and
 // clip/clipunet.py:88,91 (eps 1e-5, momentum 0.1, biased variance to normalise, unbiased variance into
 // running_var), nn.ReLU, nn.MaxPool2d(2,2) at unet.py:40 (backward routes to the first maximum in
 // row-major window order).
 #include <atomic>
-#include "common.hpp"
+#include "channel_lanes.hpp"
 #include "segk_internal.h"
 #include "ticket.hpp"
 #include "../../include/segk.h"
 
 namespace {
 __device__ unsigned g_tickets[TICKET_SLOTS * TICKET_GROUPS];     // zeroed per launch by the host (ticket.hpp)
-
-// block = CVB channel-vectors x ROWS pixel lanes (CVB*ROWS <= 256); grid.y covers channel blocks.
-struct Lanes {
-  int cx, ry, cv;
-  bool active;
-};
-__device__ __forceinline__ Lanes lanes(int cvb, int cvec) {
-  Lanes l;
-  l.cx = threadIdx.x % cvb;
-  l.ry = threadIdx.x / cvb;
-  l.cv = blockIdx.y * cvb + l.cx;
-  l.active = l.cv < cvec;
-  return l;
-}
 
 // ---------------------------------------------------------------------------------------------
 constexpr int NCH = 32;   // first-stage chunks of the per-tile statistics reduction
@@ -75,37 +62,19 @@ __device__ __forceinline__ void finalize_channels(const double* __restrict__ par
   sh[ry][cx][1] = s2;
   __syncthreads();
   if (ry != 0 || c >= C) return;
-  if (c >= C_real) {  // padded channel: stays identically zero
-    scale[c] = 0.f; shift[c] = 0.f;
-    if (mean_out) { mean_out[c] = 0.f; rstd_out[c] = 0.f; }
-    return;
-  }
+  if (c >= C_real) return bn_channel_zero(c, scale, shift, mean_out, rstd_out);
   const float g = gamma[c], be = beta[c];
   const float cb = conv_bias ? conv_bias[c] : 0.f;
   if (training) {
     s1 = 0.0; s2 = 0.0;
     for (int r = 0; r < 8; ++r) { s1 += sh[r][cx][0]; s2 += sh[r][cx][1]; }
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = g * rstd;
-    scale[c] = sc;
-    shift[c] = be - (float)mean * sc;      // applied to the bias-free conv output: the bias cancels
-    mean_out[c] = (float)mean;
-    rstd_out[c] = rstd;
-    if (rmean) {
-      const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-      rmean[c] = (1.f - momentum) * rmean[c] + momentum * ((float)mean + cb);
-      rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
-    }
-  } else {
-    const float rstd = 1.f / sqrtf(rvar[c] + eps);
-    const float sc = g * rstd;
-    scale[c] = sc;
-    shift[c] = be + (cb - rmean[c]) * sc;
-    if (mean_out) { mean_out[c] = rmean[c] - cb; rstd_out[c] = rstd; }
+    return bn_channel_finish(s1, s2, count, c, g, be, cb, rmean, rvar, momentum, eps, scale, shift, mean_out, rstd_out);
   }
+  const float rstd = 1.f / sqrtf(rvar[c] + eps);
+  const float sc = g * rstd;
+  scale[c] = sc;
+  shift[c] = be + (cb - rmean[c]) * sc;
+  if (mean_out) { mean_out[c] = rmean[c] - cb; rstd_out[c] = rstd; }
 }
 
 // eval mode (no statistics to reduce): stage B alone
@@ -121,60 +90,18 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
 }
 
 // training mode, few partial rows (MT <= 1024: every layer but the 128-channel ones at 128x128 and above): one block of
-// 32 row lanes x 32 channels walks all rows itself, sixteen rows in flight per lane, and finishes -- no second stage at all
+// 32 row lanes x 32 channels walks all rows itself (sum_rows16) and finishes -- no second stage at all
 __global__ __launch_bounds__(1024) void bn_stats_finalize_small_kernel(const float* __restrict__ part, int MT, int C,
                                                                        int C_real, double count, const float* conv_bias,
                                                                        const float* gamma, const float* beta, float* rmean,
                                                                        float* rvar, float momentum, float eps, float* scale,
                                                                        float* shift, float* mean_out, float* rstd_out) {
-  __shared__ double sh[32][32][2];
-  const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cx;
-  // sixteen rows in flight per lane and ONE accumulator pair (the registers hold loads, not partial sums: 1024 threads leave
-  // 128 per lane): MT <= 512 is a single memory round trip.  Fixed order of additions: bit-stable
-  double s1 = 0.0, s2 = 0.0;
-#pragma unroll 1
-  for (int m = ry; m < MT; m += 512) {
-    float2 v[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {   // unconditional loads of a clamped row (a conditional load compiles to branch + wait)
-      const int r = m + 32 * u < MT ? m + 32 * u : MT - 1;
-      v[u] = ((const float2*)part)[(unsigned)r * (unsigned)C + (unsigned)c];
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const bool ok = m + 32 * u < MT;
-      s1 += ok ? (double)v[u].x : 0.0;
-      s2 += ok ? (double)v[u].y : 0.0;
-    }
-  }
-  sh[ry][cx][0] = s1;
-  sh[ry][cx][1] = s2;
-  __syncthreads();
-  if (ry != 0) return;
-  s1 = 0.0; s2 = 0.0;
-#pragma unroll 8
-  for (int r = 0; r < 32; ++r) { s1 += sh[r][cx][0]; s2 += sh[r][cx][1]; }   // (32 reads in flight would spill)
-  if (c >= C_real) {  // padded channel: stays identically zero
-    scale[c] = 0.f; shift[c] = 0.f; mean_out[c] = 0.f; rstd_out[c] = 0.f;
-    return;
-  }
-  const float g = gamma[c], be = beta[c];
-  const float cb = conv_bias ? conv_bias[c] : 0.f;
-  const double mean = s1 / count;
-  double var = s2 / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = g * rstd;
-  scale[c] = sc;
-  shift[c] = be - (float)mean * sc;      // applied to the bias-free conv output: the bias cancels
-  mean_out[c] = (float)mean;
-  rstd_out[c] = rstd;
-  if (rmean) {
-    const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * ((float)mean + cb);
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
-  }
+  double s[2];
+  if (!sum_rows16<2>(part, MT, C, s)) return;
+  const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+  if (c >= C_real) return bn_channel_zero(c, scale, shift, mean_out, rstd_out);
+  bn_channel_finish(s[0], s[1], count, c, gamma[c], beta[c], conv_bias ? conv_bias[c] : 0.f, rmean, rvar, momentum, eps, scale, shift,
+                    mean_out, rstd_out);
 }
 
 // training mode, ONE launch: grid (C/32, NCH) blocks reduce their chunk of the per-tile partials (stage A); the block that
@@ -201,27 +128,25 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const T* __restrict_
                                                             const float* scale, const float* shift, long P, int C,
                                                             int cvb, int rows) {
   using E = ET<T>;
-  const Lanes l = lanes(cvb, C / E::VEC);
-  if (!l.active || l.ry >= rows) return;
+  const ChannelLanes l = channel_lanes(cvb, rows, C / E::VEC);
+  if (!l.active()) return;
   float sc[E::VEC], sh[E::VEC];
 #pragma unroll
   for (int j = 0; j < E::VEC; ++j) { sc[j] = scale[l.cv * E::VEC + j]; sh[j] = shift[l.cv * E::VEC + j]; }
-  auto one = [&](const uint4 raw, const size_t off) {
-    float f[E::VEC];
-    unpack16<T>(raw, f);
+  const size_t cofs = (size_t)l.cv * E::VEC;
+  walk_pixels<APPLY_FLIGHT>((long)blockIdx.x * rows + l.ry, (long)gridDim.x * rows, P,
+                            [&](long p) { return *(const uint4*)(z + (size_t)p * C + cofs); },
+                            [&](long p, const uint4 raw) {
+                              float f[E::VEC];
+                              unpack16<T>(raw, f);
 #pragma unroll
-    for (int j = 0; j < E::VEC; ++j) f[j] = fmaxf(fmaf(f[j], sc[j], sh[j]), 0.f);
-    *(uint4*)(y + off) = pack16<T>(f);
-  };
-  // one pixel per thread per pass: like the backward apply pass (see there) this read + write stream does not gain from
-  // more loads in flight per thread
-  for (long p = (long)blockIdx.x * rows + l.ry; p < P; p += (long)gridDim.x * rows) {
-    const size_t off = (size_t)p * C + (size_t)l.cv * E::VEC;
-    one(*(const uint4*)(z + off), off);
-  }
+                              for (int j = 0; j < E::VEC; ++j) f[j] = fmaxf(fmaf(f[j], sc[j], sh[j]), 0.f);
+                              *(uint4*)(y + (size_t)p * C + cofs) = pack16<T>(f);
+                            });
 }
 
 // ---------------------------------------------------------------------------------------------
+struct ZD { uint4 z, d; };   // one pixel of the backward passes: the channel vectors of z and dy
 // BN backward pass 1: g = dy * [z*scale+shift > 0];  partial sums of g and g*xhat per channel.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ z,
@@ -229,109 +154,49 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
                                                             const float* mean, const float* rstd, long P, int C,
                                                             int cvb, int rows, float* part) {
   using E = ET<T>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = (float*)smem;  // [rows][cvb][2*VEC]
-  const Lanes l = lanes(cvb, C / E::VEC);
-  float sg[E::VEC], sgx[E::VEC];
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // [rows][cvb][2*VEC]
+  const ChannelLanes l = channel_lanes(cvb, rows, C / E::VEC);
+  float s[2 * E::VEC];                                          // sum g, then sum g * xhat
 #pragma unroll
-  for (int j = 0; j < E::VEC; ++j) { sg[j] = 0.f; sgx[j] = 0.f; }
-  if (l.active && l.ry < rows) {
-    float sc[E::VEC], sh[E::VEC], mu[E::VEC], rs[E::VEC];
-#pragma unroll
-    for (int j = 0; j < E::VEC; ++j) {
-      const int c = l.cv * E::VEC + j;
-      sc[j] = scale[c]; sh[j] = shift[c]; mu[j] = mean[c]; rs[j] = rstd[c];
-    }
-    auto one = [&](const uint4 rz, const uint4 rd) {
-      float fz[E::VEC], fd[E::VEC];
-      unpack16<T>(rz, fz);
-      unpack16<T>(rd, fd);
-#pragma unroll
-      for (int j = 0; j < E::VEC; ++j) {
-        const float g = (fmaf(fz[j], sc[j], sh[j]) > 0.f) ? fd[j] : 0.f;
-        sg[j] += g;
-        sgx[j] = fmaf(g, (fz[j] - mu[j]) * rs[j], sgx[j]);
-      }
-    };
-    // four pixels (eight loads) per thread in flight: the grid is only two blocks per CU (short finalize), and left to itself
-    // the compiler keeps one pixel in flight.  Pixels are consumed in the old order: bit-identical sums
-    const long step = (long)gridDim.x * rows;
+  for (int j = 0; j < 2 * E::VEC; ++j) s[j] = 0.f;
+  if (l.active()) {
+    const BnConsts<E::VEC> k(scale, shift, mean, rstd, l.cv * E::VEC);
     const size_t cofs = (size_t)l.cv * E::VEC;
-    long p = (long)blockIdx.x * rows + l.ry;
-    for (; p + 3 * step < P; p += 4 * step) {
-      uint4 rz[4], rd[4];
+    // pixels are consumed in the order of a one-pixel walk: bit-identical sums
+    walk_pixels<REDUCE_FLIGHT>((long)blockIdx.x * rows + l.ry, (long)gridDim.x * rows, P,
+                               [&](long p) {
+                                 const size_t off = (size_t)p * C + cofs;
+                                 return ZD{*(const uint4*)(z + off), *(const uint4*)(dy + off)};
+                               },
+                               [&](long, const ZD& v) {
+                                 float fz[E::VEC], fd[E::VEC];
+                                 unpack16<T>(v.z, fz);
+                                 unpack16<T>(v.d, fd);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const size_t off = (size_t)(p + u * step) * C + cofs;
-        rz[u] = *(const uint4*)(z + off);
-        rd[u] = *(const uint4*)(dy + off);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise sinks the loads back to two in flight)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) one(rz[u], rd[u]);
-    }
-    for (; p < P; p += step) {
-      const size_t off = (size_t)p * C + cofs;
-      one(*(const uint4*)(z + off), *(const uint4*)(dy + off));
-    }
+                                 for (int j = 0; j < E::VEC; ++j) {
+                                   const float g = (fmaf(fz[j], k.sc[j], k.sh[j]) > 0.f) ? fd[j] : 0.f;
+                                   s[j] += g;
+                                   s[E::VEC + j] = fmaf(g, (fz[j] - k.mu[j]) * k.rs[j], s[E::VEC + j]);
+                                 }
+                               });
   }
-  if (l.ry < rows) {
-    float* r = red + ((size_t)l.ry * cvb + l.cx) * (2 * E::VEC);
+  reduce_lane_rows(reinterpret_cast<float*>(smem), l, cvb, rows, 2 * E::VEC, s, [&](const float (&tot)[2 * E::VEC]) {
+    float2* dst = (float2*)part + (size_t)blockIdx.x * C + l.cv * E::VEC;
 #pragma unroll
-    for (int j = 0; j < E::VEC; ++j) { r[j] = sg[j]; r[E::VEC + j] = sgx[j]; }
-  }
-  __syncthreads();
-  if (l.ry == 0 && l.active) {
-#pragma unroll
-    for (int j = 0; j < E::VEC; ++j) {
-      float a = 0.f, b = 0.f;
-      for (int r = 0; r < rows; ++r) {  // fixed order
-        const float* q = red + ((size_t)r * cvb + l.cx) * (2 * E::VEC);
-        a += q[j];
-        b += q[E::VEC + j];
-      }
-      float2* dst = (float2*)part + (size_t)blockIdx.x * C + l.cv * E::VEC + j;
-      *dst = make_float2(a, b);
-    }
-  }
+    for (int j = 0; j < E::VEC; ++j) dst[j] = make_float2(tot[j], tot[E::VEC + j]);
+  });
 }
 
-// partials [NB][C][2] -> dgamma, dbeta, coef = (sum_g/N, sum_gx/N)
+// partials [NB][C][2] -> dgamma, dbeta, coef = (sum_g/N, sum_gx/N); NB <= 512 (segk_bn_bwd_blocks) is ONE memory round trip
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ part, int NB, int C,
                                                                int C_real, double count, float* dgamma, float* dbeta,
                                                                float* coef) {
-  // 32 channels x 32 row-lanes per block: the NB block partials are walked in 32 interleaved streams
-  __shared__ double sh[32][32][2];
-  const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cx;
-  double s1 = 0.0, s2 = 0.0;
-  if (c < C) {
-    // sixteen rows in flight per lane, one accumulator pair: NB <= 512 (segk_bn_bwd_blocks) is ONE memory round trip.
-    // Fixed order of additions: bit-stable
-    for (int m = ry; m < NB; m += 512) {
-      float2 v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {   // unconditional loads of a clamped row (a conditional load compiles to branch + wait)
-        const int r = m + 32 * u < NB ? m + 32 * u : NB - 1;
-        v[u] = ((const float2*)part)[(unsigned)r * (unsigned)C + (unsigned)c];
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const bool ok = m + 32 * u < NB;
-        s1 += ok ? (double)v[u].x : 0.0;
-        s2 += ok ? (double)v[u].y : 0.0;
-      }
-    }
-  }
-  sh[ry][cx][0] = s1;
-  sh[ry][cx][1] = s2;
-  __syncthreads();
-  if (ry != 0 || c >= C) return;
-  s1 = 0.0; s2 = 0.0;
-  for (int r = 0; r < 32; ++r) { s1 += sh[r][cx][0]; s2 += sh[r][cx][1]; }   // fixed order
-  if (c < C_real) { dbeta[c] = (float)s1; dgamma[c] = (float)s2; }
-  coef[2 * c] = (float)(s1 / count);
-  coef[2 * c + 1] = (float)(s2 / count);
+  double s[2];
+  if (!sum_rows16<2>(part, NB, C, s)) return;
+  const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+  if (c < C_real) { dbeta[c] = (float)s[0]; dgamma[c] = (float)s[1]; }
+  coef[2 * c] = (float)(s[0] / count);
+  coef[2 * c + 1] = (float)(s[1] / count);
 }
 
 // BN backward pass 2 (in place allowed): dz = scale * (g - c1 - xhat*c2)
@@ -341,33 +206,26 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            const float* shift, const float* mean, const float* rstd,
                                                            const float* coef, long P, int C, int cvb, int rows) {
   using E = ET<T>;
-  const Lanes l = lanes(cvb, C / E::VEC);
-  if (!l.active || l.ry >= rows) return;
-  float sc[E::VEC], sh[E::VEC], mu[E::VEC], rs[E::VEC], c1[E::VEC], c2[E::VEC];
-#pragma unroll
-  for (int j = 0; j < E::VEC; ++j) {
-    const int c = l.cv * E::VEC + j;
-    sc[j] = scale[c]; sh[j] = shift[c]; mu[j] = mean[c]; rs[j] = rstd[c];
-    c1[j] = coef[2 * c]; c2[j] = coef[2 * c + 1];
-  }
+  const ChannelLanes l = channel_lanes(cvb, rows, C / E::VEC);
+  if (!l.active()) return;
+  const BnConsts<E::VEC, true> k(scale, shift, mean, rstd, l.cv * E::VEC, coef);
+  const size_t cofs = (size_t)l.cv * E::VEC;
   auto one = [&](const uint4 rz, const uint4 rd, const size_t off) {
     float fz[E::VEC], fd[E::VEC];
     unpack16<T>(rz, fz);
     unpack16<T>(rd, fd);
 #pragma unroll
-    for (int j = 0; j < E::VEC; ++j) fd[j] = bn_relu_bwd_dz(fz[j], fd[j], sc[j], sh[j], mu[j], rs[j], c1[j], c2[j]);
+    for (int j = 0; j < E::VEC; ++j)
+      fd[j] = bn_relu_bwd_dz(fz[j], fd[j], k.sc[j], k.sh[j], k.mu[j], k.rs[j], k.c1[j], k.c2[j]);
     *(uint4*)(dz + off) = pack16<T>(fd);
   };
-  // APF pixels (2 APF loads) per thread in flight, all issued before the first store (dz may be dy or z: in place allowed,
-  // a thread only ever reads the elements it writes).  Measured at B = 32 (reduce + finalize + apply, us, same box):
-  // APF 1 / 2 / 4 = 250 / 274 / 278 at 64 ch x 256^2, 122 / 125 / 132 at 128 x 128^2 -- a pass that WRITES as much as it reads
-  // streams best with one pixel per thread and the occupancy that leaves; the read-only reduce pass gains from four
-#ifndef SEGK_BN_APPLY_FLIGHT
-#define SEGK_BN_APPLY_FLIGHT 1
-#endif
-  constexpr int APF = SEGK_BN_APPLY_FLIGHT;
+  // Not walk_pixels: through it (one loop) the bf16 instance takes 78 registers instead of 100 and six waves instead of four, and
+  // ran 2 to 3 us slower at 128 ch x 128^2 and 64 ch x 256^2 (profiles/channel_refactor_kbench.txt) -- this pass, which writes as
+  // much as it reads, streams best at the occupancy the two-loop form leaves.  APPLY_FLIGHT pixels (2 loads each) per thread in
+  // flight, all issued before the first store (dz may be dy or z: in place allowed, a thread only ever reads the elements it
+  // writes)
+  constexpr int APF = APPLY_FLIGHT;
   const long step = (long)gridDim.x * rows;
-  const size_t cofs = (size_t)l.cv * E::VEC;
   long p = (long)blockIdx.x * rows + l.ry;
   for (; p + (APF - 1) * step < P; p += APF * step) {
     size_t o[APF];
@@ -404,27 +262,18 @@ __global__ __launch_bounds__(256) void bn_relu_apply_pool_kernel(const T* __rest
     float sc[E::VEC], sh[E::VEC], mx[E::VEC];
 #pragma unroll
     for (int j = 0; j < E::VEC; ++j) { sc[j] = scale[cv * E::VEC + j]; sh[j] = shift[cv * E::VEC + j]; mx[j] = 0.f; }
-    // the four loads of the window are issued together, unconditionally, from coordinates clamped into the image (a load
-    // under a per-lane condition compiles to branch + load + wait: four serial round trips per window)
-    size_t offs[4];
+    const Window2x2<T> win(b, yo, xo, cv, H, W, C);
     uint4 raw[4];
+    win.load(z, raw);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int yy = 2 * yo + (k >> 1), xx = 2 * xo + (k & 1);
-      offs[k] = (((size_t)(b * H + (yy < H ? yy : H - 1))) * W + (xx < W ? xx : W - 1)) * C + cv * E::VEC;
-      raw[k] = *(const uint4*)(z + offs[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int yy = 2 * yo + (k >> 1), xx = 2 * xo + (k & 1);
-      if (yy >= H || xx >= W) continue;
-      const size_t off = offs[k];
+      if (!win.inside(k)) continue;
       float f[E::VEC];
       unpack16<T>(raw[k], f);
 #pragma unroll
       for (int j = 0; j < E::VEC; ++j) f[j] = fmaxf(fmaf(f[j], sc[j], sh[j]), 0.f);
       const uint4 pk = pack16<T>(f);
-      *(uint4*)(y + off) = pk;
+      *(uint4*)(y + win.off[k]) = pk;
       unpack16<T>(pk, f);                           // the rounded values the pooling would read back
 #pragma unroll
       for (int j = 0; j < E::VEC; ++j) mx[j] = fmaxf(mx[j], f[j]);   // y >= 0: 0 is a neutral start
@@ -458,8 +307,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
 // dx (+)= route(dy) ; one thread per 2x2 window x channel vector (windows tile the even part of the image).
 // STAT: x is the output y = relu(bn(z)) of a DoubleConv block and dx its complete gradient (skip gradient + routed
 // pool gradient): the kernel also accumulates that BatchNorm's backward reductions sum(g), sum(g * xhat) with
-// g = dx where y > 0 -- xhat is recovered from y itself where the ReLU is active, xhat = (y - shift) * rstd / scale - mean * rstd,
-// and pixels with y == 0 contribute nothing -- so the block's bn_bwd_reduce pass (a read of dx and z) disappears.
+// g = dx where y > 0 -- xhat is recovered from y itself where the ReLU is active (xhat_from_y), and pixels with y == 0
+// contribute nothing -- so the block's bn_bwd_reduce pass (a read of dx and z) disappears.
 // Needs a power-of-two number of channel vectors (a thread then keeps its channels); channels with scale == 0 or
 // |scale| < |shift| / 16 take xhat from z instead (see from_z below; without z they would get xhat = -mean * rstd).
 template <typename T, bool STAT>
@@ -484,10 +333,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
 #pragma unroll
     for (int j = 0; j < E::VEC; ++j) {
       const int c = cv0 * E::VEC + j;
-      const float sc = scale[c], rs = rstd[c], sh = shift[c];
+      const float sc = scale[c], sh = shift[c];
       from_z = from_z || (z != nullptr && (sc == 0.f || fabsf(sc) * 16.f < fabsf(sh)));
-      xa[j] = sc != 0.f ? rs / sc : 0.f;
-      xb[j] = -sh * xa[j] - mean[c] * rs;
+      xhat_from_y(sc, sh, mean[c], rstd[c], xa[j], xb[j]);
       sg[j] = 0.f; sgx[j] = 0.f;
     }
   }
@@ -495,22 +343,14 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
     const Idx4 ix = split4(i, (unsigned)CV, (unsigned)Wc, (unsigned)Hc);
     const int cv = ix.cv, xo = ix.x, yo = ix.y, b = ix.b;
     const bool inwin = (yo < Ho) && (xo < Wo);
-    // every load of the window is issued before any is used, unconditionally, from coordinates clamped into the image (a
-    // load under a per-lane condition compiles to branch + load + wait: nine serial memory round trips per window)
+    // every load of the window is issued before any is used (nine serial memory round trips per window otherwise); the pooled
+    // gradient too comes from a clamped window
     const int yoc = yo < Ho ? yo : Ho - 1, xoc = xo < Wo ? xo : Wo - 1;
     const uint4 rg = *(const uint4*)(dy + (((size_t)(b * Ho + yoc)) * Wo + xoc) * C + cv * E::VEC);
+    const Window2x2<T> win(b, yo, xo, cv, H, W, C);
     uint4 rv[4], ro[4];
-    size_t off[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int yy = 2 * yo + (k >> 1), xx = 2 * xo + (k & 1);
-      off[k] = (((size_t)(b * H + (yy < H ? yy : H - 1))) * W + (xx < W ? xx : W - 1)) * C + cv * E::VEC;
-      rv[k] = *(const uint4*)(x + off[k]);
-    }
-    if (accumulate) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ro[k] = *(const uint4*)(dx + off[k]);
-    }
+    win.load(x, rv);
+    if (accumulate) win.load(dx, ro);
     float g[E::VEC];
     float v[4][E::VEC];
     unpack16<T>(rg, g);
@@ -527,8 +367,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int yy = 2 * yo + (k >> 1), xx = 2 * xo + (k & 1);
-      if (yy >= H || xx >= W) continue;
+      if (!win.inside(k)) continue;
       float o[E::VEC];
       if (accumulate) unpack16<T>(ro[k], o);
 #pragma unroll
@@ -541,7 +380,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
           sgx[j] = fmaf(gg, fmaf(v[k][j], xa[j], xb[j]), sgx[j]);
         }
       }
-      *(uint4*)(dx + off[k]) = pack16<T>(o);
+      *(uint4*)(dx + win.off[k]) = pack16<T>(o);
     }
   }
   if (STAT) {
@@ -554,11 +393,11 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
       for (int j = 0; j < E::VEC; ++j) sgx[j] = 0.f;
       for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)total; i += gridDim.x * 256u) {
         const Idx4 ix = split4(i, (unsigned)CV, (unsigned)Wc, (unsigned)Hc);
-        const int cv = ix.cv, xo = ix.x, yo = ix.y, b = ix.b;
+        const int cv = ix.cv;
+        const Window2x2<T> win(ix.b, ix.y, ix.x, cv, H, W, C, false);
         for (int k = 0; k < 4; ++k) {
-          const int yy = 2 * yo + (k >> 1), xx = 2 * xo + (k & 1);
-          if (yy >= H || xx >= W) continue;
-          const size_t off = (((size_t)(b * H + yy)) * W + xx) * C + cv * E::VEC;
+          if (!win.inside(k)) continue;
+          const size_t off = win.at(k);
           float fy[E::VEC], fd[E::VEC], fz[E::VEC];
           unpack16<T>(*(const uint4*)(x + off), fy);
           unpack16<T>(*(const uint4*)(dx + off), fd);
@@ -592,82 +431,39 @@ template <typename T>
 __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ x, long P, int C, int cvb, int rows,
                                                           float* part) {
   using E = ET<T>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = (float*)smem;  // [rows][cvb][VEC]
-  const Lanes l = lanes(cvb, C / E::VEC);
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // [rows][cvb][VEC]
+  const ChannelLanes l = channel_lanes(cvb, rows, C / E::VEC);
   float s[E::VEC];
 #pragma unroll
   for (int j = 0; j < E::VEC; ++j) s[j] = 0.f;
-  if (l.active && l.ry < rows) {
-    auto one = [&](const uint4 raw) {
-      float f[E::VEC];
-      unpack16<T>(raw, f);
-#pragma unroll
-      for (int j = 0; j < E::VEC; ++j) s[j] += f[j];
-    };
-    // a read-only pass on two blocks per CU: four pixels per thread in flight, consumed in the old order (bit-identical sums)
-    const long step = (long)gridDim.x * rows;
+  if (l.active()) {
     const size_t cofs = (size_t)l.cv * E::VEC;
-    long p = (long)blockIdx.x * rows + l.ry;
-    for (; p + 3 * step < P; p += 4 * step) {
-      uint4 r[4];
+    walk_pixels<REDUCE_FLIGHT>((long)blockIdx.x * rows + l.ry, (long)gridDim.x * rows, P,
+                               [&](long p) { return *(const uint4*)(x + (size_t)p * C + cofs); },
+                               [&](long, const uint4 raw) {
+                                 float f[E::VEC];
+                                 unpack16<T>(raw, f);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = *(const uint4*)(x + (size_t)(p + u * step) * C + cofs);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) one(r[u]);
-    }
-    for (; p < P; p += step) one(*(const uint4*)(x + (size_t)p * C + cofs));
+                                 for (int j = 0; j < E::VEC; ++j) s[j] += f[j];
+                               });
   }
-  if (l.ry < rows) {
-    float* r = red + ((size_t)l.ry * cvb + l.cx) * E::VEC;
+  reduce_lane_rows(reinterpret_cast<float*>(smem), l, cvb, rows, E::VEC, s, [&](const float (&tot)[E::VEC]) {
+    float* dst = part + (size_t)blockIdx.x * C + l.cv * E::VEC;
 #pragma unroll
-    for (int j = 0; j < E::VEC; ++j) r[j] = s[j];
-  }
-  __syncthreads();
-  if (l.ry == 0 && l.active)
-#pragma unroll
-    for (int j = 0; j < E::VEC; ++j) {
-      float a = 0.f;
-      for (int r = 0; r < rows; ++r) a += red[((size_t)r * cvb + l.cx) * E::VEC + j];
-      part[(size_t)blockIdx.x * C + l.cv * E::VEC + j] = a;
-    }
+    for (int j = 0; j < E::VEC; ++j) dst[j] = tot[j];
+  });
 }
+// partials [NB][C] -> out; NB <= 512 (segk_bn_bwd_blocks) is one memory round trip
 __global__ __launch_bounds__(1024) void channel_sum_finalize_kernel(const float* __restrict__ part, int NB, int C,
                                                                     int C_real, float* out) {
-  // 32 channels x 32 row lanes, sixteen rows in flight per lane (unconditional loads of a clamped row): NB <= 512
-  // (segk_bn_bwd_blocks) is one memory round trip.  Fixed order of additions: bit-stable
-  __shared__ double sh[32][32];
-  const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cx;
-  double s = 0.0;
-  if (c < C) {
-    for (int m = ry; m < NB; m += 512) {
-      float v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int r = m + 32 * u < NB ? m + 32 * u : NB - 1;
-        v[u] = part[(unsigned)r * (unsigned)C + (unsigned)c];
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) s += (m + 32 * u < NB) ? (double)v[u] : 0.0;
-    }
-  }
-  sh[ry][cx] = s;
-  __syncthreads();
-  if (ry != 0 || c >= C_real) return;
-  s = 0.0;
-#pragma unroll 8
-  for (int r = 0; r < 32; ++r) s += sh[r][cx];
-  out[c] = (float)s;
+  double s[1];
+  if (!sum_rows16<1>(part, NB, C, s)) return;
+  const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+  if (c < C_real) out[c] = (float)s[0];
 }
 
-static inline void lane_geometry(int C, int vec, int* cvb, int* rows, int* gy) {
-  const int cvec = C / vec;
-  *cvb = cvec < 128 ? cvec : 128;
-  *rows = 256 / *cvb;
-  *gy = cdiv(cvec, *cvb);
-}
+template <typename T> constexpr int dtype_of() { return sizeof(T) == 2 ? SEGK_DT_BF16 : SEGK_DT_F32; }
+template <typename T> LaneGeometry bn_lanes(int C) { return lane_geometry(C / ET<T>::VEC, BN_LANE_CAP); }
 
 }  // namespace
 
@@ -734,24 +530,19 @@ int segk_bn_stats_floats(int tiles, int Cp) {
   return n > 0x7fffffffLL ? 0 : (int)n;     // sizes that do not fit an int are not served (the launch entries refuse them)
 }
 
-template <typename T>
-static int bn_relu_apply_t(const void* z, void* y, const float* scale, const float* shift, long P, int C, hipStream_t st) {
-  int cvb, rows, gy;
-  lane_geometry(C, ET<T>::VEC, &cvb, &rows, &gy);
-  long gx = (P + rows - 1) / rows;
-  if (gx > 4096) gx = 4096;
-  hipLaunchKernelGGL(bn_relu_apply_kernel<T>, dim3((int)gx, gy), dim3(256), 0, st, (const T*)z, (T*)y, scale, shift, P,
-                     C, cvb, rows);
-  SEGK_CHECK_LAUNCH("bn_relu_apply");
-  return 0;
-}
 extern "C" int segk_bn_relu_apply(const void* z, void* y, const float* scale, const float* shift, long P, int C, int dtype,
                                   segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("bn_relu_apply", dtype);
   hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(z && y && scale && shift && P > 0 && C > 0 && C % 32 == 0, "bn_relu_apply: bad arguments");
-  return dtype == SEGK_DT_BF16 ? bn_relu_apply_t<bf16_t>(z, y, scale, shift, P, C, st)
-                               : bn_relu_apply_t<float>(z, y, scale, shift, P, C, st);
+  return by_dtype(dtype, [&](auto Tc) {
+    using T = decltype(Tc);
+    const LaneGeometry g = bn_lanes<T>(C);
+    hipLaunchKernelGGL(bn_relu_apply_kernel<T>, dim3(apply_blocks(P, g.rows), g.gy), dim3(256), 0, st, (const T*)z, (T*)y, scale,
+                       shift, P, C, g.cvb, g.rows);
+    SEGK_CHECK_LAUNCH("bn_relu_apply");
+    return 0;
+  });
 }
 
 extern "C" int segk_bn_relu_apply_pool(const void* z, void* y, void* pooled, const float* scale, const float* shift, int B,
@@ -760,17 +551,14 @@ extern "C" int segk_bn_relu_apply_pool(const void* z, void* y, void* pooled, con
   hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(z && y && pooled && scale && shift && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 32 == 0,
                "bn_relu_apply_pool: bad arguments");
-  const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
-  long total = (long)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / vec);
-  SEGK_REQUIRE(total < (1L << 31), "bn_relu_apply_pool: more than 2^31 windows x channel vectors");
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (dtype == SEGK_DT_BF16)
-    hipLaunchKernelGGL(bn_relu_apply_pool_kernel<bf16_t>, dim3((int)g), dim3(256), 0, st, (const bf16_t*)z, (bf16_t*)y,
-                       (bf16_t*)pooled, scale, shift, B, H, W, C);
-  else
-    hipLaunchKernelGGL(bn_relu_apply_pool_kernel<float>, dim3((int)g), dim3(256), 0, st, (const float*)z, (float*)y,
-                       (float*)pooled, scale, shift, B, H, W, C);
+  const int g = window_grid(B, H, W, C, dtype, true, 8192);
+  SEGK_REQUIRE(g > 0, "bn_relu_apply_pool: more than 2^31 windows x channel vectors");
+  by_dtype(dtype, [&](auto Tc) {
+    using T = decltype(Tc);
+    hipLaunchKernelGGL(bn_relu_apply_pool_kernel<T>, dim3(g), dim3(256), 0, st, (const T*)z, (T*)y, (T*)pooled, scale, shift, B, H,
+                       W, C);
+    return 0;
+  });
   SEGK_CHECK_LAUNCH("bn_relu_apply_pool");
   return 0;
 }
@@ -786,169 +574,127 @@ int segk_bn_bwd_finalize_launch(const float* part, int nb, int C, int C_real, lo
 
 int segk_bn_bwd_blocks(long P, int C, int dtype) {
   if (P <= 0 || C <= 0 || C % 32 != 0) return 0;      // nonsense input: no blocks (the launch entries refuse it)
-  const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
-  int cvb, rows, gy;
-  lane_geometry(C, vec, &cvb, &rows, &gy);
-  long gx = (P + rows - 1) / rows;
-  if (gx > 512) gx = 512;      // enough blocks to fill the chip; keeps the finalize pass short
-  return (int)gx;
+  const int rows = lane_geometry(C / (dtype == SEGK_DT_BF16 ? 8 : 4), BN_LANE_CAP).rows;
+  const long gx = (P + rows - 1) / rows;
+  return (int)(gx > 512 ? 512 : gx);      // enough blocks to fill the chip; keeps the finalize pass short
 }
 
+// The BatchNorm + ReLU backward: reduce (partials of nb = segk_bn_bwd_blocks rows into `part`; without it `part` holds nb rows
+// another kernel produced), finalize, apply (without it the consumer of dz forms it in registers: segk_stem3x3_wgrad_bn)
 template <typename T>
-static int bn_bwd_t(const void* dy, const void* z, void* dz, const float* scale, const float* shift, const float* mean,
-                    const float* rstd, long P, int C, int C_real, float* part, float* dgamma, float* dbeta,
-                    float* coef, hipStream_t st) {
-  using E = ET<T>;
-  int cvb, rows, gy;
-  lane_geometry(C, E::VEC, &cvb, &rows, &gy);
-  const int gx = segk_bn_bwd_blocks(P, C, sizeof(T) == 2 ? SEGK_DT_BF16 : SEGK_DT_F32);
-  const size_t lds = (size_t)rows * cvb * 2 * E::VEC * sizeof(float);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(gx, gy), dim3(256), lds, st, (const T*)dy, (const T*)z, scale, shift,
-                     mean, rstd, P, C, cvb, rows, part);
-  SEGK_CHECK_LAUNCH("bn_bwd_reduce");
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C / 32), dim3(1024), 0, st, part, gx, C, C_real, (double)P, dgamma,
-                     dbeta, coef);
-  SEGK_CHECK_LAUNCH("bn_bwd_finalize");
-  long ga = (P + rows - 1) / rows;
-  if (ga > 4096) ga = 4096;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((int)ga, gy), dim3(256), 0, st, (const T*)dy, (const T*)z, (T*)dz,
-                     scale, shift, mean, rstd, coef, P, C, cvb, rows);
-  SEGK_CHECK_LAUNCH("bn_bwd_apply");
-  return 0;
-}
-// finalize + apply from partials another kernel already produced (nb rows of [C][2])
-template <typename T>
-static int bn_bwd_from_part_t(const void* dy, const void* z, void* dz, const float* scale, const float* shift, const float* mean,
-                              const float* rstd, long P, int C, int C_real, const float* part, int nb, float* dgamma,
-                              float* dbeta, float* coef, hipStream_t st) {
-  using E = ET<T>;
-  int cvb, rows, gy;
-  lane_geometry(C, E::VEC, &cvb, &rows, &gy);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C / 32), dim3(1024), 0, st, part, nb, C, C_real, (double)P, dgamma,
-                     dbeta, coef);
-  SEGK_CHECK_LAUNCH("bn_bwd_finalize");
-  long ga = (P + rows - 1) / rows;
-  if (ga > 4096) ga = 4096;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((int)ga, gy), dim3(256), 0, st, (const T*)dy, (const T*)z, (T*)dz,
-                     scale, shift, mean, rstd, coef, P, C, cvb, rows);
-  SEGK_CHECK_LAUNCH("bn_bwd_apply");
+static int bn_bwd_launch(bool reduce, bool apply, const void* dy, const void* z, void* dz, const float* scale, const float* shift,
+                         const float* mean, const float* rstd, long P, int C, int C_real, float* part, int nb, float* dgamma,
+                         float* dbeta, float* coef, hipStream_t st) {
+  const LaneGeometry g = bn_lanes<T>(C);
+  if (reduce) {
+    nb = segk_bn_bwd_blocks(P, C, dtype_of<T>());
+    const size_t lds = (size_t)g.rows * g.cvb * 2 * ET<T>::VEC * sizeof(float);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(nb, g.gy), dim3(256), lds, st, (const T*)dy, (const T*)z, scale, shift, mean,
+                       rstd, P, C, g.cvb, g.rows, part);
+    SEGK_CHECK_LAUNCH("bn_bwd_reduce");
+  }
+  if (const int rc = segk_bn_bwd_finalize_launch(part, nb, C, C_real, P, dgamma, dbeta, coef, st)) return rc;
+  if (apply) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(apply_blocks(P, g.rows), g.gy), dim3(256), 0, st, (const T*)dy, (const T*)z,
+                       (T*)dz, scale, shift, mean, rstd, coef, P, C, g.cvb, g.rows);
+    SEGK_CHECK_LAUNCH("bn_bwd_apply");
+  }
   return 0;
 }
 extern "C" int segk_bn_relu_bwd_from_part(const void* dy, const void* z, void* dz, const float* scale, const float* shift,
                                           const float* mean, const float* rstd, long P, int C, int C_real, const float* part,
                                           int nb, float* dgamma, float* dbeta, float* coef, int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("bn_relu_bwd_from_part", dtype);
-  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(dy && z && dz && scale && shift && mean && rstd && part && dgamma && dbeta && coef && nb > 0,
                "bn_bwd_from_part: bad arguments");
   SEGK_REQUIRE(P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_bwd_from_part: bad shape");
-  return dtype == SEGK_DT_BF16
-             ? bn_bwd_from_part_t<bf16_t>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, nb, dgamma, dbeta, coef, st)
-             : bn_bwd_from_part_t<float>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, nb, dgamma, dbeta, coef, st);
+  return by_dtype(dtype, [&](auto Tc) {
+    return bn_bwd_launch<decltype(Tc)>(false, true, dy, z, dz, scale, shift, mean, rstd, P, C, C_real, const_cast<float*>(part), nb,
+                                       dgamma, dbeta, coef, (hipStream_t)s);
+  });
 }
 
-// reduce + finalize only (no apply pass: the consumer of dz forms it in registers, segk_stem3x3_wgrad_bn)
-template <typename T>
-static int bn_bwd_stats_t(const void* dy, const void* z, const float* scale, const float* shift, const float* mean,
-                          const float* rstd, long P, int C, int C_real, float* part, float* dgamma, float* dbeta, float* coef,
-                          hipStream_t st) {
-  using E = ET<T>;
-  int cvb, rows, gy;
-  lane_geometry(C, E::VEC, &cvb, &rows, &gy);
-  const int gx = segk_bn_bwd_blocks(P, C, sizeof(T) == 2 ? SEGK_DT_BF16 : SEGK_DT_F32);
-  const size_t lds = (size_t)rows * cvb * 2 * E::VEC * sizeof(float);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(gx, gy), dim3(256), lds, st, (const T*)dy, (const T*)z, scale, shift,
-                     mean, rstd, P, C, cvb, rows, part);
-  SEGK_CHECK_LAUNCH("bn_bwd_reduce");
-  return segk_bn_bwd_finalize_launch(part, gx, C, C_real, P, dgamma, dbeta, coef, st);
-}
 extern "C" int segk_bn_relu_bwd_stats(const void* dy, const void* z, const float* scale, const float* shift, const float* mean,
                                       const float* rstd, long P, int C, int C_real, float* part, float* dgamma, float* dbeta,
                                       float* coef, int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("bn_relu_bwd_stats", dtype);
-  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(dy && z && scale && shift && mean && rstd && part && dgamma && dbeta && coef, "bn_bwd_stats: null pointer");
   SEGK_REQUIRE(P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_bwd_stats: bad shape");
-  return dtype == SEGK_DT_BF16 ? bn_bwd_stats_t<bf16_t>(dy, z, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st)
-                               : bn_bwd_stats_t<float>(dy, z, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st);
+  return by_dtype(dtype, [&](auto Tc) {
+    return bn_bwd_launch<decltype(Tc)>(true, false, dy, z, nullptr, scale, shift, mean, rstd, P, C, C_real, part, 0, dgamma, dbeta,
+                                       coef, (hipStream_t)s);
+  });
 }
 
 extern "C" int segk_bn_relu_bwd(const void* dy, const void* z, void* dz, const float* scale, const float* shift,
                                 const float* mean, const float* rstd, long P, int C, int C_real, float* part, float* dgamma,
                                 float* dbeta, float* coef, int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("bn_relu_bwd", dtype);
-  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(dy && z && dz && scale && shift && mean && rstd && part && dgamma && dbeta && coef,
                "bn_bwd: null pointer");
   SEGK_REQUIRE(P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "bn_bwd: bad shape");
-  return dtype == SEGK_DT_BF16
-             ? bn_bwd_t<bf16_t>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st)
-             : bn_bwd_t<float>(dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, dgamma, dbeta, coef, st);
+  return by_dtype(dtype, [&](auto Tc) {
+    return bn_bwd_launch<decltype(Tc)>(true, true, dy, z, dz, scale, shift, mean, rstd, P, C, C_real, part, 0, dgamma, dbeta, coef,
+                                       (hipStream_t)s);
+  });
 }
 
 extern "C" int segk_maxpool2x2_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("maxpool2x2_fwd", dtype);
   hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && y && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 32 == 0, "maxpool_fwd: bad arguments");
-  const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
-  long total = (long)B * (H / 2) * (W / 2) * (C / vec);
-  SEGK_REQUIRE(total < (1L << 31), "maxpool_fwd: more than 2^31 windows x channel vectors");
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (dtype == SEGK_DT_BF16)
-    hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3((int)g), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
-  else
-    hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3((int)g), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C);
+  const int g = window_grid(B, H, W, C, dtype, false, 8192);
+  SEGK_REQUIRE(g > 0, "maxpool_fwd: more than 2^31 windows x channel vectors");
+  by_dtype(dtype, [&](auto Tc) {
+    using T = decltype(Tc);
+    hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, B, H, W, C);
+    return 0;
+  });
   SEGK_CHECK_LAUNCH("maxpool_fwd");
   return 0;
+}
+
+// the two forms of the pooling backward on a grid of g blocks (bn, part, z: the statistics form's operands)
+template <bool STAT>
+static void maxpool_bwd_launch(int g, const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate,
+                               const float* const* bn, float* part, const void* z, int dtype, hipStream_t st) {
+  by_dtype(dtype, [&](auto Tc) {
+    using T = decltype(Tc);
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T, STAT>), dim3(g), dim3(256), 0, st, (const T*)x, (const T*)dy, (T*)dx, B, H, W, C,
+                       accumulate, bn[0], bn[1], bn[2], bn[3], part, (const T*)z);
+    return 0;
+  });
 }
 
 extern "C" int segk_maxpool2x2_bwd(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate,
                                    int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("maxpool2x2_bwd", dtype);
-  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && dy && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 32 == 0, "maxpool_bwd: bad arguments");
-  const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
-  long total = (long)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / vec);
-  SEGK_REQUIRE(total < (1L << 31), "maxpool_bwd: more than 2^31 windows x channel vectors");
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (dtype == SEGK_DT_BF16)
-    hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, false>), dim3((int)g), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy,
-                       (bf16_t*)dx, B, H, W, C, accumulate, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((maxpool_bwd_kernel<float, false>), dim3((int)g), dim3(256), 0, st, (const float*)x, (const float*)dy,
-                       (float*)dx, B, H, W, C, accumulate, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const int g = window_grid(B, H, W, C, dtype, true, 8192);
+  SEGK_REQUIRE(g > 0, "maxpool_bwd: more than 2^31 windows x channel vectors");
+  const float* const none[4] = {nullptr, nullptr, nullptr, nullptr};
+  maxpool_bwd_launch<false>(g, x, dy, dx, B, H, W, C, accumulate, none, nullptr, nullptr, dtype, (hipStream_t)s);
   SEGK_CHECK_LAUNCH("maxpool_bwd");
   return 0;
 }
 
 // blocks (= partial rows) of the fused pooling-backward + BatchNorm-reduce kernel, or 0 when the shape is not served
 int segk_maxpool_bwd_stat_blocks(int B, int H, int W, int C, int dtype) {
-  const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
   if (B <= 0 || H < 2 || W < 2 || C <= 0 || C % 32 != 0) return 0;
-  const int cv = C / vec;
+  const int cv = C / (dtype == SEGK_DT_BF16 ? 8 : 4);
   if ((cv & (cv - 1)) != 0 || cv > 256) return 0;
-  long total = (long)B * ((H + 1) / 2) * ((W + 1) / 2) * cv;
-  if (total >= (1L << 31)) return 0;                  // the kernels index windows x channel vectors with 32 bits
-  long g = (total + 255) / 256;
-  return (int)(g > 1024 ? 1024 : g);
+  return window_grid(B, H, W, C, dtype, true, 1024);    // (0: the kernels index windows x channel vectors with 32 bits)
 }
 
 extern "C" int segk_maxpool2x2_bwd_bnstat(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int accumulate,
                                           const float* scale, const float* shift, const float* mean, const float* rstd,
                                           float* part, const void* z, int dtype, segk_stream_t s) {
   SEGK_REQUIRE_DTYPE("maxpool2x2_bwd_bnstat", dtype);
-  hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && dy && dx && scale && shift && mean && rstd && part, "maxpool_bwd_bnstat: null pointer");
   const int g = segk_maxpool_bwd_stat_blocks(B, H, W, C, dtype);
   SEGK_REQUIRE(g > 0, "maxpool_bwd_bnstat: shape not served (channel vectors must be a power of two)");
-  if (dtype == SEGK_DT_BF16)
-    hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, true>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy,
-                       (bf16_t*)dx, B, H, W, C, accumulate, scale, shift, mean, rstd, part, (const bf16_t*)z);
-  else
-    hipLaunchKernelGGL((maxpool_bwd_kernel<float, true>), dim3(g), dim3(256), 0, st, (const float*)x, (const float*)dy,
-                       (float*)dx, B, H, W, C, accumulate, scale, shift, mean, rstd, part, (const float*)z);
+  const float* const bn[4] = {scale, shift, mean, rstd};
+  maxpool_bwd_launch<true>(g, x, dy, dx, B, H, W, C, accumulate, bn, part, z, dtype, (hipStream_t)s);
   SEGK_CHECK_LAUNCH("maxpool_bwd_bnstat");
   return 0;
 }
@@ -957,15 +703,14 @@ extern "C" int segk_channel_sum(const void* x, long P, int C, int C_real, float*
   SEGK_REQUIRE_DTYPE("channel_sum", dtype);
   hipStream_t st = (hipStream_t)s;
   SEGK_REQUIRE(x && part && out && P > 0 && C > 0 && C % 32 == 0 && C_real > 0 && C_real <= C, "channel_sum: bad arguments");
-  const int vec = dtype == SEGK_DT_BF16 ? 8 : 4;
-  int cvb, rows, gy;
-  lane_geometry(C, vec, &cvb, &rows, &gy);
   const int gx = segk_bn_bwd_blocks(P, C, dtype);
-  const size_t lds = (size_t)rows * cvb * vec * sizeof(float);
-  if (dtype == SEGK_DT_BF16)
-    hipLaunchKernelGGL(channel_sum_kernel<bf16_t>, dim3(gx, gy), dim3(256), lds, st, (const bf16_t*)x, P, C, cvb, rows, part);
-  else
-    hipLaunchKernelGGL(channel_sum_kernel<float>, dim3(gx, gy), dim3(256), lds, st, (const float*)x, P, C, cvb, rows, part);
+  by_dtype(dtype, [&](auto Tc) {
+    using T = decltype(Tc);
+    const LaneGeometry g = bn_lanes<T>(C);
+    const size_t lds = (size_t)g.rows * g.cvb * ET<T>::VEC * sizeof(float);
+    hipLaunchKernelGGL(channel_sum_kernel<T>, dim3(gx, g.gy), dim3(256), lds, st, (const T*)x, P, C, g.cvb, g.rows, part);
+    return 0;
+  });
   SEGK_CHECK_LAUNCH("channel_sum");
   hipLaunchKernelGGL(channel_sum_finalize_kernel, dim3(C / 32), dim3(1024), 0, st, part, gx, C, C_real, out);
   SEGK_CHECK_LAUNCH("channel_sum_finalize");

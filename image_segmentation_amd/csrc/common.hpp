@@ -95,6 +95,13 @@ __device__ __forceinline__ float bn_relu_bwd_dz(float z, float d, float sc, floa
   const float xh = (z - mu) * rs;
   return sc * (g - c1 - xh * c2);
 }
+// xhat recovered from y = relu(z * scale + shift) where the ReLU is active: xhat = y * xa + xb = (y - shift) * rstd / scale -
+// mean * rstd (a channel with scale == 0 gets xa = 0).  Stated ONCE: the kernels that reduce sum(g * xhat) from the block output
+// (maxpool_bwd_kernel<STAT>, head_bwd_kernel) must agree bit for bit.
+__device__ __forceinline__ void xhat_from_y(float sc, float sh, float mu, float rs, float& xa, float& xb) {
+  xa = sc != 0.f ? rs / sc : 0.f;
+  xb = -sh * xa - mu * rs;
+}
 
 // Conv epilogue helper: the 16 fp32 results one lane holds of a 32x32 accumulator fragment (one output channel,
 // pixel rows (r & 3) + 8 (r >> 2) of the fragment) -> running per-channel (sum, sum of squares) for

@@ -1,6 +1,8 @@
 // Output head: the 1x1 Conv2d to a handful of classes, forward and backward, and the BatchNorm + ReLU backward apply pass of the
 // block in front of it without a stored gradient.  All HBM-bound; logits are fp32 NCHW exactly like the reference returns
-// them (unet/unet.py:91,105; clip/clipunet.py:181,187).  The losses and the metric on those logits: loss.hip.
+// them (unet/unet.py:91,105; clip/clipunet.py:181,187).  The losses and the metric on those logits: loss.hip.  The backward
+// kernels are channel-vector streaming kernels like bn_pool.hip's: lane map, row reduce, constants and walk of channel_lanes.hpp.
+#include "channel_lanes.hpp"
 #include "class_pixels.hpp"
 #include "segk_internal.h"
 
@@ -145,13 +147,13 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   // that BatchNorm's backward reductions sum(g), sum(g*xhat) (xhat recovered from y where the ReLU is active), like
   // maxpool_bwd_kernel<STAT> does for the Down blocks
   const bool stat = bnpart != nullptr;
-  float xa[HV], xb[HV], sg[HV], sgx[HV];
+  float xa[HV], xb[HV], sg[2 * HV];               // sg: sum g, then sum g * xhat
 #pragma unroll
-  for (int j = 0; j < HV; ++j) { xa[j] = 0.f; xb[j] = 0.f; sg[j] = 0.f; sgx[j] = 0.f; }
+  for (int j = 0; j < HV; ++j) { xa[j] = 0.f; xb[j] = 0.f; sg[j] = 0.f; sg[HV + j] = 0.f; }
   constexpr int RW = MAXC * HV + MAXC;
-  const int cx = threadIdx.x % cvb, ry = threadIdx.x / cvb;
-  const int cv = blockIdx.y * cvb + cx;
-  const bool active = cv < Cp / HV && ry < rows;
+  const ChannelLanes l = channel_lanes(cvb, rows, Cp / HV);
+  const int cx = l.cx, ry = l.ry, cv = l.cv;
+  const bool active = l.active();
   float wr[NC][HV], aw[NC][HV], ab[NC];
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
@@ -173,8 +175,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         zc[j] = sc; zh[j] = bn_shift[c];
         xa[j] = rs; xb[j] = -bn_mean[c] * rs;
       } else {
-        xa[j] = sc != 0.f ? rs / sc : 0.f;
-        xb[j] = -bn_shift[c] * xa[j] - bn_mean[c] * rs;
+        xhat_from_y(sc, bn_shift[c], bn_mean[c], rs, xa[j], xb[j]);
       }
     }
   }
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         for (int j = 0; j < HV; ++j) {
           const float gg = f[j] > 0.f ? o[j] : 0.f;
           sg[j] += gg;
-          sgx[j] = fmaf(gg, fmaf(ZIN ? z[j] : f[j], xa[j], xb[j]), sgx[j]);
+          sg[HV + j] = fmaf(gg, fmaf(ZIN ? z[j] : f[j], xa[j], xb[j]), sg[HV + j]);
         }
       }
     };
@@ -215,11 +216,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
       while (r >= HW) { r -= HW; ++b; }
     };
     // PIF pixels per iteration: all their loads are in flight before the first is used (the loop is latency-bound otherwise);
-    // every pixel stream carries its own (image, offset)
-#ifndef HEAD_BWD_PIF
-#define HEAD_BWD_PIF 2
-#endif
-    constexpr int PIF = HEAD_BWD_PIF;
+    // every pixel stream carries its own (image, offset), which is why this is not walk_pixels (channel_lanes.hpp): its load
+    // sees a pixel index, not the stream the pixel belongs to
+    constexpr int PIF = 2;
     const long step = (long)gridDim.x * rows;
     long p = (long)blockIdx.x * rows + ry;
     long bS[PIF], rS[PIF];
@@ -277,24 +276,11 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   }
   if (stat) {
     __syncthreads();
-    if (ry < rows) {
-      float* q = red + ((size_t)ry * cvb + cx) * RW;
+    reduce_lane_rows(red, l, cvb, rows, RW, sg, [&](const float (&tot)[2 * HV]) {
+      float2* dst = (float2*)bnpart + (size_t)blockIdx.x * Cp + cv * HV;
 #pragma unroll
-      for (int j = 0; j < HV; ++j) { q[j] = sg[j]; q[HV + j] = sgx[j]; }
-    }
-    __syncthreads();
-    if (ry == 0 && cv < Cp / HV) {
-#pragma unroll
-      for (int j = 0; j < HV; ++j) {
-        float a = 0.f, b2 = 0.f;
-        for (int r2 = 0; r2 < rows; ++r2) {   // fixed order
-          const float* q = red + ((size_t)r2 * cvb + cx) * RW;
-          a += q[j];
-          b2 += q[HV + j];
-        }
-        ((float2*)bnpart)[(size_t)blockIdx.x * Cp + cv * HV + j] = make_float2(a, b2);
-      }
-    }
+      for (int j = 0; j < HV; ++j) dst[j] = make_float2(tot[j], tot[HV + j]);
+    });
   }
 }
 
@@ -321,9 +307,7 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
 // A thread owns one channel vector and walks pixels; the vector is head_bwd_kernel's (bf16: four channels, 8 bytes), not the
 // 16 bytes of bn_bwd_apply_kernel: beside six BatchNorm constants per channel the NC weights per channel make 8 channels
 // 138 registers (3 waves per SIMD; 268 MB took 173 us, no faster than the stored apply pass), 4 channels about 80.
-// One pixel in flight per thread: a two-pixel form measured 256 against 253 us for statistics + apply at B = 32, 64 ch x 256^2
-// (same box, 2 us spread; profiles/end_fusion_kbench.txt) -- like bn_bwd_apply_kernel, a pass that writes as much as it reads
-// gains nothing from more loads in flight.
+// One pixel in flight per thread (APPLY_FLIGHT, channel_lanes.hpp).
 template <typename T, int NC>
 __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const float* __restrict__ dlog, const T* __restrict__ z,
                                                                 const float* __restrict__ w, T* __restrict__ dz,
@@ -333,21 +317,34 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const float* __r
                                                                 int ncls, int cvb, int rows) {
   constexpr int V = HeadVec<T>::HV;
   using Raw = typename HeadVec<T>::Raw;
-  const int cx = threadIdx.x % cvb, ry = threadIdx.x / cvb;
-  const int cv = blockIdx.y * cvb + cx;
-  if (cv >= Cp / V || ry >= rows) return;
-  float sc[V], sh[V], mu[V], rs[V], c1[V], c2[V], wr[NC][V];
+  const ChannelLanes l = channel_lanes(cvb, rows, Cp / V);
+  if (!l.active()) return;
+  const int cv = l.cv;
+  const BnConsts<V, true> bn(scale, shift, mean, rstd, cv * V, coef);
+  float wr[NC][V];
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     const int c = cv * V + j;
-    sc[j] = scale[c]; sh[j] = shift[c]; mu[j] = mean[c]; rs[j] = rstd[c];
-    c1[j] = coef[2 * c]; c2[j] = coef[2 * c + 1];
 #pragma unroll
     for (int k = 0; k < NC; ++k) wr[k][j] = (k < ncls && c < C) ? w[(size_t)k * C + c] : 0.f;
   }
-  auto pixel = [&](long p, const float (&dl)[NC], const Raw raw) {
+  struct Pixel { Raw z; float dl[NC]; };
+  // the (image, offset) of the thread's pixel is carried along instead of divided out per pixel, as in head_bwd_kernel
+  const long step = (long)gridDim.x * rows, first = (long)blockIdx.x * rows + l.ry;
+  long b = 0, r = 0;
+  if (first < P) split_hw(first, HW, b, r);
+  auto load = [&](long p) {
+    Pixel v;
+    v.z = *(const Raw*)(z + (size_t)p * Cp + cv * V);
+    load_classes<NC>(dlog, b, r, ncls, HW, v.dl, 0.f);      // head_bwd_kernel's load
+    r += step;
+    while (r >= HW) { r -= HW; ++b; }
+    return v;
+  };
+  auto pixel = [&](long p, const Pixel& v) {
+    const float (&dl)[NC] = v.dl;
     float fz[V], o[V];
-    HeadVec<T>::unpack(raw, fz);
+    HeadVec<T>::unpack(v.z, fz);
 #pragma unroll
     for (int j = 0; j < V; ++j) o[j] = 0.f;
 #pragma unroll
@@ -356,34 +353,21 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const float* __r
       for (int j = 0; j < V; ++j) o[j] = fmaf(dl[k], wr[k][j], o[j]);
     HeadVec<T>::unpack(HeadVec<T>::pack(o), o);      // the value the stored dy would have held
 #pragma unroll
-    for (int j = 0; j < V; ++j) o[j] = bn_relu_bwd_dz(fz[j], o[j], sc[j], sh[j], mu[j], rs[j], c1[j], c2[j]);
+    for (int j = 0; j < V; ++j)
+      o[j] = bn_relu_bwd_dz(fz[j], o[j], bn.sc[j], bn.sh[j], bn.mu[j], bn.rs[j], bn.c1[j], bn.c2[j]);
     *(Raw*)(dz + (size_t)p * Cp + cv * V) = HeadVec<T>::pack(o);
   };
-  // the (image, offset) of the thread's pixel is carried along instead of divided out per pixel, as in head_bwd_kernel
-  const long step = (long)gridDim.x * rows;
-  long p = (long)blockIdx.x * rows + ry, b = 0, r = 0;
-  if (p < P) split_hw(p, HW, b, r);
-  for (; p < P; p += step) {
-    const Raw raw = *(const Raw*)(z + (size_t)p * Cp + cv * V);
-    float dl[NC];
-    load_classes<NC>(dlog, b, r, ncls, HW, dl, 0.f);      // head_bwd_kernel's load
-    pixel(p, dl, raw);
-    r += step;
-    while (r >= HW) { r -= HW; ++b; }
-  }
+  walk_pixels<APPLY_FLIGHT>(first, step, P, load, pixel);
 }
 }  // namespace
 
 template <typename T> static size_t head_lds() { return (size_t)HT * (HCH * ET<T>::ES + 16); }
 
 // ------------------------------------------------------------------------------------------------
-#ifndef SEGK_HEAD_BLOCKS_CAP
-#define SEGK_HEAD_BLOCKS_CAP 1024
-#endif
 int segk_head_blocks(long P) {
   if (P <= 0) return 0;
-  long g = (P + 31) / 32;
-  return (int)(g > SEGK_HEAD_BLOCKS_CAP ? SEGK_HEAD_BLOCKS_CAP : g);
+  const long g = (P + 31) / 32;
+  return (int)(g > 1024 ? 1024 : g);
 }
 int segk_head_part_floats(long P, int Cp) {
   if (P <= 0 || Cp <= 0) return 0;
@@ -410,7 +394,7 @@ static int head_fwd(const void* y, const float* w, const float* bias, float* log
                                                    bias, logits, P, HW, Cp, C, ncls, zsc, zsh);
   };
   auto by_nc = [&](auto Tc) { return dispatch_head_nc(ncls, [&](auto NCc) { return launch(Tc, NCc); }); };
-  return dtype == SEGK_DT_BF16 ? by_nc(bf16_t{}) : by_nc(float{});
+  return by_dtype(dtype, by_nc);
 }
 extern "C" int segk_head_fwd(const void* y, const float* w, const float* bias, float* logits, int B, int H, int W, int Cp, int C,
                              int ncls, int dtype, segk_stream_t s) {
@@ -428,17 +412,15 @@ static int head_bwd_t(const float* dlog, const void* y, const float* w, void* dy
                       long P, long HW, int Cp, int C, int ncls, const float* const* bn, float* bnpart, bool zin, bool store,
                       hipStream_t st) {
   constexpr int HV = HeadVec<T>::HV;
-  const int cvec = Cp / HV;
-  const int cvb = cvec < 64 ? cvec : 64;
-  const int rows = 256 / cvb, gy = cdiv(cvec, cvb);
+  const LaneGeometry g = lane_geometry(Cp / HV, HEAD_LANE_CAP);
   const int nb = segk_head_blocks(P);
-  const size_t lds = (size_t)rows * cvb * (MAXC * HV + MAXC) * sizeof(float);
+  const size_t lds = (size_t)g.rows * g.cvb * (MAXC * HV + MAXC) * sizeof(float);
   // gy > 1 (more than 64 channel vectors: above 256 channels): blockIdx.y slices the channels; every slice walks the
   // block's pixels and writes its own columns of the partial rows (tests/test_gpu_kernels.py at 288 and 512 channels)
   auto launch_z = [&](auto NCc, auto ZINc, auto STOREc) {
     constexpr int NC = decltype(NCc)::value;
     return segk_launch_lds<head_bwd_kernel<T, NC, decltype(ZINc)::value, decltype(STOREc)::value>>(
-        "head_bwd", 96 * 1024, dim3(nb, gy), dim3(256), lds, st, dlog, (const T*)y, w, (T*)dy, part, P, HW, Cp, C, ncls, cvb, rows,
+        "head_bwd", 96 * 1024, dim3(nb, g.gy), dim3(256), lds, st, dlog, (const T*)y, w, (T*)dy, part, P, HW, Cp, C, ncls, g.cvb, g.rows,
         bn ? bn[0] : nullptr, bn ? bn[1] : nullptr, bn ? bn[2] : nullptr, bn ? bn[3] : nullptr, bnpart);
   };
   auto launch = [&](auto NCc) {      // the form without the store exists on the pre-activation input only
@@ -466,8 +448,9 @@ static int head_bwd(const float* dlog, const void* y, const float* w, void* dy, 
   SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
   const float* bn[4] = {bn_scale, bn_shift, bn_mean, bn_rstd};
   const float* const* bnp = (bnpart || zin) ? bn : nullptr;
-  return dtype == SEGK_DT_BF16 ? head_bwd_t<bf16_t>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, store != 0, st)
-                               : head_bwd_t<float>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, store != 0, st);
+  return by_dtype(dtype, [&](auto Tc) {
+    return head_bwd_t<decltype(Tc)>(dlog, y, w, dy, part, dw, db, P, HW, Cp, C, ncls, bnp, bnpart, zin != 0, store != 0, st);
+  });
 }
 extern "C" int segk_head_bwd(const float* dlogits, const void* y, const float* w, void* dy, float* part, float* dw, float* db,
                              int B, int H, int W, int Cp, int C, int ncls, int dtype, segk_stream_t s) {
@@ -504,14 +487,10 @@ extern "C" int segk_head_bwd_bn_stats(const float* dlogits, const void* z, const
 template <typename T>
 static int head_bn_bwd_apply_t(const float* dlog, const void* z, const float* w, void* dz, const float* const* bn,
                                const float* coef, long P, long HW, int Cp, int C, int ncls, hipStream_t st) {
-  const int cvec = Cp / HeadVec<T>::HV;       // the block geometry of head_bwd_t
-  const int cvb = cvec < 64 ? cvec : 64;
-  const int rows = 256 / cvb, gy = cdiv(cvec, cvb);
-  long ga = (P + rows - 1) / rows;
-  if (ga > 4096) ga = 4096;
+  const LaneGeometry g = lane_geometry(Cp / HeadVec<T>::HV, HEAD_LANE_CAP);       // head_bwd_t's
   dispatch_head_nc(ncls, [&](auto NCc) {
-    hipLaunchKernelGGL((head_bn_bwd_apply_kernel<T, decltype(NCc)::value>), dim3((int)ga, gy), dim3(256), 0, st, dlog, (const T*)z, w,
-                       (T*)dz, bn[0], bn[1], bn[2], bn[3], coef, P, HW, Cp, C, ncls, cvb, rows);
+    hipLaunchKernelGGL((head_bn_bwd_apply_kernel<T, decltype(NCc)::value>), dim3(apply_blocks(P, g.rows), g.gy), dim3(256), 0, st, dlog,
+                       (const T*)z, w, (T*)dz, bn[0], bn[1], bn[2], bn[3], coef, P, HW, Cp, C, ncls, g.cvb, g.rows);
   });
   SEGK_CHECK_LAUNCH("head_bn_bwd_apply");
   return 0;
@@ -530,6 +509,5 @@ extern "C" int segk_head_bn_bwd_apply(const float* dlogits, const void* z, const
   SEGK_REQUIRE(P < (1L << 31), "head / loss kernels index pixels with 32 bits: %ld pixels", P);
   if (const int rc = segk_bn_bwd_finalize_launch(bnpart, nb, Cp, C, P, dgamma, dbeta, coef, st)) return rc;
   const float* bn[4] = {scale, shift, mean, rstd};
-  return dtype == SEGK_DT_BF16 ? head_bn_bwd_apply_t<bf16_t>(dlogits, z, w, dz, bn, coef, P, HW, Cp, C, ncls, st)
-                               : head_bn_bwd_apply_t<float>(dlogits, z, w, dz, bn, coef, P, HW, Cp, C, ncls, st);
+  return by_dtype(dtype, [&](auto Tc) { return head_bn_bwd_apply_t<decltype(Tc)>(dlogits, z, w, dz, bn, coef, P, HW, Cp, C, ncls, st); });
 }

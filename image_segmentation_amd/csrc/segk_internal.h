@@ -26,6 +26,10 @@ struct ConvArgs {
 };
 int segk_conv_igemm_launch(const ConvArgs& a, int geo, int dtype, hipStream_t st);
 
+// f(bf16_t{}) or f(float{}) for a dtype the entry has checked (SEGK_REQUIRE_DTYPE)
+template <typename F>
+inline auto by_dtype(int dtype, F&& f) { return dtype == SEGK_DT_BF16 ? f(bf16_t{}) : f(float{}); }
+
 // per-device launch state (hipFuncSetAttribute flags, CU counts) is indexed by the current device
 #define SEGK_MAX_DEVICES 64
 int segk_device_index();                  // hipGetDevice(), clamped to [0, SEGK_MAX_DEVICES)

@@ -9,7 +9,7 @@ U24 = 2.0 ** -24          # unit roundoff of fp32
 
 
 def lane_geometry(Cp, dtype):
-    """lane_geometry() of bn_pool.hip: (channel vectors per block, pixel rows per block, channel blocks)."""
+    """lane_geometry(cvec, 128) of csrc/channel_lanes.hpp as bn_pool.hip calls it: (channel vectors per block, pixel rows per block, channel blocks)."""
     vec = 8 if dtype == torch.bfloat16 else 4
     cvec = Cp // vec
     cvb = min(cvec, 128)

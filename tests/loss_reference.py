@@ -89,7 +89,7 @@ def head_blocks(P):
 
 
 def head_lane_geometry(Cp):
-    """lane_geometry of head_bwd_t: (channel vectors per block, pixel rows per block, channel slices); four channels per
+    """lane_geometry(cvec, 64) of csrc/channel_lanes.hpp as head.hip calls it: (channel vectors per block, pixel rows per block, channel slices); four channels per
     thread in both dtypes."""
     cvec = Cp // 4
     cvb = min(cvec, 64)

@@ -188,8 +188,9 @@ def pool_items(c, kernel):
 
 
 def pool_grid(c, kernel):
-    """blocks of 256 threads: segk_maxpool2x2_fwd / _bwd / segk_bn_relu_apply_pool (cap 8192), kernel "stat":
-    segk_maxpool_bwd_stat_blocks (cap 1024; 0 where the channel vectors are no power of two or more than 256)"""
+    """blocks of 256 threads, window_grid() of csrc/channel_lanes.hpp: segk_maxpool2x2_fwd / _bwd / segk_bn_relu_apply_pool
+    (cap 8192), kernel "stat": segk_maxpool_bwd_stat_blocks (cap 1024; 0 where the channel vectors are no power of two or more
+    than 256)"""
     if c.B <= 0 or c.H < 2 or c.W < 2 or c.Cp <= 0 or c.Cp % 32 != 0:
         return 0
     total = pool_items(c, kernel)

@@ -130,7 +130,9 @@ def convt():
 
 
 def bn():
-    """BatchNorm+ReLU backward (reduce + finalize + apply) and forward apply at the U-Net activation shapes."""
+    """BatchNorm+ReLU backward (reduce + finalize + apply) at the U-Net activation shapes through ops.py, then every entry of
+    bn_pool.hip (finalize, apply, apply + pool, the three backward forms, pooling forward / backward / backward with the
+    BatchNorm reductions, channel sum) through the C ABI at 64 ch x 256^2, 128 x 128^2 and 256 x 64^2, B = 32."""
     dt = torch.bfloat16
     B = 32
     for C, hw in [(64, 256), (128, 128), (256, 64), (512, 32), (1024, 16)]:
@@ -143,6 +145,46 @@ def bn():
         t = timeit(lambda: ops.bn_relu_bwd(dy.data_ptr(), z.data_ptr(), dz.data_ptr(), sc, sh, mu, rs, P, C, dt, "cuda"), 20)
         by = 5.0 * P * C * 2
         print(f"bn_bwd C={C:5d}@{hw:3d}  {t:8.1f} us  {by/t/1e3:7.1f} GB/s (5 passes)")
+    # every entry of bn_pool.hip through the C ABI at the workload's shapes: median [min..max] of five repeats of 20 launches
+    st = ops._stream()
+    for C, hw in [(64, 256), (128, 128), (256, 64)]:
+        P, ho = B * hw * hw, hw // 2
+        z = torch.randn((P, C), device="cuda").to(dt); dy = torch.randn((P, C), device="cuda").to(dt)
+        y = torch.relu(z); dz = torch.empty_like(z); pooled = torch.empty((B * ho * ho, C), dtype=dt, device="cuda")
+        dp = torch.randn((B * ho * ho, C), device="cuda").to(dt)
+        sc = torch.rand(C, device="cuda") + 0.5; sh = torch.rand(C, device="cuda") - 0.5
+        mu = torch.zeros(C, device="cuda"); rs = torch.ones(C, device="cuda")
+        bnv = (sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), rs.data_ptr())
+        ga = torch.ones(C, device="cuda"); be = torch.zeros(C, device="cuda"); rm = torch.zeros(C, device="cuda"); rv = torch.ones(C, device="cuda")
+        o4 = [torch.empty(C, device="cuda") for _ in range(4)]
+        coef = torch.empty(2 * C, device="cuda"); dga = torch.empty(C, device="cuda"); dbe = torch.empty(C, device="cuda")
+        nb = _lib.query("segk_bn_bwd_blocks", P, C, 1)
+        part = torch.rand(max(nb, 1024) * C * 2, device="cuda")
+        MT = _lib.query("segk_conv_tiles", B, hw, hw, C, C, 1)
+        stats = torch.rand(_lib.query("segk_bn_stats_floats", MT, C), device="cuda")
+        nbp = _lib.query("segk_maxpool_bwd_stat_blocks", B, hw, hw, C, 1)
+        ppart = torch.empty(nbp * C * 2, device="cuda"); csum = torch.empty(C, device="cuda")
+        entries = [
+            ("bn_finalize", lambda: _lib.call("segk_bn_finalize", stats.data_ptr(), MT, C, C, float(P), None, ga.data_ptr(), be.data_ptr(),
+                                              rm.data_ptr(), rv.data_ptr(), 0.1, 1e-5, 1, *[o.data_ptr() for o in o4], st)),
+            ("bn_relu_apply", lambda: _lib.call("segk_bn_relu_apply", z.data_ptr(), dz.data_ptr(), bnv[0], bnv[1], P, C, 1, st)),
+            ("bn_relu_apply_pool", lambda: _lib.call("segk_bn_relu_apply_pool", z.data_ptr(), dz.data_ptr(), pooled.data_ptr(), bnv[0],
+                                                     bnv[1], B, hw, hw, C, 1, st)),
+            ("bn_relu_bwd", lambda: _lib.call("segk_bn_relu_bwd", dy.data_ptr(), z.data_ptr(), dz.data_ptr(), *bnv, P, C, C, part.data_ptr(),
+                                              dga.data_ptr(), dbe.data_ptr(), coef.data_ptr(), 1, st)),
+            ("bn_relu_bwd_stats", lambda: _lib.call("segk_bn_relu_bwd_stats", dy.data_ptr(), z.data_ptr(), *bnv, P, C, C, part.data_ptr(),
+                                                    dga.data_ptr(), dbe.data_ptr(), coef.data_ptr(), 1, st)),
+            ("bn_relu_bwd_from_part", lambda: _lib.call("segk_bn_relu_bwd_from_part", dy.data_ptr(), z.data_ptr(), dz.data_ptr(), *bnv, P,
+                                                        C, C, part.data_ptr(), 1024, dga.data_ptr(), dbe.data_ptr(), coef.data_ptr(), 1, st)),
+            ("maxpool2x2_fwd", lambda: _lib.call("segk_maxpool2x2_fwd", y.data_ptr(), pooled.data_ptr(), B, hw, hw, C, 1, st)),
+            ("maxpool2x2_bwd", lambda: _lib.call("segk_maxpool2x2_bwd", y.data_ptr(), dp.data_ptr(), dz.data_ptr(), B, hw, hw, C, 0, 1, st)),
+            ("maxpool2x2_bwd_bnstat", lambda: _lib.call("segk_maxpool2x2_bwd_bnstat", y.data_ptr(), dp.data_ptr(), dz.data_ptr(), B, hw, hw,
+                                                        C, 0, *bnv, ppart.data_ptr(), None, 1, st)),
+            ("channel_sum", lambda: _lib.call("segk_channel_sum", dy.data_ptr(), P, C, C, part.data_ptr(), csum.data_ptr(), 1, st)),
+        ]
+        for name, fn in entries:
+            ts = sorted(timeit(fn, 20) for _ in range(5))
+            print(f"{name:22s} C={C:4d}@{hw:3d}  {ts[2]:8.1f} us  [{ts[0]:.1f}..{ts[-1]:.1f}]", flush=True)
 
 
 def loss():
