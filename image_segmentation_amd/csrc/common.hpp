@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -11,6 +12,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // native vector: stays in registers (SSA)
 
 #define SEGK_DT_F32 0
 #define SEGK_DT_BF16 1
@@ -129,6 +131,26 @@ __device__ __forceinline__ void stage_frag(const float (&v)[16], char* obase, in
   }
   s1 += p1.x + p1.y;
   s2 += p2.x + p2.y;
+}
+
+// compile-time loop: f(std::integral_constant<int, I>) for I = 0 .. N-1 (inline-asm immediates need constants)
+template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
+}
+template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
+  const int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
+  return v + __int_as_float(x);
+}
+// sum over the 16 lanes of a DPP row, result in every lane: xor 1, xor 2 (quad permutes), half mirror, mirror -- a fixed tree
+__device__ __forceinline__ float row16_sum(float v) {
+  v = dpp_add<0xB1>(v);
+  v = dpp_add<0x4E>(v);
+  v = dpp_add<0x141>(v);
+  v = dpp_add<0x140>(v);
+  return v;
 }
 
 // XCD-aware block remap: blocks b and b+8 share an XCD (observed round-robin dispatch; speed only).

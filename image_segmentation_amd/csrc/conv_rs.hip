@@ -23,28 +23,13 @@
 // One s_barrier per tile.  PRO (second conv of a DoubleConv block): the BatchNorm+ReLU of the previous layer is applied
 // in LDS by the wave that fetched the piece (after its own vmcnt wait), which also writes the transformed activation
 // to `act_out` for the weight-gradient pass.
-#include <type_traits>
-#include "common.hpp"
-#include "segk_internal.h"
+// The walk, the slot map with its inverse, the zero page and the launch set-up are conv_tile.hpp's.
+#include "conv_tile.hpp"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_vp;
-typedef const __attribute__((address_space(1))) void* glb_vp;
-
-// out-of-image pixels are fetched from here (a device array of the code object: nothing is allocated)
-__device__ __attribute__((aligned(256))) unsigned char g_rs_zero_page[256];
-
 constexpr int RS_PW = 34, RS_NPIX = 340, RS_NBLK = 22, RS_CHB = RS_NBLK * 1024;
-
-// compile-time loop: f(std::integral_constant<int, I>) for I = 0 .. N-1 (inline-asm immediates need constants)
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
+struct RsTile { static constexpr int TW = 32, TH = 8; };
 
 // LDS reads of DMA-written data go through inline asm: hipcc orders every LDS load it can see behind ALL pending
 // global_load_lds (s_waitcnt vmcnt(0)-like), which would drain the tiles in flight once per tile.  The statement's
@@ -61,19 +46,6 @@ template <int N> __device__ __forceinline__ void lds_wait() {
 template <int OFF> __device__ __forceinline__ void lds_wr128(int addr, const uint4& v) {
   const u32x4 t = {v.x, v.y, v.z, v.w};
   asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(t), "n"(OFF) : "memory");
-}
-
-template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
-  const int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
-  return v + __int_as_float(x);
-}
-// sum over the 16 lanes of a DPP row, result in every lane: xor 1, xor 2 (quad permutes), half mirror, mirror
-__device__ __forceinline__ float row16_sum(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  v = dpp_add<0x140>(v);
-  return v;
 }
 
 // Diagnostic build only (-DSEGK_RS_STAMPS, tools/stamp_build.sh): per-wave cycle sums of the loop's phases, written over
@@ -128,15 +100,12 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
   const int H = a.H, W = a.W;
 
   // ---- work: the channel tile is fixed per workgroup, pixel tiles are walked with stride GW inside the XCD's range
-  const int NT = a.Ntot >> 6;
-  const int tpi = a.tiles_x * a.tiles_y, MT = a.B * tpi;
-  const int xcd = blockIdx.x & 7, wgi = blockIdx.x >> 3, GWX = gridDim.x >> 3;
-  const int nt = wgi % NT, slot = wgi / NT, GW = GWX / NT;
-  const int mpx = (MT + 7) >> 3;
-  int mt = xcd * mpx + slot;
-  const int mt_end = min(MT, (xcd + 1) * mpx);
+  const int tpi = a.tiles_x * a.tiles_y;
+  const TileWalk tw = tile_walk(a.B * tpi, a.Ntot >> 6);
+  const int nt = tw.nt, GW = tw.GW, mt_end = tw.mt_end;
+  int mt = tw.mt;
   const int n0 = nt * 64;
-  const int srow = (xcd * GW + slot) * 4 + s;         // this wave's row of the statistics partials
+  const int srow = (tw.xcd * GW + tw.slot) * 4 + s;   // this wave's row of the statistics partials
   float2* const stat_dst = a.stats ? (float2*)a.stats + (size_t)srow * a.Ntot + n0 + 32 * jh + 8 * g : nullptr;
   if (mt >= mt_end) {                                 // nothing to do: the partial rows still have to exist
     if (stat_dst && col == 0) {
@@ -145,13 +114,7 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
     }
     return;
   }
-  auto decode = [&](int m, int& b, int& y0, int& x0) {
-    b = m / tpi;
-    const int trem = m - b * tpi;
-    const int tyi = trem / a.tiles_x;
-    y0 = tyi * 8;
-    x0 = (trem - tyi * a.tiles_x) * 32;
-  };
+  auto decode = [&](int m, int& b, int& y0, int& x0) { decode_tile<32, 8>(a, tpi, m, b, y0, x0); };
 
   // ---- resident weights: A operand (16 channels x 32 k) of the wave's two channel blocks, every tap and chunk.
   // Row m = 4 g' + i of block cb is channel 8 g' + 4 cb + i, so that accumulator row 4 g + i (held by lane row g) of
@@ -177,15 +140,11 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
     }
   }
 
-  // ---- DMA: lane -> (pixel pl of the 16-pixel block, piece q) by inverting the slot map (file header).  Piece i of the
+  // ---- DMA: lane -> (pixel pl of the 16-pixel block, piece q) by inverting the slot map (dma_slot_lane).  Piece i of the
   // wave is block bi = wave + 8 i of the tile (chunk bi / 22, pixels 16 (bi % 22) ..).  poff[i]: byte offset of the
   // lane's 16 bytes from the chunk's tile origin (patch pixel (0,0) = image pixel (y0-1, x0-1)); pixels past the patch
   // (the tail of the last block) re-read the last patch pixel into LDS slots nobody reads.
-  auto dma_lane = [](int l, int& dq, int& dpl) {
-    const int drow = l >> 4, dslot = l & 15;
-    dq = ((drow & 1) << 1) | (dslot & 1);
-    dpl = ((drow >> 1) << 3) | ((3 * (((dslot - (dslot & 1) - 2 * (drow & 1)) & 15) >> 1)) & 7);
-  };
+  auto dma_lane = [](int l, int& dq, int& dpl) { dma_slot_lane(l, dq, dpl); };
   int CAs = a.CA, CBs = a.CB;                        // pinned in scalar registers (hipcc otherwise re-loads them from
   asm volatile("" : "+s"(CAs), "+s"(CBs));           // the kernel-argument segment for every DMA piece)
   const int nchA = CAs >> 5;
@@ -240,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
         lane_pixel(bi, dpl, py, px);
         const int gy = y0 + py - 1, gx = x0 + px - 1;
         const bool ok = (py < 10) & (gy >= 0) & (gy < H) & (gx >= 0) & (gx < W);
-        const char* src = ok ? cb + po : (const char*)g_rs_zero_page + (fl & 15) * 16;
+        const char* src = ok ? cb + po : (const char*)g_conv_zero_page + (fl & 15) * 16;
         __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)dst, 16, 0, 0);
       }
     }
@@ -312,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void conv_rs_kernel(const ConvArgs a) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int u = k + col + (pwv & 7);
-    abuf[k] = ((u >> 3) + (pwv >> 3)) * 512 + (g >> 1) * 256 + ((6 * u + g) & 15) * 16;
+    abuf[k] = (pwv >> 3) * 512 + dma_slot(u, g);
   }
 
   // ---- output: lane (col, g) stores the 8 channels 8 g .. 8 g + 7 of its half for pixel (2 s + rr, 16 xh + col) of
@@ -507,18 +466,15 @@ int launch_rs(ConvArgs a, const ConvPlan& p, hipStream_t st) {
   constexpr size_t lds = 3 * (size_t)NCH * RS_CHB + NCH * 256;
   static_assert(lds <= 160 * 1024, "conv_rs: LDS exceeds 160 KiB");
   SEGK_REQUIRE(p.bm == 256 && p.twl == 5, "conv_rs: written for 8 x 32 tiles, the plan says %d pixels (twl %d)", p.bm, p.twl);
-  a.tiles_x = cdiv(a.W, 32);
-  a.tiles_y = cdiv(a.H, 8);
   int gw, GW;
-  segk_conv_rs_grid(a.B * a.tiles_x * a.tiles_y, a.Ntot / 64, &gw, &GW);
-  a.persistent = 1;
+  segk_conv_rs_grid(conv_set_tiles<RsTile>(a, a.twl), a.Ntot / 64, &gw, &GW);
   return segk_launch_lds<conv_rs_kernel<NCH, PRO>>("conv_rs", 160 * 1024, dim3(8 * gw), dim3(512), lds, st, a);
 }
 
 }  // namespace
 
 // workgroups per XCD (gw, a multiple of the NT channel tiles) and per channel tile (GW) for MT pixel tiles; one workgroup per
-// CU at most.  Shared with the weight-stationary kernel (conv_igemm.hip: launch_ws)
+// CU at most.  Shared with the weight-stationary kernel (conv_ws.hip: launch_ws)
 void segk_conv_rs_grid(int MT, int NT, int* gw_out, int* GW_out) {
   int gw = segk_num_cus() / 8;
   gw -= gw % NT;

@@ -17,7 +17,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // KS = K / 32 k-steps, NBW = 16-channel blocks per wave (KS * NBW = 32 fragments = 128 weight registers).
 // MODE 0: forward, K = Cin, N = 4 Cout (tap-major), x [B,H,W,Cin] -> out [B,2H,2W,Cout] pixel-shuffled (+ bias4).

@@ -8,7 +8,7 @@
 // against the packed weights [K/32][N][32] of segk_pack_conv_weight / segk_pack_convt_weight.
 //
 // Round 4 form: LDS-DMA producers, 16x16x32 consumers and results straight from the accumulators -- the form the 3x3
-// producer/consumer convolution took (conv_igemm.hip, DMA form), for the same reasons, plus some specific to a plain GEMM.
+// producer/consumer convolution took (conv_pipe.hip, DMA form), for the same reasons, plus some specific to a plain GEMM.
 // The generic streaming kernel (conv_igemm.hip) joins all waves at a barrier every 32 K-elements (8 MFMAs per wave); with
 // K = 768..3072 that leaves the matrix pipe idle most of the time.  Here a 512-thread workgroup owns a BM x 128 output tile;
 // 4 CONSUMER waves (one per SIMD) issue only ds_read_b128 + MFMA, and 4 PRODUCER waves move the K stream global -> LDS by
@@ -25,15 +25,11 @@
 // One barrier per chunk.  MFMA orientation: channels x rows (A = weights with the rows a lane reads
 // permuted so that accumulator rows 4 lq + j of a block pair are 8 consecutive output channels): 16-byte stores from
 // registers, bias / quick_gelu on the way, no epilogue tile, no boundary barriers -- the ring runs through unit boundaries.
-#include <type_traits>
-#include "common.hpp"
-#include "segk_internal.h"
+#include "conv_tile.hpp"
 
 namespace {
 
 constexpr int G_BN = 128;                 // channel tile of every work unit
-typedef __attribute__((address_space(3))) void* g_lds_vp;
-typedef const __attribute__((address_space(1))) void* g_glb_vp;
 typedef __attribute__((ext_vector_type(4))) float g_f32x4;
 
 template <int MODE, int BM>   // 0 plain, 1 pixel-shuffle store, 2 un-shuffle gather
@@ -72,7 +68,7 @@ __global__ __launch_bounds__(512, 2) void gemm_dma_kernel(const GemmArgs g) {
     // ================================================ PRODUCERS ================================================
     const int pw = wave - 4;
     const int lrow = lane >> 2;
-    const unsigned lpc = (unsigned)(((lane & 3) ^ ((0x1230 >> (4 * ((lane >> 4) & 3))) & 3)) << 4);   // global piece of the lane's LDS slot
+    const unsigned lpc = (unsigned)(((lane & 3) ^ wswz(lane >> 2)) << 4);   // global piece of the lane's LDS slot
     const unsigned wl_off = (unsigned)(lrow * 64) + lpc;
     unsigned arow[NA];                           // byte offset of the lane's row of each A piece (unit of the fetch cursor)
     int cu = u, cc = 0;                          // fetch cursor: unit, chunk within it
@@ -110,11 +106,11 @@ __global__ __launch_bounds__(512, 2) void gemm_dma_kernel(const GemmArgs g) {
       char* const sb = smem + slot * SLOT;
 #pragma unroll
       for (int i = 0; i < NA; ++i)
-        __builtin_amdgcn_global_load_lds((g_glb_vp)(ab + arow[i]), (g_lds_vp)(sb + (pw + 4 * i) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_vp)(ab + arow[i]), (lds_vp)(sb + (pw + 4 * i) * 1024), 16, 0, 0);
       const char* const wb = g.w + ((size_t)kc * N + cn0) * 64 + wl_off;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
-        __builtin_amdgcn_global_load_lds((g_glb_vp)(wb + (pw + 4 * i) * 1024), (g_lds_vp)(sb + BM * 64 + (pw + 4 * i) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_vp)(wb + (pw + 4 * i) * 1024), (lds_vp)(sb + BM * 64 + (pw + 4 * i) * 1024), 16, 0, 0);
       if (++cc == nck) {
         cc = 0;
         cu += GW;
@@ -153,12 +149,12 @@ __global__ __launch_bounds__(512, 2) void gemm_dma_kernel(const GemmArgs g) {
   const int wm = wave >> 1, wn = wave & 1;
   const int lc = lane & 15, lq = lane >> 4;
   // activation rows: block mb of the wave = rows (wm * MBW + mb) * 16 + lc of the tile: one per-lane address + immediates
-  const int laneX = (wm * MBW * 16 + lc) * 64 + ((lq ^ ((0x1230 >> (4 * ((lc >> 2) & 3))) & 3)) << 4);
+  const int laneX = (wm * MBW * 16 + lc) * 64 + ((lq ^ wswz(lc)) << 4);
   int laneW[4];
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     const int row = (wn * 4 + (nb & ~1)) * 16 + 8 * (lc >> 2) + 4 * (nb & 1) + (lc & 3);   // channel 8 (lc >> 2) + 4 (nb & 1) + (lc & 3) of the pair's 32
-    laneW[nb] = BM * 64 + row * 64 + ((lq ^ ((0x1230 >> (4 * ((row >> 2) & 3))) & 3)) << 4);
+    laneW[nb] = BM * 64 + row * 64 + ((lq ^ wswz(row)) << 4);
   }
   g_f32x4 acc[MBW][4];
   auto zero_acc = [&]() {

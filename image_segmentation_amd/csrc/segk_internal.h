@@ -21,7 +21,6 @@ struct ConvArgs {
   int Ntot, CO1, CO2;
   int twl, tiles_x, tiles_y;
   int unshuf, shuffle;
-  int persistent;       // set by the launcher
   int act;              // 1x1 geometry only: 1 = quick_gelu on (acc + bias) (CLIP MLP fc1)
 };
 int segk_conv_igemm_launch(const ConvArgs& a, int geo, int dtype, hipStream_t st);
@@ -41,6 +40,9 @@ int segk_conv_rs_rows(int B, int H, int W, int n_p);          // rows of BatchNo
 void segk_conv_rs_grid(int MT, int NT, int* gw_out, int* GW_out);   // MT pixel tiles, NT channel tiles (conv_ws too)
 struct ConvPlan;
 int segk_conv_rs_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
+// weight-stationary (conv_ws.hip) and producer/consumer (conv_pipe.hip) kernels: bf16 3x3 calls the plan gives them
+int segk_conv_ws_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
+int segk_conv_pipe_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
 // the U-Net stem on the NCHW fp32 input (stem.hip)
 int segk_stem_rows(int B, int H, int W, int Cin, int Cout, int dtype);
 int segk_stem_launch(const float* x, const float* w, void* z, void* xn, float* stats, int B, int H, int W, int Cin, int Cout,
@@ -67,10 +69,10 @@ int segk_conv_writes_act(int cin_p, int n_p, int dtype); // the layer's kernel c
 // BatchNorm statistics buffer the host allocates cannot drift apart.
 enum ConvForm {
   CONV_RS,        // register-stationary (conv_rs.hip)
-  CONV_WS,        // weight-stationary
-  CONV_PIPE,      // producer/consumer, channel tile bn (its LDS-DMA producers are chosen per call: launch_pipe)
+  CONV_WS,        // weight-stationary (conv_ws.hip)
+  CONV_PIPE,      // producer/consumer (conv_pipe.hip), channel tile bn (its LDS-DMA producers are chosen per call: launch_pipe)
   CONV_GEMM_DMA,  // LDS-DMA GEMM of the 1x1 geometry (gemm.hip)
-  CONV_GENERIC,   // conv_igemm_kernel<T, GEO, twl, wm, wn, mf, nf, pbuf>
+  CONV_GENERIC,   // conv_igemm_kernel<T, GEO, twl, wm, wn, mf, nf, pbuf> (conv_igemm.hip)
 };
 struct ConvPlan {
   ConvForm form;

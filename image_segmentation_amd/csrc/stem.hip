@@ -16,20 +16,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
-  const int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
-  return v + __int_as_float(x);
-}
-// sum over the 16 lanes of a DPP row, result in every lane: xor 1, xor 2 (quad permutes), half mirror, mirror
-__device__ __forceinline__ float row16_sum(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  v = dpp_add<0x140>(v);
-  return v;
-}
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
   return cvt_pk_bf16(a, b);      // compiler-visible (common.hpp): an asm conversion behind an MFMA reads too early
 }

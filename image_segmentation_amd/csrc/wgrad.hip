@@ -15,20 +15,11 @@
 // fp32: exact 32x32x2 MFMA, one ds_read_b32 per operand (lanes = 32 contiguous channels).
 // Each wave owns a 32x32 (n,k) block for ALL taps (9 accumulators); split-K over spatial tiles writes
 // fp32 slabs that segk_wgrad_reduce sums in fixed order (bit-stable, no atomics).
-#include <type_traits>
 #include "common.hpp"
 #include "segk_internal.h"
 #include "../../include/segk.h"
 
 namespace {
-
-// compile-time loop: f(std::integral_constant<int, I>) for I = 0 .. N-1 (inline-asm immediates need constants)
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 template <typename T, int GEO, int WC = 1> struct WG {
   static constexpr bool BF = (sizeof(T) == 2);

@@ -1,6 +1,6 @@
 """Case table of the 3x3 convolution forward / data-gradient matrix (tests/test_gpu_conv_matrix.py runs it on the GPU,
-tests/test_conv_instances.py checks on the CPU that it reaches every compiled 3x3 instance of csrc/conv_igemm.hip and
-csrc/conv_rs.hip) and a Python mirror of the dispatch.  Plain Python, no torch: both test modules import it.
+tests/test_conv_instances.py checks on the CPU that it reaches every compiled 3x3 instance of csrc/conv_igemm.hip,
+csrc/conv_pipe.hip, csrc/conv_ws.hip and csrc/conv_rs.hip) and a Python mirror of the dispatch.  Plain Python, no torch: both test modules import it.
 
 A case is (dtype, B, H, W, CA, CB, CO1, CO2, prologue, act_out, bias, stats, mode): the arguments of segk_conv3x3 /
 segk_conv3x3_act.  dtype "bf16" / "fp32"; CA, CB padded channel counts of the two sources, CO1, CO2 of the two destinations;
@@ -14,7 +14,7 @@ Case = namedtuple("Case", "dtype B H W CA CB CO1 CO2 prologue act_out bias stats
 NUM_CUS = 256                   # MI355X: the launch arithmetic below (grids, statistics rows of conv_rs) is evaluated for it
 REF_MADD_CAP = 6 * 10 ** 8      # float64 reference on the CPU: P * 9 * (CA + CB) * (CO1 + CO2) multiply-adds per dense case
 LDS_BYTES = 160 * 1024
-PIXB = 80                       # conv_igemm.hip: LDS pitch of one pixel's 64-byte chunk
+PIXB = 80                       # conv_tile.hpp: LDS pitch of one pixel's 64-byte chunk
 
 
 def cdiv(a, b):

@@ -1,5 +1,5 @@
-"""float64 restatement of the 3x3 convolution forward / data gradient (csrc/conv_igemm.hip, csrc/conv_rs.hip), the inputs of
-the three runs of tests/test_gpu_conv_matrix.py and the derived bound of its dense run.  CPU torch only; activations are
+"""float64 restatement of the 3x3 convolution forward / data gradient (csrc/conv_igemm.hip, conv_pipe.hip,
+conv_ws.hip, conv_rs.hip), the inputs of the three runs of tests/test_gpu_conv_matrix.py and the derived bound of its dense run.  CPU torch only; activations are
 NHWC [B, H, W, C], weights OIHW as the layer holds them.  Nothing here is taken from what the kernels return.
 
 The dense bound.  Operands are exact in the reference (they are rounded to `dtype` before both sides see them; with the

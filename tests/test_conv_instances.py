@@ -1,5 +1,5 @@
 """CPU: the case table of the 3x3 convolution matrix (tests/conv_cases.py) reaches every 3x3 kernel instance that
-csrc/conv_igemm.hip and csrc/conv_rs.hip compile to, without exception, and nothing else.
+csrc/conv_igemm.hip, csrc/conv_pipe.hip, csrc/conv_ws.hip and csrc/conv_rs.hip compile to, without exception, and nothing else.
 The units are compiled device-only exactly as tools/spill_report.py does and the kernel names of the resource-usage remarks
 are parsed: a new instance without a case, or a dispatch change that strands a case, fails here on any machine.  Also the
 table's own conditions: image kinds per instance, the W = 16 / 17 pairs, the spread of the features, the cases with three or
@@ -49,7 +49,7 @@ def compiled_instances():
     finally:
         sys.path.pop(0)
     names = []
-    for unit in ("conv_igemm", "conv_rs"):
+    for unit in ("conv_igemm", "conv_pipe", "conv_ws", "conv_rs"):
         rows = spill_report.report(unit)
         assert rows, f"the resource-usage remarks of {unit}.hip were not found"
         assert all("conv" in r["name"] for r in rows), [r["name"] for r in rows]

@@ -1,5 +1,5 @@
 """GPU (-m gpu): every reachable 3x3 instance of the convolution forward / data-gradient kernels (csrc/conv_igemm.hip,
-csrc/conv_rs.hip) through the C ABI (segk_conv3x3, segk_conv3x3_act), one case table (tests/conv_cases.py;
+csrc/conv_pipe.hip, csrc/conv_ws.hip, csrc/conv_rs.hip) through the C ABI (segk_conv3x3, segk_conv3x3_act), one case table (tests/conv_cases.py;
 tests/test_conv_instances.py proves on the CPU that it reaches all of them), three runs per case against
 tests/conv_reference.py.
 
