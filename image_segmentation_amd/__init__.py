@@ -5,7 +5,7 @@ from .ops import set_compute_dtype, get_compute_dtype      # noqa: F401
 from .unet import unet, DoubleConvReLU, Down, Up             # noqa: F401
 from .losses import (CrossEntropyLoss, MSELoss, WeightedMemoryEfficientDiceLoss, WeightedDiceCELoss,     # noqa: F401
                      WeightedMemoryEfficientDiceLossPrompt, WeightedDiceNLLLoss, HardPixelLoss, FocalLoss,
-                     OhemCrossEntropyLoss)
+                     OhemCrossEntropyLoss, LovaszSoftmaxLoss, LovaszCELoss)
 from .clipunet import ClipUNet, UNetDecoder, DecoderBlock, ClipViTEncoder                   # noqa: F401
 from .autoencoder import SegmentationAutoencoder, ReconstructionAutoencoder               # noqa: F401
 from .prompt import PromptModel                                                            # noqa: F401

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 323         # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 324         # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
@@ -109,6 +109,8 @@ SIGNATURES = {
     "segk_distill_bwd": (_i, [_fp, _vp, _i, _vp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _f, _fp, _vp]),
     "segk_hard_loss_fwd": (_i, [_fp, _vp, _fp, _i, _i, _l, _i, _f, _f, _i, _f, _i, _i, _vp, _vp, _fp, _fp, _fp, _vp]),
     "segk_hard_loss_bwd": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _i, _i, _l, _i, _f, _f, _i, _fp, _vp]),
+    "segk_lovasz_fwd": (_i, [_fp, _vp, _fp, _i, _i, _l, _i, _i, _i, _vp, _l, _fp, _vp, _fp, _vp]),
+    "segk_lovasz_bwd": (_i, [_fp, _vp, _fp, _vp, _fp, _i, _i, _l, _i, _i, _fp, _vp]),
     "segk_prompt_mix_fwd": (_i, [_fp, _fp, _fp, _i, _l, _vp]),
     "segk_prompt_mix_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _l, _vp]),
     "segk_prob_loss_fwd": (_i, [_fp, _vp, _fp, _i, _i, _l, _i, _f, _f, _f, _i, _f, _fp, _fp, _fp, _vp]),

@@ -117,6 +117,94 @@ class OhemCrossEntropyLoss(HardPixelLoss):
                          min_kept=min_kept, min_fraction=min_fraction)
 
 
+def _check_lovasz_weight(weight):
+    """class weights of the Lovasz term: finite and non-negative (a zero takes the class out); checked where the host can see
+    them, on CPU tensors and sequences -- a device tensor is taken as it is, reading it would be a sync"""
+    if weight is None or (isinstance(weight, torch.Tensor) and weight.is_cuda):
+        return
+    w = torch.as_tensor(weight, dtype=torch.float64)
+    if w.dim() != 1 or w.numel() == 0:
+        raise ValueError(f"weight must be a vector of class weights, got shape {tuple(w.shape)}")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("weight must be finite and non-negative")
+
+
+class LovaszSoftmaxLoss(nn.Module):
+    """Lovasz-Softmax loss (Berman, Triki, Blaschko 2018), the convex surrogate of mean IoU, on [N,C,H,W]
+    logits: per class the pixel errors (1 - p_c where the label is c, p_c elsewhere) sorted descending on the device and
+    weighted by the gradient of the Jaccard index along that order; the weighted mean over the classes that enter, then over
+    the segments.
+      per_image   one sort per image and the mean over the images (images without a labelled pixel stay in the divisor)
+                  instead of one sort over the batch;
+      classes     "present": the classes with a labelled pixel in the segment; "all": every class;
+      weight      class weights of that mean (1 when absent; a zero takes the class out).
+    No labelled pixel at all: exactly 0 with a zero gradient (not CrossEntropy's NaN).  Only reduction 'mean' exists; under
+    DistributedDataParallel every rank sorts its own batch.  After a call `.last` holds device tensors (no sync): "n" (labelled
+    pixels, float64), "present" (int32 [S,C], the classes that entered) and "per_class" (float64 [S,C], the class terms), S = N
+    with per_image, else 1.  Targets [N,H,W] or [N,1,H,W] class indices."""
+
+    def __init__(self, per_image: bool = False, classes: str = "present", weight: Optional[torch.Tensor] = None,
+                 ignore_index: Optional[int] = None):
+        super().__init__()
+        if classes not in ("present", "all"):
+            raise ValueError(f"classes must be 'present' or 'all', got {classes!r}")
+        _check_lovasz_weight(weight)
+        self.per_image = bool(per_image)
+        self.classes = classes
+        self.weight = weight
+        self.ignore_index = ignore_index
+        self.last = {}
+
+    def forward(self, outputs, targets):
+        _check_targets(outputs, targets)
+        if self.weight is not None and outputs.dim() == 4 and len(self.weight) != outputs.shape[1]:
+            raise ValueError(f"weight has {len(self.weight)} entries, the logits {outputs.shape[1]} classes")
+        ign = self.ignore_index if self.ignore_index is not None and self.ignore_index >= 0 else None
+        loss, state = ops.LovaszFn.apply(outputs, targets, self.weight, ign, self.per_image, self.classes == "all")
+        N, C = outputs.shape[0], outputs.shape[1]
+        S = N if self.per_image else 1
+        Q = S * C
+        self.last = {"n": state[1], "present": state[2 + 3 * Q:2 + 4 * Q].view(S, C).to(torch.int32),
+                     "per_class": state[2:2 + Q].view(S, C)}
+        return loss
+
+
+class LovaszCELoss(nn.Module):
+    """lovasz_weight * LovaszSoftmaxLoss + ce_weight * CrossEntropyLoss on the same logits, the form the Lovasz term is
+    trained in.  class_weights and ignore_index go to both terms; ce_kwargs may hold label_smoothing.  A term whose weight is 0
+    launches nothing."""
+
+    def __init__(self, lovasz_weight: float = 1.0, ce_weight: float = 1.0, class_weights: Optional[torch.Tensor] = None,
+                 ignore_index: Optional[int] = None, per_image: bool = False, classes: str = "present", ce_kwargs=None):
+        super().__init__()
+        ce_kwargs = dict(ce_kwargs or {})
+        if set(ce_kwargs) - {"label_smoothing"}:
+            raise NotImplementedError("extra nn.CrossEntropyLoss kwargs are not supported by the fused kernel "
+                                      "(label_smoothing is the one that is)")
+        self.lovasz_weight = float(lovasz_weight)
+        self.ce_weight = float(ce_weight)
+        if self.lovasz_weight == 0.0 and self.ce_weight == 0.0:
+            raise ValueError("lovasz_weight and ce_weight are both 0: nothing to compute")
+        self.lovasz = LovaszSoftmaxLoss(per_image=per_image, classes=classes, weight=class_weights, ignore_index=ignore_index)
+        self.ce = CrossEntropyLoss(weight=class_weights, ignore_index=-100 if ignore_index is None else ignore_index,
+                                   label_smoothing=ce_kwargs.get("label_smoothing", 0.0))
+
+    @property
+    def last(self):
+        return self.lovasz.last
+
+    def forward(self, outputs, targets):
+        _check_targets(outputs, targets)
+        total = None
+        for weight, term in ((self.lovasz_weight, self.lovasz), (self.ce_weight, self.ce)):
+            if weight == 0.0:
+                continue
+            value = term(outputs, targets)
+            value = value if weight == 1.0 else weight * value      # a weight of 1 hands the term's own buffer on
+            total = value if total is None else total + value
+        return total
+
+
 class MSELoss(nn.Module):
     """nn.MSELoss(size_average=None, reduce=None, reduction='mean') for two same-shaped tensors (the reconstruction and its
     input, utils/training.py:141,234).  'mean' and 'sum' run on the deterministic HIP reduction; 'none' and the legacy

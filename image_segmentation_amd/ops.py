@@ -1696,6 +1696,59 @@ class HardLossFn(torch.autograd.Function):
         return dl, None, None, None, None, None, None
 
 
+LOVASZ_TILE = 2048          # SEGK_LOVASZ_TILE
+
+
+def lovasz_scratch_bytes(C, P, S):
+    """SEGK_LOVASZ_SCRATCH_BYTES(C, P, S) of include/segk.h: the words and payloads of the C * P slots twice, 260 words per tile
+    of LOVASZ_TILE slots and 258 per (segment, class)"""
+    return 4 * (4 * C * P + 260 * C * S * ((P // S + LOVASZ_TILE - 1) // LOVASZ_TILE) + 258 * C * S)
+
+
+def lovasz_state_doubles(C, S):
+    """SEGK_LOVASZ_STATE_DOUBLES(C, S): loss, n, four [S, C] tables (L, a, G, enters), n_s [S]"""
+    return 2 + 4 * C * S + S
+
+
+class LovaszFn(torch.autograd.Function):
+    """Lovasz-Softmax loss on [N,C,H,W] logits: per (segment, class) the errors sorted on the device, weighted by
+    the Jaccard gradient along that order, mean over the entering classes and the segments.  per_image: one segment per image
+    instead of one for the batch; all_classes: every class enters a segment with labelled pixels, not only those present in it.
+    Returns (loss, state): the loss in a buffer of its own and the float64 state [loss, n, L [S,C], a [S,C], G [S,C], enters
+    [S,C], n_s [S]] (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, class_weights, ignore_index, per_image, all_classes):
+        lg, tg, cw, ign, _part, _state, out = _loss_operands(logits, target, class_weights, ignore_index, "Lovasz-Softmax loss",
+                                                             "logits")
+        N, C, H, W = logits.shape
+        P, dev = N * H * W, logits.device
+        S = N if per_image else 1
+        nbytes = lovasz_scratch_bytes(C, P, S)
+        scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        coef = torch.empty((C, P), dtype=torch.float32, device=dev)
+        state = torch.empty(lovasz_state_doubles(C, S), dtype=torch.float64, device=dev)
+        with _span("lovasz_fwd", 0.0, P * (4.0 * C + 8) + C * P * (8.0 + 4 * 20.0 + 8.0 + 12.0)):
+            _lib.call("segk_lovasz_fwd", lg.data_ptr(), tg.data_ptr(), _p(cw), N, C, H * W, ign, int(bool(per_image)),
+                      int(bool(all_classes)), scratch.data_ptr(), nbytes, coef.data_ptr(), state.data_ptr(), out.data_ptr(),
+                      _stream())
+        ctx.cfg = (N, C, H, W, ign, int(bool(per_image)))
+        ctx.save_for_backward(lg, tg, coef, state)
+        ctx.mark_non_differentiable(state)
+        return out.view(()), state
+
+    @staticmethod
+    def backward(ctx, gout, _gstate):
+        lg, tg, coef, state = ctx.saved_tensors
+        N, C, H, W, ign, per_image = ctx.cfg
+        go = _f32c(gout).reshape(1)
+        dl = torch.empty_like(lg)
+        with _span("lovasz_bwd", 0.0, N * H * W * (12.0 * C + 8)):
+            _lib.call("segk_lovasz_bwd", lg.data_ptr(), tg.data_ptr(), coef.data_ptr(), state.data_ptr(), go.data_ptr(), N, C,
+                      H * W, ign, per_image, dl.data_ptr(), _stream())
+        return dl, None, None, None, None, None
+
+
 class PromptMixFn(torch.autograd.Function):
     """final_probs of the prompt model (reference prompt_based/prompt.py:35-56): softmax of the frozen 4-class CLIP-UNet
     logits remixed with the sigmoid of the mask U-Net's logit; gradient flows to the mask logit only (prompt.py:30-31)."""

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 323
-#define SEGK_ENTRY_COUNT 106
+#define SEGK_ABI_VERSION 324
+#define SEGK_ENTRY_COUNT 108
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -535,6 +535,46 @@ int segk_hard_loss_fwd(const float* logits, const int64_t* labels, const float* 
 int segk_hard_loss_bwd(const float* logits, const int64_t* labels, const float* class_weights, const uint32_t* keys,
                        const float* state, const float* grad_out, int N, int C, long HW, int ignore_index,
                        float label_smoothing, float gamma, int select, float* dlogits, segk_stream_t s);
+
+/* ---- Lovasz-Softmax loss: device segmented sort, Jaccard scan -----------------------------------------
+ * logits fp32 [N,C,HW], 1 <= C <= 8; labels int64 [N,HW]; P = N HW < 2^31; class_weights [C] or NULL (all 1); ignore_index < 0:
+ * none.  A pixel COUNTS when 0 <= y < C and y != ignore_index.  per_image 1: S = N segments of L = HW pixels; 0: S = 1, L = P.
+ * Per counted pixel, in fp32: m = max z, e_k = expf(z_k - m), se = sum e_k, p_k = e_k * (1 / se); for every class c, fg =
+ * [y = c] and err_c = fg ? sum_{k != c} p_k (class order from 0.f, never 1 - p_c) : p_c.  Sort word: bits(err_c) + 1, 0x3FFFFFFF
+ * for a NaN error, 0 for a pixel that does not count; payload (fg << 31) | index-in-segment.  Inside every (segment s, class c)
+ * the slots are ordered by word descending, ties by index ascending (a stable sort: the permutation is unique).  With G = the fg
+ * slots of (s, c) and F_i = the fg slots among the sorted positions 1..i, in float64 from integers: J_i = 1 - (G - F_i) /
+ * (G + i - F_i), J_0 = 0, g_i = J_i - J_{i-1}; L_{s,c} = sum_i (double)err_i g_i over the counted slots, err_i the value of the
+ * word (NaN for the NaN word), summed per tile of SEGK_LOVASZ_TILE sorted slots and over the tiles in one fixed order.
+ * Class c ENTERS segment s iff s has a counted pixel and (classes == SEGK_LOVASZ_ALL or G_{s,c} > 0).  loss_s = sum_{c enters}
+ * w_c L_{s,c} / sum_{c enters} w_c (0 when no class enters or the weights sum to 0); loss = (float)((1 / S) sum_s loss_s): exactly
+ * 0 when no pixel counts (not CrossEntropy's NaN), NaN when an error is NaN.
+ * coef fp32 [C][P] (class-major, pixel order), written everywhere: (float)g_i, negated when fg, at the pixel sorted to position i;
+ * exactly 0 at pixels that do not count.  state: SEGK_LOVASZ_STATE_DOUBLES(C, S) float64: [0] loss, [1] the counted pixels, then
+ * four [S][C] tables -- L_{s,c}; a_{s,c} = (float)(w_c / (S sum_{c' enters} w_c')) for entering classes, else 0; G_{s,c}; 1 where
+ * c enters -- then n_s [S].  loss_out (may be NULL): the loss.
+ * scratch: SEGK_LOVASZ_SCRATCH_BYTES(C, P, S) bytes, 16-byte aligned, nothing in it needs a value before the call; a smaller
+ * scratch_bytes is refused.  With T = SEGK_LOVASZ_TILE, TS = ceil(L / T), NT = C S TS, as uint32 words in this order: the float64
+ * tile sums [2 NT]; sorted words [C P] and sorted payloads [C P] (segment (s, c) at slot (c S + s) L); their second copies
+ * [C P], [C P]; the tile digit tables [256 NT]; the segment digit totals [256 C S]; the tile fg counts, exclusive over a segment
+ * [NT]; the tile counted slots [NT]; G [C S] and the counted slots [C S] by segment c S + s.
+ * Kernels: keys, four radix passes (8 bits: tile histogram, scan over the tiles, ranked scatter), count, scan, terms; the block of
+ * the terms pass that arrives last finishes.  No workgroup waits for another, no host sync, no float atomics.
+ * Every scalar and every host-visible pointer is validated (-2 before any launch). */
+#define SEGK_LOVASZ_TILE 2048
+#define SEGK_LOVASZ_PRESENT 0
+#define SEGK_LOVASZ_ALL 1
+#define SEGK_LOVASZ_SCRATCH_WORDS(C, P, S) (4 * (C) * (P) + 260 * (C) * (S) * (((P) / (S) + SEGK_LOVASZ_TILE - 1) / SEGK_LOVASZ_TILE) + 258 * (C) * (S))
+#define SEGK_LOVASZ_SCRATCH_BYTES(C, P, S) (4 * SEGK_LOVASZ_SCRATCH_WORDS(C, P, S))   /* 64-bit arguments */
+#define SEGK_LOVASZ_STATE_DOUBLES(C, S) (2 + 4 * (C) * (S) + (S))
+int segk_lovasz_fwd(const float* logits, const int64_t* labels, const float* class_weights, int N, int C, long HW,
+                    int ignore_index, int per_image, int classes, void* scratch, long scratch_bytes, float* coef,
+                    double* state, float* loss_out, segk_stream_t s);
+/* With t_c = (a_{s,c} coef_c) p_c and A = sum_c t_c (class order from 0.f), all fp32, p formed again by the forward's code:
+ * dlogits_j = grad_out[0] (t_j - p_j A) at counted pixels -- the sum over c of a_{s,c} coef_c p_c ([j = c] - p_j) -- and
+ * exactly 0 at every other pixel.  coef and state as segk_lovasz_fwd left them; same N, C, HW, ignore_index, per_image. */
+int segk_lovasz_bwd(const float* logits, const int64_t* labels, const float* coef, const double* state, const float* grad_out,
+                    int N, int C, long HW, int ignore_index, int per_image, float* dlogits, segk_stream_t s);
 
 /* ---- prompt model (prompt_based/prompt.py:33-56; utils/weighted_loss.py:170-343) ---------------------------
  * remix of the frozen 4-class CLIP-UNet softmax with the sigmoid of the 1-channel mask U-Net, fp32 NCHW:

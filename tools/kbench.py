@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill, hardloss, optim)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill, hardloss, lovasz, optim)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -295,6 +295,55 @@ def hardloss():
         counts = state[6:8].view(torch.int32).tolist()
         print(f"hard {name:22s}fwd {tf:7.1f} us ({nf/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({nbw/tb/1e3:7.1f} GB/s)   value {float(out):.6f}"
               f"   n {counts[0]} kept {counts[1]}")
+
+
+def lovasz():
+    """Lovasz-Softmax forward / backward (segk_lovasz_fwd / _bwd) through the C ABI beside segk_loss_fwd / _bwd (CrossEntropy) and
+    the hard-pixel selection in the same run, at the bench batch (32 x 3 x 256 x 256) and at config 5 (8 x 4 x 512 x 512), one
+    segment per batch and one per image.  Forward: 1 keys launch, 4 x (histogram, scan, scatter), count, scan, terms = 16 launches;
+    bytes P (4 C + 8) + C P (8 written by keys, 4 x (4 + 8 + 8 + 16) by the passes -- words read twice, payloads once, both
+    written -- 8 by count, 8 + 4 by terms)."""
+    import math
+    iters = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 50
+    st = ops._stream()
+    for N, C, H, W in ((32, 3, 256, 256), (8, 4, 512, 512)):
+        P = N * H * W
+        lg = torch.randn((N, C, H, W), device="cuda")
+        tg = torch.randint(0, C, (N, H, W), device="cuda")
+        part = torch.empty(_lib.query("segk_loss_part_floats", P), device="cuda")
+        state = torch.empty(_lib.query("segk_loss_state_floats"), device="cuda")
+        out = torch.empty(1, device="cuda"); go = torch.ones(1, device="cuda"); dl = torch.empty_like(lg)
+        keys = torch.empty(P, dtype=torch.int32, device="cuda")
+        hist = torch.empty(ops.HARD_HIST_WORDS, dtype=torch.int32, device="cuda")
+        f = lambda: _lib.call("segk_loss_fwd", lg.data_ptr(), tg.data_ptr(), None, N, C, H * W, -1, 1e-5, 0.0, 1.0,
+                              part.data_ptr(), state.data_ptr(), out.data_ptr(), st)
+        b = lambda: _lib.call("segk_loss_bwd", lg.data_ptr(), tg.data_ptr(), None, state.data_ptr(), go.data_ptr(), N, C,
+                              H * W, -1, 0.0, 1.0, dl.data_ptr(), st)
+        tf = timeit(f, iters); tb = timeit(b, iters)
+        fb, bb = P * (4 * C + 8), P * (8 * C + 8)
+        print(f"{N}x{C}x{H}x{W}  loss ce             fwd {tf:8.1f} us ({fb/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us ({bb/tb/1e3:7.1f} GB/s)"
+              f"   value {float(out):.6f}")
+        f = lambda: _lib.call("segk_hard_loss_fwd", lg.data_ptr(), tg.data_ptr(), None, N, C, H * W, -1, 0.0, 0.0, 1, -math.log(0.7),
+                              0, 16384, keys.data_ptr(), hist.data_ptr(), part.data_ptr(), state.data_ptr(), out.data_ptr(), st)
+        b = lambda: _lib.call("segk_hard_loss_bwd", lg.data_ptr(), tg.data_ptr(), None, keys.data_ptr(), state.data_ptr(),
+                              go.data_ptr(), N, C, H * W, -1, 0.0, 0.0, 1, dl.data_ptr(), st)
+        tf = timeit(f, iters); tb = timeit(b, iters)
+        print(f"{N}x{C}x{H}x{W}  hard selection on   fwd {tf:8.1f} us ({(fb + P*(16+4*C+8))/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us"
+              f" ({(bb+4*P)/tb/1e3:7.1f} GB/s)   value {float(out):.6f}")
+        for per_image in (0, 1):
+            S = N if per_image else 1
+            nbytes = ops.lovasz_scratch_bytes(C, P, S)
+            scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device="cuda")
+            coef = torch.empty((C, P), device="cuda")
+            lstate = torch.empty(ops.lovasz_state_doubles(C, S), dtype=torch.float64, device="cuda")
+            f = lambda: _lib.call("segk_lovasz_fwd", lg.data_ptr(), tg.data_ptr(), None, N, C, H * W, -1, per_image, 0,
+                                  scratch.data_ptr(), nbytes, coef.data_ptr(), lstate.data_ptr(), out.data_ptr(), st)
+            b = lambda: _lib.call("segk_lovasz_bwd", lg.data_ptr(), tg.data_ptr(), coef.data_ptr(), lstate.data_ptr(), go.data_ptr(),
+                                  N, C, H * W, -1, per_image, dl.data_ptr(), st)
+            tf = timeit(f, iters); tb = timeit(b, iters)
+            nf, nbw = fb + C * P * (8 + 4 * 36 + 8 + 12), P * (12 * C + 8)
+            print(f"{N}x{C}x{H}x{W}  lovasz per_image={per_image}  fwd {tf:8.1f} us ({nf/tf/1e3:7.1f} GB/s)   bwd {tb:7.1f} us"
+                  f" ({nbw/tb/1e3:7.1f} GB/s)   value {float(out):.6f}   scratch {nbytes/2**20:.1f} MiB   n {int(lstate[1].item())}")
 
 
 def head():
@@ -1173,6 +1222,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "recon":
         recon()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "lovasz":
+        lovasz()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "hardloss":
         hardloss()
