@@ -31,6 +31,7 @@ from . import _lib, ops, prompts, tiles as _tiles, tta as _tta
 from .augment import _upload
 from .clipunet import ClipUNet
 from .components import Components, as_clean, components as _components
+from .vectors import as_vectors, vectorize as _vectorize
 from . import utils as U
 
 # app.py:187-208 -- the demo's palette and the two class-name tables
@@ -67,6 +68,7 @@ class Prediction:
     # set on merged views, None otherwise; attributes, not dataclass fields: the constructor stays as it was
     confidence = None                          # uint8 [H,W], (uint8)(255 p_best + 0.5)
     scores = None                              # Segmenter(return_scores=True): float32 [C,H,W], the merged probabilities
+    vectors = None                             # Segmenter(vectors=...): the vectors.Vectors of `mask`
 
 
 def _num_classes(model):
@@ -301,16 +303,22 @@ class Segmenter:
     temperature=  a positive float (calibration.fit_temperature finds it), or one per model of an ensemble: each model's
               logits are multiplied by the float32 1/T before the prediction kernels run.  One view: the mask is unchanged
               up to rounding and the confidence is the calibrated one; merged views under "prob": the merge itself changes.
-              Refused for outputs="probs"."""
+              Refused for outputs="probs".
+
+    Vector output (with None nothing changes on any route):
+    vectors=  True or a dict of vectors.vectorize's keywords (connectivity, classes, max_components, max_runs, max_edges,
+              max_rings, max_vertices): Prediction.vectors holds the run table, contour rings and corner vertices of the final
+              (cleaned) mask, built on the device without a synchronisation."""
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
                  sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False, tiles=None,
-                 temperature=None):
+                 temperature=None, vectors=None):
         models = list(model) if isinstance(model, (list, tuple)) else [model]
         if not models:
             raise ValueError("an ensemble needs at least one model")
         model = models[0]
         self.clean = as_clean(clean)
+        self.vectors = as_vectors(vectors)
         if not float(sigma) > 0:
             raise ValueError(f"sigma must be positive, got {sigma}")
         self.sigma = float(sigma)
@@ -480,6 +488,8 @@ class Segmenter:
                 pred = Prediction(comps.mask, color, counts[k, :C], Mk, meta, mask, comps)
             if confident:
                 pred.confidence, pred.scores = conf, scores
+            if self.vectors is not None:
+                pred.vectors = _vectorize(pred.mask, **self.vectors)
             preds.append(pred)
         return preds
 

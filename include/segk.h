@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 324
-#define SEGK_ENTRY_COUNT 108
+#define SEGK_ABI_VERSION 325
+#define SEGK_ENTRY_COUNT 110
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -418,6 +418,42 @@ int segk_cc_clean(const uint8_t* mask, uint8_t* out, int32_t* ws, int32_t* kept,
  * color 4-byte aligned; at least one output. */
 int segk_mask_finish(const uint8_t* mask, uint8_t* color, const uint8_t* palette, uint64_t* counts, const int64_t* labels,
                      uint64_t* M, int C, int H, int W, segk_stream_t s);
+
+/* ---- mask vectorisation: run table, contour rings, corner vertices (the reference has no such code: this
+ * replaces a mask.cpu() + cv2.findContours / pycocotools encode).  Integer arithmetic only: results are unique and bit-stable.
+ * No launch waits for another workgroup, the host reads no count back, and every device loop is bounded by an argument; the
+ * counts the later launches need are read from device memory.
+ *
+ * Workspace: SEGK_VEC_WS_INTS(H, W, max_edges) 32-bit words, 16-byte aligned, uninitialised, scratch of ONE call (either
+ * entry; nothing has to survive between calls).  With HW = H*W, ME = max_edges and R4(n) = n rounded up to a multiple of 4,
+ * in words: 16 | ring areas uint64 [ME/4 + 1] | block partials uint64 [ceil(ME/2048)] | two jump buffers int2 [ME] each |
+ * edge keys [ME] | successors, later the ring order [ME] | ring heads [ME] | edge base per pixel [HW] | block partials
+ * [ceil(HW/2048)] | corner flags, bytes [ME] | side masks, bytes [HW].  segk_vec_runs uses the first W * ceil(H/128) words. */
+#define SEGK_VEC_CHUNK 2048
+#define SEGK_VEC_RUN_ROWS 128
+#define SEGK_VEC_MAX_CAP (1L << 30)
+#define SEGK_VEC_R4(n) (((long)(n) + 3L) / 4L * 4L)
+#define SEGK_VEC_WS_INTS(H, W, ME)                                                                                              \
+  (16L + SEGK_VEC_R4(2L * ((long)(ME) / 4L + 1L)) + SEGK_VEC_R4(2L * (((long)(ME) + SEGK_VEC_CHUNK - 1L) / SEGK_VEC_CHUNK)) + \
+   7L * SEGK_VEC_R4(ME) + SEGK_VEC_R4((long)(H) * (long)(W)) +                                                                  \
+   SEGK_VEC_R4(((long)(H) * (long)(W) + SEGK_VEC_CHUNK - 1L) / SEGK_VEC_CHUNK) + SEGK_VEC_R4(((long)(ME) + 3L) / 4L) +          \
+   SEGK_VEC_R4(((long)(H) * (long)(W) + 3L) / 4L))
+/* DESIGN.md 3.17 "run table": obj [H,W] int32 (0: nothing, else an id >= 1; Components.labels) read in column-major order
+ * t = x*H + y.  A run starts at t = 0 and wherever obj differs from the element before; run_start / run_obj [max_runs] hold
+ * the first min(runs, max_runs) runs in ascending t (runs of id 0 included), totals[0] = runs.  Nothing at or past max_runs or
+ * the run count is written.  H*W <= SEGK_CC_MAX_PIXELS, 1 <= max_runs <= SEGK_VEC_MAX_CAP. */
+int segk_vec_runs(const int32_t* obj, int32_t* run_start, int32_t* run_obj, int32_t* totals, int32_t* ws, int H, int W,
+                  int max_runs, segk_stream_t s);
+/* DESIGN.md 3.17 "boundary edges", "successor", "ring record", "vertices", "capacities": totals[1] = E, the directed unit
+ * boundary edges of all objects.  With E <= max_edges: totals[2] = R rings, totals[3] = V corner vertices; ring_obj / ring_head
+ * / ring_len [max_rings] and ring_area2 int64 [max_rings] hold the first min(R, max_rings) rings in ascending head key,
+ * ring_offset [max_rings + 1] the first min(R, max_rings) + 1 entries of the CSR offsets into xy, xy [max_vertices][2] = (x, y)
+ * the first min(V, max_vertices) vertices.  With E > max_edges: totals[2] = totals[3] = -1 and no ring array is touched.
+ * Nothing at or past a capacity or a total is written.  connectivity 4 or 8: which of two diagonal pixels of one object a
+ * ring joins -- the connectivity obj was labelled with.  1 <= every capacity <= SEGK_VEC_MAX_CAP; ring_area2 8-byte aligned. */
+int segk_vec_rings(const int32_t* obj, int32_t* ring_obj, int32_t* ring_head, int32_t* ring_len, int64_t* ring_area2,
+                   int32_t* ring_offset, int32_t* xy, int32_t* totals, int32_t* ws, int H, int W, int connectivity,
+                   int max_edges, int max_rings, int max_vertices, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

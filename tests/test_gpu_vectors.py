@@ -1,0 +1,244 @@
+"""MI355X: mask vectorisation (image_segmentation_amd/vectors.py, csrc/vectors.hip) against the restatement of DESIGN.md 3.17
+in tests/vector_reference.py -- EXACT equality of every array prefix and of every entry of totals, for both connectivities,
+through the C ABI (segk_vec_runs / segk_vec_rings on the restatement's object map) and through seg.vectorize (on the mask,
+labelled by segk_cc_label).  Output and workspace buffers start as 0xFF bytes: what lies at or past a capacity or a total
+must still be 0xFF afterwards, and nothing may rest on a zeroed workspace.  There is nothing to tolerance: the arithmetic is
+integer and the definition makes the result unique.  The overflow cases are ordinary bounded runs."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import vector_cases as VC                                                          # noqa: E402
+import vector_reference as VR                                                      # noqa: E402
+
+pytestmark = pytest.mark.gpu
+BOTH = pytest.mark.parametrize("connectivity", [4, 8])
+ARRAYS = ("run_start", "run_obj") + VR.RING_ARRAYS
+
+
+def shapes(caps):
+    mr, me, mg, mv = caps
+    return {"run_start": (mr,), "run_obj": (mr,), "ring_obj": (mg,), "ring_head": (mg,), "ring_len": (mg,), "ring_area2": (mg,),
+            "ring_offset": (mg + 1,), "xy": (mv, 2), "totals": (4,)}
+
+
+def expected(full, caps):
+    """the whole buffers a call must leave: the truncated restatement in front, 0xFF bytes (-1) behind"""
+    t = VR.truncate(full, *caps)
+    out = {}
+    for name, shape in shapes(caps).items():
+        a = np.full(shape, -1, np.int64 if name == "ring_area2" else np.int32)
+        a[:len(t[name])] = t[name]
+        out[name] = a
+    return out
+
+
+def run_abi(O, connectivity, caps, stream=None):
+    """both entries on the object map O, every buffer pre-filled with 0xFF -> the whole buffers as NumPy arrays"""
+    from image_segmentation_amd import _lib, ops, vectors as V
+    H, W = O.shape
+    dev = torch.device("cuda:0")
+    obj = torch.from_numpy(np.ascontiguousarray(O, dtype=np.int32)).to(dev)
+    buf = {n: torch.full(s, -1, dtype=torch.int64 if n == "ring_area2" else torch.int32, device=dev) for n, s in shapes(caps).items()}
+    ws = torch.full((V.ws_ints(H, W, caps[1]),), -1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev):
+        s = ops._stream()
+        P = lambda n: buf[n].data_ptr()
+        _lib.call("segk_vec_runs", obj.data_ptr(), P("run_start"), P("run_obj"), P("totals"), ws.data_ptr(), H, W, caps[0], s)
+        _lib.call("segk_vec_rings", obj.data_ptr(), P("ring_obj"), P("ring_head"), P("ring_len"), P("ring_area2"), P("ring_offset"),
+                  P("xy"), P("totals"), ws.data_ptr(), H, W, connectivity, caps[1], caps[2], caps[3], s)
+    torch.cuda.synchronize()
+    assert np.array_equal(obj.cpu().numpy(), O), "the object map was modified"
+    return {n: b.cpu().numpy() for n, b in buf.items()}
+
+
+def compare(got, want, what):
+    assert got["totals"].tolist() == want["totals"].tolist(), f"{what}: totals {got['totals'].tolist()}, expected {want['totals'].tolist()}"
+    for n in ARRAYS:
+        assert got[n].dtype == want[n].dtype and got[n].shape == want[n].shape, (what, n)
+        bad = np.flatnonzero((got[n] != want[n]).reshape(len(want[n]), -1).any(axis=1))
+        assert bad.size == 0, f"{what}: {n} differs in {bad.size} rows, first at {bad[0]}: {got[n][bad[0]]} != {want[n][bad[0]]}"
+
+
+@pytest.mark.parametrize("name", VC.NAMES)
+@BOTH
+def test_c_abi_equals_the_restatement(name, connectivity):
+    O, full = VC.object_map(name, connectivity), VC.reference(name, connectivity)
+    first = None
+    for regime, caps in VC.regimes(full).items():
+        got = run_abi(O, connectivity, caps)
+        compare(got, expected(full, caps), f"{name} c{connectivity} {regime} {caps}")
+        first = first or (caps, got)
+    caps, got = first                                                      # the roomy regime again, and on a side stream
+    again, side = run_abi(O, connectivity, caps), run_abi(O, connectivity, caps, torch.cuda.Stream())
+    for n in ARRAYS + ("totals",):
+        assert np.array_equal(again[n], got[n]) and np.array_equal(side[n], got[n]), (name, n)
+
+
+@pytest.mark.parametrize("which", ["exact", "below", "above"])
+@BOTH
+def test_serpentine_round_count_follows_the_capacity(which, connectivity):
+    """one ring of a few thousand edges: the pointer-jumping rounds are derived from max_edges alone"""
+    full = VC.reference("serpentine", connectivity)
+    runs, E, R, V = (int(v) for v in full["totals"])
+    assert R == 1 and E > 4000
+    me = VC.serpentine_capacities()[which]
+    caps = (runs, me, 4, V)
+    got = run_abi(VC.object_map("serpentine", connectivity), connectivity, caps)
+    compare(got, expected(full, caps), f"serpentine c{connectivity} max_edges={me}")
+    assert (got["totals"][2] == -1) == (which == "below")
+
+
+@pytest.mark.parametrize("name", VC.MASK_NAMES)
+@BOTH
+def test_vectorize_equals_the_restatement(name, connectivity):
+    import image_segmentation_amd as seg
+    mask, classes = VC.MASKS[name]
+    full = VC.reference(name, connectivity)
+    dev = torch.from_numpy(mask.copy()).cuda()
+    K = len(VC.labelled(name, connectivity)[1])
+    for regime, caps in VC.regimes(full).items():
+        rows = 1024 if regime == "roomy" else max(1, K // 2)
+        vec = seg.vectorize(dev, connectivity=connectivity, classes=classes, max_components=rows, max_runs=caps[0], max_edges=caps[1],
+                            max_rings=caps[2], max_vertices=caps[3])
+        # torch.empty buffers: only the prefixes are defined
+        t = VR.truncate(full, *caps)
+        assert vec.totals.cpu().numpy().tolist() == t["totals"].tolist(), (name, regime)
+        for n in ARRAYS:
+            a = getattr(vec, n).cpu().numpy()
+            assert a.shape == shapes(caps)[n] and np.array_equal(a[:len(t[n])], t[n]), (name, regime, n)
+        rows_ref = VC.labelled(name, connectivity)[1]
+        k = min(K, rows)
+        assert int(vec.num.item()) == K and vec.size == mask.shape and vec.connectivity == connectivity and vec.max_edges == caps[1]
+        for key in ("cls", "area", "box"):
+            a = getattr(vec, key).cpu().numpy()
+            assert np.array_equal(a[:k], np.asarray([r[key] for r in rows_ref[:k]], np.int32).reshape(a[:k].shape)), (name, key)
+        fits = all(int(v) <= c for v, c in zip(full["totals"], caps)) and K <= rows
+        assert vec.complete == fits and (fits or regime != "roomy" or K > rows)
+    assert np.array_equal(dev.cpu().numpy(), mask), "the input mask was modified"
+
+
+def test_vectorize_defaults_components_and_host_methods():
+    import image_segmentation_amd as seg
+    name = "noise0.1_3c_120x77"
+    mask, classes = VC.MASKS[name]
+    full, rows = VC.reference(name, 4), VC.labelled(name, 4)[1]
+    O = VC.object_map(name, 4)
+    dev = torch.from_numpy(mask.copy()).cuda()
+    vec = seg.vectorize(dev, classes=classes)                              # default capacities
+    H, W = mask.shape
+    assert (vec.run_start.shape[0], vec.max_edges, vec.ring_obj.shape[0], vec.xy.shape[0]) == seg.default_capacities(H, W)
+    assert vec.complete and vec.totals.cpu().numpy().tolist() == full["totals"].tolist()
+    polys = vec.polygons()
+    assert len(polys) == len(full["ring_obj"])
+    off = full["ring_offset"]
+    for i, (o, a2, v) in enumerate(polys):
+        assert o == full["ring_obj"][i] and a2 == full["ring_area2"][i] and np.array_equal(v, full["xy"][off[i]:off[i + 1]])
+    for k in (1, 2, len(rows)):
+        assert np.array_equal(VR.rle_decode(vec.coco_rle(k)), O == k)
+    ann = vec.to_coco(3, {1: 1, 2: 2, 3: 3})
+    assert len(ann) == len(rows) and sum(a["area"] for a in ann) == int((mask != 0).sum())
+    # a Components: its cleaned mask is vectorised afresh
+    comps = seg.components(dev, classes=classes, min_area=3)
+    a, b = seg.vectorize(comps, classes=classes), seg.vectorize(comps.mask, classes=classes)
+    for n in ARRAYS:
+        k = {"run_start": 0, "run_obj": 0, "ring_offset": 2, "xy": 3}.get(n, 2)
+        cnt = int(b.totals[k].item()) + (1 if n == "ring_offset" else 0)
+        assert torch.equal(getattr(a, n)[:cnt], getattr(b, n)[:cnt]), n
+    assert torch.equal(a.totals, b.totals) and int(a.totals[2].item()) < int(vec.totals[2].item())
+    with pytest.raises(ValueError):
+        seg.vectorize(dev, max_edges=0)
+    with pytest.raises(ValueError):
+        seg.vectorize(dev.to(torch.int32))
+
+
+def test_segmenter_vectors():
+    """Segmenter(model, clean=..., vectors=True): pred.vectors is vectorize(pred.mask); without vectors= nothing changes"""
+    import image_segmentation_amd as seg
+    from oracle.fill import fill, fill_module
+    from oracle import resize_ref, unet_ref
+    sizes, T = [(40, 56), (33, 61)], 64
+    images = [fill((3,) + s, 70 + i, 0, 1) for i, s in enumerate(sizes)]
+    r = unet_ref.unet(3, 4)
+    fill_module(r, 1000)
+    Xb, _ = resize_ref.process_batch_forward(images, T)
+    with torch.no_grad():
+        r.train()
+        for _ in range(20):
+            r(Xb)
+        r.eval()
+        r.output.bias -= r(Xb).mean(dim=(0, 2, 3))
+    m = seg.unet(3, 4)
+    m.load_state_dict(r.state_dict())
+    m.cuda().eval()
+    same = lambda a, b: (a is None and b is None) or torch.equal(a, b)
+    for clean in (None, dict(min_area=6)):
+        plain = seg.Segmenter(m, target_size=T, clean=clean)(images)
+        kw = dict(connectivity=8, classes=(1, 2, 3), max_edges=9000)
+        for vectors, preds in ((True, seg.Segmenter(m, target_size=T, clean=clean, vectors=True)(images)),
+                               (kw, seg.predict(m, images, target_size=T, clean=clean, vectors=kw))):
+            for p, q in zip(preds, plain):
+                assert same(p.mask, q.mask) and same(p.color, q.color) and same(p.counts, q.counts) and same(p.raw_mask, q.raw_mask)
+                assert q.vectors is None and p.meta == q.meta
+                want = seg.vectorize(p.mask, **({} if vectors is True else vectors))
+                assert torch.equal(p.vectors.totals, want.totals) and p.vectors.size == tuple(p.mask.shape)
+                runs, E, R, V = (int(v) for v in want.totals.cpu())
+                assert torch.equal(p.vectors.run_start[:min(runs, want.run_start.shape[0])], want.run_start[:min(runs, want.run_start.shape[0])])
+                if vectors is True:                 # the default capacities: a random-weight net's mask may exceed them
+                    assert p.vectors.max_edges == seg.default_capacities(*p.mask.shape)[1] and (R >= 0) == (E <= p.vectors.max_edges)
+                    continue
+                assert p.vectors.complete and R > 1 and p.vectors.connectivity == 8
+                for n, cnt in (("run_start", runs), ("run_obj", runs), ("ring_obj", R), ("ring_head", R), ("ring_len", R),
+                               ("ring_area2", R), ("ring_offset", R + 1), ("xy", V)):
+                    assert torch.equal(getattr(p.vectors, n)[:cnt], getattr(want, n)[:cnt]), n
+                # and the restatement on the mask the device produced
+                lab = VR.vectorize(__import__("components_reference").label(p.mask.cpu().numpy(), p.vectors.connectivity,
+                                                                            None if vectors is True else (1, 2, 3))[0],
+                                   p.vectors.connectivity)
+                assert lab["totals"].tolist() == [runs, E, R, V] and np.array_equal(p.vectors.xy[:V].cpu().numpy(), lab["xy"])
+
+
+def test_predict_tool_writes_coco(tmp_path):
+    """tools/predict.py --coco: one file for all inputs, whose annotations describe the masks the same run wrote"""
+    import json
+    import subprocess
+    from PIL import Image
+    import image_segmentation_amd as seg
+    from oracle.fill import fill, fill_module
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    m = seg.unet(3, 4)
+    fill_module(m, 1000)
+    torch.save({"model_state_dict": m.state_dict()}, tmp_path / "w.pt")
+    paths = []
+    for i, (h, w) in enumerate(((40, 56), (33, 61))):
+        img = (fill((h, w, 3), 70 + i, 0, 1).numpy() * 255).astype(np.uint8)
+        paths.append(str(tmp_path / f"im{i}.png"))
+        Image.fromarray(img, "RGB").save(paths[-1])
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "predict.py"), "--checkpoint", str(tmp_path / "w.pt"), "--size", "64",
+                        "--out", str(out), "--min-area", "4", "--coco", str(tmp_path / "c.json"), "--coco-categories", "1=cat,3=edge", *paths],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    coco = json.load(open(tmp_path / "c.json"))
+    assert coco["categories"] == [{"id": 1, "name": "cat"}, {"id": 3, "name": "edge"}]
+    assert [(im["id"], im["file_name"], im["height"], im["width"]) for im in coco["images"]] == [(1, "im0.png", 40, 56), (2, "im1.png", 33, 61)]
+    assert [a["id"] for a in coco["annotations"]] == list(range(1, len(coco["annotations"]) + 1))
+    for im in coco["images"]:
+        mask = np.asarray(Image.open(out / (im["file_name"][:-4] + "_mask.png")))
+        anns = [a for a in coco["annotations"] if a["image_id"] == im["id"]]
+        assert {a["category_id"] for a in anns} <= {1, 3}
+        assert sum(a["area"] for a in anns) == int(((mask == 1) | (mask == 3)).sum())
+        paint = np.zeros(mask.shape, bool)
+        for a in anns:                                                     # every annotation decodes to pixels of its class
+            if a["iscrowd"]:
+                part = VR.rle_decode(a["segmentation"])
+            else:
+                part = VR.fill_even_odd([np.asarray(p).reshape(-1, 2) for p in a["segmentation"]], *mask.shape)
+            assert part.sum() == a["area"] and (mask[part] == a["category_id"]).all() and not (paint & part).any()
+            paint |= part
+        assert np.array_equal(paint, (mask == 1) | (mask == 3))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, tta, tiles, calib, distill, hardloss, lovasz, optim)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -858,6 +858,99 @@ def components():
     print(f"components clock probe: median {clk['median_ghz']} GHz; written to {path}")
 
 
+def vectors():
+    """Mask vectorisation through the C ABI (csrc/vectors.hip): segk_vec_runs and segk_vec_rings on the labels of
+    segk_cc_label (connectivity 4, every class labelled) at 256 x 256, 1024 x 1024 and 3000 x 4000 -- smooth blobs (the realistic
+    case) and noise (half the pixels one of three classes: a ring every few pixels).  max_edges is the mask's own edge count
+    rounded up to a multiple of 4096 (read once, before the timing), so the round count is the one that mask needs.  Beside each
+    line: `mask.cpu()` alone at that size -- the floor of any host route.  Device-event times, warmed, seven rounds: median and
+    min..max; mask.cpu() by the host clock around a synchronised copy.  Written to profiles/vectors_kbench.txt (or --out)."""
+    import time
+    from image_segmentation_amd.components import ws_ints as cc_ws
+    from image_segmentation_amd.vectors import ws_ints as vec_ws
+    st = ops._stream()
+    i32 = dict(dtype=torch.int32, device="cuda")
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    def blobs(H, W):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        m = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+        for c, (cy, cx, ry, rx) in ((1, (0.35, 0.3, 0.25, 0.2)), (2, (0.65, 0.7, 0.22, 0.25))):
+            d = ((yy - cy * H) / (ry * H)) ** 2 + ((xx - cx * W) / (rx * W)) ** 2
+            m[d <= 1.0] = c
+            m[(d > 1.0) & (d <= 1.25)] = 3
+        return m
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+    say(f"vectors: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz")
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None       # one size, e.g. 3000x4000 (a profiler run)
+    for H, W in ((256, 256), (1024, 1024), (3000, 4000)):
+        if only is not None and only != f"{H}x{W}":
+            continue
+        iters = 50 if H * W <= 1 << 20 else 5
+        for kind in ("blobs", "noise"):
+            if kind == "blobs":
+                m = blobs(H, W)
+            else:
+                fg = torch.rand((H, W), generator=g, device="cuda") < 0.5
+                m = torch.where(fg, torch.randint(1, 4, (H, W), generator=g, device="cuda", dtype=torch.uint8), torch.zeros((), dtype=torch.uint8, device="cuda"))
+            labels, num, totals = torch.empty((H, W), **i32), torch.empty(1, **i32), torch.empty(4, **i32)
+            cap = 1024
+            r, box = torch.empty((3, cap), **i32), torch.empty((cap, 4), **i32)
+            ws = torch.empty(cc_ws(H, W), **i32)
+            f_l = lambda: _lib.call("segk_cc_label", m.data_ptr(), labels.data_ptr(), num.data_ptr(), r[0].data_ptr(), r[1].data_ptr(),
+                                    box.data_ptr(), r[2].data_ptr(), ws.data_ptr(), H, W, 4, 0b1110, cap, st)
+            f_l()
+            one = torch.empty(8, **i32)
+            wsv = torch.empty(vec_ws(H, W, 1), **i32)                   # a first call with max_edges = 1 only counts the edges
+            _lib.call("segk_vec_rings", labels.data_ptr(), one.data_ptr(), one.data_ptr(), one.data_ptr(), one.data_ptr(), one.data_ptr(),
+                      one.data_ptr(), totals.data_ptr(), wsv.data_ptr(), H, W, 4, 1, 1, 1, st)
+            E = int(totals[1].item())
+            me = max(4096, (E + 4095) // 4096 * 4096)
+            mr, mg = min(H * W, me + W), me // 4
+            del ws, wsv
+            wsv = torch.empty(vec_ws(H, W, me), **i32)
+            runs, rings, xy = torch.empty((2, mr), **i32), torch.empty((3, mg), **i32), torch.empty((me, 2), **i32)
+            area2, off = torch.empty(mg, dtype=torch.int64, device="cuda"), torch.empty(mg + 1, **i32)
+            f_r = lambda: _lib.call("segk_vec_runs", labels.data_ptr(), runs[0].data_ptr(), runs[1].data_ptr(), totals.data_ptr(),
+                                    wsv.data_ptr(), H, W, mr, st)
+            f_g = lambda: _lib.call("segk_vec_rings", labels.data_ptr(), rings[0].data_ptr(), rings[1].data_ptr(), rings[2].data_ptr(),
+                                    area2.data_ptr(), off.data_ptr(), xy.data_ptr(), totals.data_ptr(), wsv.data_ptr(), H, W, 4, me, mg, me, st)
+            f_r(); f_g()
+            tot = totals.tolist()
+            jumps = 1
+            while (1 << (jumps - 1)) < me:
+                jumps += 1
+            tr, tg = rounds(f_r, iters), rounds(f_g, iters)
+            cpu = []
+            for _ in range(7):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                m.cpu()
+                cpu.append((time.perf_counter() - t0) * 1e6)
+            cpu.sort()
+            say(f"vectors {H}x{W} {kind:5s} K={int(num.item()):8d} runs={tot[0]:9d} edges={tot[1]:9d} rings={tot[2]:8d} vertices={tot[3]:9d} "
+                f"max_edges={me:9d} ({2 * jumps} jump launches of {13 + 2 * jumps})")
+            say(f"    segk_vec_runs {tr[0]:10.1f} us [{tr[1]:.1f}..{tr[2]:.1f}]   segk_vec_rings {tg[0]:10.1f} us [{tg[1]:.1f}..{tg[2]:.1f}]   "
+                f"mask.cpu() {cpu[3]:10.1f} us [{cpu[0]:.1f}..{cpu[-1]:.1f}]   rings / mask.cpu() = {tg[0] / cpu[3]:6.2f}")
+            del wsv, runs, rings, xy, area2, off
+    path = os.path.join(ROOT, "profiles", "vectors_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def tta():
     """Multi-view prediction through the C ABI (csrc/predict.hip): segk_predict_merge -- mask, colour, class
     counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
@@ -1192,6 +1285,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "components":
         components()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "vectors":
+        vectors()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "perturb":
         perturb()

@@ -18,7 +18,11 @@ and blends the tiles' outputs on the device (--tile-window triang
 reflect|zero fills a tile beyond an image smaller than itself, --merge as above); --batch-size then counts tiles per forward.
 It does not combine with --tta, --sizes or several --checkpoint; --confidence works with it.
 --temperature T divides every model's logits by T before the prediction kernels run (tools/calibrate.py fits
-it): the confidence maps become the calibrated ones.  Not for --model prompt, whose outputs are probabilities."""
+it): the confidence maps become the calibrated ones.  Not for --model prompt, whose outputs are probabilities.
+--coco FILE.json writes ONE COCO-style file for all inputs (images, annotations, categories): every connected component of a
+final (cleaned) mask whose class has a category becomes an annotation with bbox, area and a polygon list -- or, when it has a
+hole, its uncompressed RLE -- built on the device.  --coco-categories 1=cat,2=dog maps classes to category
+ids (the class number) and names; the default is every class but 0 under its class name."""
 import argparse
 import os
 import sys
@@ -56,6 +60,8 @@ def main():
     ap.add_argument("--connectivity", type=int, choices=[4, 8], default=4)
     ap.add_argument("--max-components", type=int, default=1024, help="components reported per image in --boxes")
     ap.add_argument("--boxes", metavar="FILE.json", help="write the kept components' class, area and box per image")
+    ap.add_argument("--coco", metavar="FILE.json", help="write the components of all masks as COCO annotations (polygons / RLE)")
+    ap.add_argument("--coco-categories", default=None, metavar="C=NAME,...", help="classes that become categories, with their names")
     ap.add_argument("images", nargs="+", metavar="IMG")
     args = ap.parse_args()
     try:
@@ -96,6 +102,18 @@ def main():
     if args.min_area > 0 or keep is not False or args.boxes:
         clean = dict(connectivity=args.connectivity, min_area=args.min_area, keep_largest=keep, max_components=args.max_components)
 
+    categories = None
+    if args.coco_categories is not None:
+        if not args.coco:
+            ap.error("--coco-categories needs --coco FILE")
+        try:
+            categories = {int(c): n for c, n in (item.split("=", 1) for item in args.coco_categories.split(","))}
+        except ValueError:
+            ap.error("--coco-categories takes CLASS=NAME pairs separated by commas")
+        if not categories or any(not 0 <= c < args.classes or not n for c, n in categories.items()):
+            ap.error(f"--coco-categories: classes in 0..{args.classes - 1}, each with a name")
+    vectors = dict(connectivity=args.connectivity, max_components=args.max_components) if args.coco else None
+
     import json
     import numpy as np
     from PIL import Image
@@ -114,7 +132,7 @@ def main():
     try:
         segmenter = seg.Segmenter(models if tta is not None else models[0], target_size=args.size, interpolation=args.interpolation,
                                   palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta, tiles=tiles,
-                                  temperature=args.temperature)
+                                  temperature=args.temperature, vectors=vectors)
     except ValueError as e:
         ap.error(str(e))
     if args.confidence:
@@ -122,6 +140,9 @@ def main():
     boxes = {}
     os.makedirs(args.out, exist_ok=True)
     names = seg.CLASS_NAMES["prompt_model" if clicks else "standard"]
+    if categories is None:
+        categories = {c: str(names.get(c, c)) for c in range(1, args.classes)}
+    coco = {"images": [], "annotations": [], "categories": [{"id": c, "name": n} for c, n in sorted(categories.items())]}
     for i in range(0, len(args.images), args.batch_size):
         paths = args.images[i:i + args.batch_size]
         preds = segmenter([np.asarray(Image.open(p).convert("RGB")) for p in paths],
@@ -136,6 +157,15 @@ def main():
                 Image.fromarray(pred.confidence.cpu().numpy(), "L").save(os.path.join(args.confidence, name))
             counts = pred.counts.tolist()
             print(p, " ".join(f"{names.get(k, k)}={c}" for k, c in enumerate(counts)))
+            if args.coco:
+                vec = pred.vectors
+                if not vec.complete:                 # more boundary than the default capacities hold: again, sized by the counts
+                    edges, k = int(vec.totals[1].item()), int(vec.num.item())
+                    vec = seg.vectorize(pred.mask, connectivity=args.connectivity, max_components=max(k, 1), max_edges=max(edges, 1))
+                image_id = len(coco["images"]) + 1
+                H, W = vec.size
+                coco["images"].append({"id": image_id, "file_name": os.path.basename(p), "height": H, "width": W})
+                coco["annotations"] += vec.to_coco(image_id, {c: c for c in categories}, first_id=len(coco["annotations"]) + 1)
             if args.boxes:
                 c = pred.components
                 k = min(c.n, args.max_components)
@@ -145,6 +175,9 @@ def main():
     if args.boxes:
         with open(args.boxes, "w") as f:
             json.dump(boxes, f, indent=1)
+    if args.coco:
+        with open(args.coco, "w") as f:
+            json.dump(coco, f)
 
 
 if __name__ == "__main__":
