@@ -19,6 +19,8 @@ from .tta import TTA, view_table, view_order, VIEW_DESC                         
 from .tiles import Tiles, tile_axis, tile_plan                                                                # noqa: F401
 from .components import components, Components, Clean, mask_finish                                          # noqa: F401
 from .vectors import vectorize, Vectors, default_capacities                                                 # noqa: F401
+from .raster import (Shape, rasterize, rasterize_batch, shapes_from_coco, shapes_from_vectors, rle_to_string,   # noqa: F401
+                     rle_from_string, raster_plan)
 from .calibration import (Reliability, reliability, TemperatureFit, fit_temperature, refine_temperature,            # noqa: F401
                           default_temperatures, inverse_temperatures, fit_from_counts)
 from .distill import Teacher, TeacherViews, DistillLoss, teacher_table, TEACHER_DESC                                 # noqa: F401

@@ -128,10 +128,11 @@ class Vectors:
             counts = [0] + counts
         return {"size": [H, W], "counts": [int(c) for c in counts]}
 
-    def to_coco(self, image_id, category_of_class, first_id=1):
+    def to_coco(self, image_id, category_of_class, first_id=1, compressed=False):
         """COCO annotation dicts of the objects whose class has an entry in category_of_class (others -- background -- are
         skipped): bbox [x, y, w, h] and area from the component rows, segmentation a polygon list when the object has no hole
-        ring, else its uncompressed RLE (iscrowd 1, as COCO reads an RLE)."""
+        ring, else its uncompressed RLE (iscrowd 1, as COCO reads an RLE); compressed=True writes the RLE counts as COCO's
+        compressed string (raster.rle_to_string)."""
         rings, verts = self._need_rings("to_coco")
         k = self._h["num"]
         if k > self.cls.shape[0]:
@@ -150,6 +151,9 @@ class Vectors:
             mine = of_obj.get(o, [])
             if any(ra[i] < 0 for i in mine):
                 seg, crowd = self.coco_rle(o), 1
+                if compressed:
+                    from .raster import rle_to_string
+                    seg["counts"] = rle_to_string(seg["counts"])
             else:
                 seg, crowd = [[int(v) for v in xy[off[i]:off[i + 1]].reshape(-1)] for i in mine], 0
             y0, x0, y1, x1 = (int(v) for v in box[o - 1])

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 325
-#define SEGK_ENTRY_COUNT 110
+#define SEGK_ABI_VERSION 326
+#define SEGK_ENTRY_COUNT 111
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -454,6 +454,38 @@ int segk_vec_runs(const int32_t* obj, int32_t* run_start, int32_t* run_obj, int3
 int segk_vec_rings(const int32_t* obj, int32_t* ring_obj, int32_t* ring_head, int32_t* ring_len, int64_t* ring_area2,
                    int32_t* ring_offset, int32_t* xy, int32_t* totals, int32_t* ws, int H, int W, int connectivity,
                    int max_edges, int max_rings, int max_vertices, segk_stream_t s);
+
+/* ---- label rasterisation: polygons and run-length codes -> uint8 label maps (the reference has no such code:
+ * this replaces a host rasteriser plus one upload per image).  Integer arithmetic only: the result is unique and bit-stable.
+ * One launch serves a ragged batch, one workgroup per tile of SEGK_RAST_TILE_H rows x SEGK_RAST_TILE_W columns; the host
+ * builds every table and all of them are DEVICE pointers, so the entry validates the arguments only and the kernel clamps
+ * every index it reads from a table to its argument.  No workgroup waits for another; no atomics on global memory. */
+#define SEGK_RAST_TILE_H 64
+#define SEGK_RAST_TILE_W 256
+#define SEGK_RAST_MAX_SIDE 8192
+#define SEGK_RAST_POLYGON 0          /* begin / end: rows of edges; inside = odd number of counting crossings (even-odd) */
+#define SEGK_RAST_RLE 1              /* begin / end: entries of run_start; inside = odd run index */
+typedef struct segk_rast_shape {     /* one shape; 32 bytes */
+  int32_t kind;                      /* SEGK_RAST_POLYGON | SEGK_RAST_RLE */
+  int32_t value;                     /* 0..255, painted where the shape is inside */
+  int32_t begin, end;                /* its rows of edges, or its entries of run_start */
+  int32_t H;                         /* height of its image: t = x*H + y */
+  int32_t pad_[3];
+} segk_rast_shape;
+typedef struct segk_rast_tile {      /* one tile; 32 bytes, 8-byte aligned */
+  int64_t out_off;                   /* byte offset of the image (uint8 [H][W], dense) in out */
+  int32_t H, W;                      /* 1..SEGK_RAST_MAX_SIDE */
+  int32_t y0, x0;                    /* first row and column of the tile */
+  int32_t list0, list1;              /* its entries of shape_list */
+} segk_rast_tile;
+/* every pixel of every tile = fill, then the shapes shape_list[list0:list1) of the tile in that order, a
+ * later shape over an earlier one.  edges int32 [n_edges][4] = (X0, Y0, X1, Y1) with 8 fractional bits, |X| <= 2^22, 16-byte
+ * aligned; run_start int32 [n_runs] cumulative run starts, ascending inside a shape.  The tiles of an image must cover it
+ * exactly once for its bytes to be written once; a tile record that does not lie inside out[0, out_bytes) writes nothing.
+ * n_tiles >= 1, out_bytes >= n_tiles, 0 <= fill <= 255; the table lengths may be 0 but no pointer may be NULL. */
+int segk_raster_labels(const segk_rast_tile* tiles, int n_tiles, const segk_rast_shape* shapes, int n_shapes,
+                       const int32_t* shape_list, int list_len, const int32_t* edges, int n_edges, const int32_t* run_start,
+                       int n_runs, uint8_t* out, long out_bytes, int fill, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

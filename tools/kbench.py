@@ -951,6 +951,111 @@ def vectors():
     print(f"written to {path}")
 
 
+def raster():
+    """Label rasterisation (csrc/raster.hip): segk_raster_labels on (a) the polygons seg.vectorize finds in a
+    blob mask at 256 x 256, batch 32, (b) the same at 3000 x 4000 (12 MP), batch 4, (c) 200 random triangles per image at
+    512 x 512, batch 32.  Per workload: the launch alone (tables already on the device; device events, warmed, seven rounds:
+    median and min..max), the whole seg.rasterize_batch call (host plan, pinned upload, launch; host clock, synchronised), the
+    floor (the output bytes at the device-to-device copy rate measured beside it) and the host path it replaces (PIL
+    ImageDraw.polygon per shape plus one upload per image; timing only: PIL's fill rule is not the one of 3.18).  Written to
+    profiles/raster_kbench.txt (or --out)."""
+    import time
+    import numpy as np
+    from PIL import Image, ImageDraw
+    import image_segmentation_amd as seg
+    from image_segmentation_amd import raster as R
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    def host_rounds(fn, n=5):
+        t = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            t.append((time.perf_counter() - t0) * 1e6)
+        t.sort()
+        return t[len(t) // 2], t[0], t[-1]
+
+    def blobs(H, W):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        m = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+        for c, (cy, cx, ry, rx) in ((1, (0.35, 0.3, 0.25, 0.2)), (2, (0.65, 0.7, 0.22, 0.25))):
+            d = ((yy - cy * H) / (ry * H)) ** 2 + ((xx - cx * W) / (rx * W)) ** 2
+            m[d <= 1.0] = c
+            m[(d > 1.0) & (d <= 1.25)] = 3
+        return m
+
+    def blob_shapes(H, W):
+        m = blobs(H, W)
+        vec = seg.vectorize(m, classes=(1, 2, 3), max_edges=4 * (H + W) * 8)
+        shapes = seg.shapes_from_vectors(vec)
+        assert torch.equal(seg.rasterize(shapes, (H, W)), m)                # the loop closes on this mask
+        return shapes
+
+    def triangles(H, W, n, seed):
+        rng = np.random.default_rng(seed)
+        return [seg.Shape(rings=[rng.uniform(-0.1, 1.1, (3, 2)) * (W, H)], value=1 + k % 7) for k in range(n)]
+
+    say(f"raster: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz, tile {R.TILE_H} x {R.TILE_W}")
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    work = (("blobs256", 256, 256, 32, 50), ("blobs12mp", 3000, 4000, 4, 5), ("triangles200", 512, 512, 32, 20))
+    for name, H, W, B, iters in work:
+        if only is not None and only != name:
+            continue
+        if name == "triangles200":
+            per_image = [triangles(H, W, 200, 10 + b) for b in range(B)]
+        else:
+            per_image = [blob_shapes(H, W)] * B
+        sizes = [(H, W)] * B
+        plan = seg.raster_plan(per_image, sizes)
+        out = torch.empty(plan["out_bytes"], dtype=torch.uint8, device=dev)
+        other = torch.empty_like(out)
+        blob, ptr = R._upload([plan["tiles"], plan["shapes"], plan["shape_list"], plan["edges"], plan["run_start"]], dev)
+        st = ops._stream()
+        f_k = lambda: _lib.call("segk_raster_labels", ptr[0], len(plan["tiles"]), ptr[1], len(plan["shapes"]), ptr[2], len(plan["shape_list"]),
+                                ptr[3], len(plan["edges"]), ptr[4], len(plan["run_start"]), out.data_ptr(), out.numel(), 0, st)
+        tk = rounds(f_k, iters)
+        tc = rounds(lambda: other.copy_(out), iters)
+        rate = 2 * out.numel() / tc[0] / 1e6                                # TB/s of the copy (read + write)
+        floor = out.numel() / (rate * 1e6)                                  # us to write the output bytes at that rate
+        tw = host_rounds(lambda: seg.rasterize_batch(per_image, sizes))
+        polys = [[(s.value, [tuple(v) for v in (r / 256.0).tolist()]) for s in shp for r in s.rings] for shp in per_image]
+
+        def pil():
+            for pl in polys:
+                im = Image.new("L", (W, H), 0)
+                d = ImageDraw.Draw(im)
+                for v, xy in pl:
+                    d.polygon(xy, fill=v)
+                torch.from_numpy(np.array(im)).to(dev)
+        tp = host_rounds(pil, 3)
+        listed = len(plan["shape_list"]) / len(plan["tiles"])
+        say(f"raster {name:12s} {B} x {H}x{W}  shapes/image={len(per_image[0])} edges={len(plan['edges'])} tiles={len(plan['tiles'])} "
+            f"shapes/tile={listed:.1f} out={out.numel() / 1e6:.2f} MB")
+        say(f"    segk_raster_labels {tk[0]:10.1f} us [{tk[1]:.1f}..{tk[2]:.1f}]   floor (copy {rate:.2f} TB/s) {floor:9.1f} us   "
+            f"kernel / floor = {tk[0] / floor:6.2f}")
+        say(f"    rasterize_batch (plan + upload + launch) {tw[0]:10.1f} us [{tw[1]:.1f}..{tw[2]:.1f}]   PIL polygon + upload "
+            f"{tp[0]:10.1f} us [{tp[1]:.1f}..{tp[2]:.1f}]   PIL / rasterize_batch = {tp[0] / tw[0]:6.2f}")
+        del out, other, blob
+    path = os.path.join(ROOT, "profiles", "raster_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def tta():
     """Multi-view prediction through the C ABI (csrc/predict.hip): segk_predict_merge -- mask, colour, class
     counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
@@ -1288,6 +1393,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "vectors":
         vectors()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "raster":
+        raster()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "perturb":
         perturb()
