@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 326
-#define SEGK_ENTRY_COUNT 111
+#define SEGK_ABI_VERSION 327
+#define SEGK_ENTRY_COUNT 113
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -486,6 +486,52 @@ typedef struct segk_rast_tile {      /* one tile; 32 bytes, 8-byte aligned */
 int segk_raster_labels(const segk_rast_tile* tiles, int n_tiles, const segk_rast_shape* shapes, int n_shapes,
                        const int32_t* shape_list, int list_len, const int32_t* edges, int n_edges, const int32_t* run_start,
                        int n_runs, uint8_t* out, long out_bytes, int fill, segk_stream_t s);
+
+/* ---- object-level evaluation: overlap table, IoU > 0.5 matching, Panoptic Quality statistics (the reference
+ * has no such code: this replaces a mask.cpu() + labelling + np.unique of combined ids).  Integer arithmetic only, integer
+ * atomics only, no float on the device: the result is unique and bit-stable.  No launch waits for another workgroup, the host
+ * reads no count back, every device loop is bounded by an argument.
+ *
+ * A segment id is 0 (nothing), 1..max_components (a labelled component: row id - 1 of its cls array) or max_components + 1 + c
+ * (stuff class c); a target segment may also be -1 (void).  Per-segment arrays hold max_components + 8 rows, row r = segment
+ * r + 1; the rows in use are 0..num-1 and max_components..max_components+7, the rows between are never read or written.
+ *
+ * Workspace of segk_pq_pairs: SEGK_PQ_WS_INTS(H, W, max_pairs, max_components) 32-bit words, 16-byte aligned, uninitialised,
+ * scratch of one call (segk_pq_match needs none; max_components is part of the macro so that it may).  In words, with
+ * S = SEGK_PQ_SLOTS(max_pairs) and B = ceil(H*W / 32): 16 (word 0: the overflow flag) | keys uint64 [S] | counts [S] | first
+ * pixels [S] | leader bitmap [R4(B)] | leaders before each bitmap word [R4(B)] | leaders per chunk [R4(ceil(B / 1024))]. */
+#define SEGK_PQ_BLOCK_PIXELS 2048    /* pixels one workgroup of the insert pass collapses */
+#define SEGK_PQ_LDS_SLOTS 256        /* slots of its LDS table */
+#define SEGK_PQ_CHUNK 1024           /* bitmap words (32 pixels each) one workgroup counts and scans */
+#define SEGK_PQ_MIN_SLOTS 1024
+#define SEGK_PQ_STAT_COLS 16
+#define SEGK_PQ_MAX_PAIRS (1L << 28)
+#define SEGK_PQ_SLOTS(MP) (2L * (long)(MP) + SEGK_PQ_MIN_SLOTS)
+#define SEGK_PQ_WS_INTS(H, W, MP, MC)                                                                            \
+  (16L + 4L * SEGK_PQ_SLOTS(MP) + 2L * SEGK_VEC_R4(((long)(H) * (long)(W) + 31L) / 32L) +                       \
+   SEGK_VEC_R4((((long)(H) * (long)(W) + 31L) / 32L + SEGK_PQ_CHUNK - 1L) / SEGK_PQ_CHUNK) + 0L * (long)(MC))
+/* DESIGN.md 3.19 "segments", "void", "pair table": pred / target uint8 [H,W] masks with their label maps int32 [H,W] and
+ * component counts num[1] (segk_cc_label with the thing classes, or instance ids given by the caller; a label outside 1..num
+ * counts as 0).  A pixel with label 0 whose value is a class of stuff_mask belongs to that stuff segment.  A target pixel whose
+ * value is ignore_index (-1: none) or >= 8 is void.  pair_g / pair_p / pair_n [max_pairs]: every distinct (target segment,
+ * predicted segment) with its pixel count, in ascending order of the pair's first pixel; totals[0] = P.  If P > max_pairs or
+ * either num > max_components: totals[0..3] = -1 and no pair array is touched.  Nothing at or past P is written.
+ * H*W <= SEGK_CC_MAX_PIXELS, 1 <= max_components <= 2^24, 1 <= max_pairs <= SEGK_PQ_MAX_PAIRS.  The inputs are only read. */
+int segk_pq_pairs(const uint8_t* pred, const int32_t* pred_labels, const int32_t* pred_num, const uint8_t* target,
+                  const int32_t* target_labels, const int32_t* target_num, int32_t* pair_g, int32_t* pair_p, int32_t* pair_n,
+                  int32_t* totals, int32_t* ws, int H, int W, int stuff_mask, int ignore_index, int max_components,
+                  int max_pairs, segk_stream_t s);
+/* DESIGN.md 3.19 "areas", "match", "statistics", "totals": from the pair table of segk_pq_pairs (same totals, capacities and
+ * num words) and the cls arrays [max_components] of both labellings.  area_g / match_g / inter_g / union_g and area_p / void_p
+ * / match_p [max_components + 8]: match is the matched segment id of the other side (0: none), inter and union those of the
+ * match (0: none).  totals[1..3] = target segments, predicted segments, matches (segments with area > 0).  stats int64 [8][16],
+ * 8-byte aligned, is ADDED to and never zeroed: row = class, columns TP, FP, FN, sum of floor(inter 2^32 / union), TP at
+ * IoU >= 0.50 + 0.05 k (k = 0..9), target segments, predicted segments.  A segment whose class is outside 0..7 matches nothing
+ * and is counted nowhere.  Returns at once, touching nothing, when totals[0] < 0. */
+int segk_pq_match(const int32_t* pair_g, const int32_t* pair_p, const int32_t* pair_n, int32_t* totals, const int32_t* pred_cls,
+                  const int32_t* pred_num, const int32_t* target_cls, const int32_t* target_num, int32_t* area_g,
+                  int32_t* match_g, int32_t* inter_g, int32_t* union_g, int32_t* area_p, int32_t* void_p, int32_t* match_p,
+                  int64_t* stats, int max_components, int max_pairs, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

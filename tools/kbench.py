@@ -1056,6 +1056,137 @@ def raster():
     print(f"written to {path}")
 
 
+def pq():
+    """Object-level evaluation through the C ABI (csrc/panoptic.hip): segk_pq_pairs and segk_pq_match on the labels
+    of segk_cc_label (connectivity 4, things 1..3, stuff 0) at 256 x 256 and 3000 x 4000 -- smooth blobs against the same blobs
+    shifted by (1, 2) (the realistic case) and two independent noise masks (half the pixels one of three classes: millions of
+    objects and pairs at 12 MP).  max_components and max_pairs are the masks' own counts rounded up to a multiple of 4096 (read
+    once, before the timing).  Per entry: device-event time, warmed, seven rounds: median and min..max; the bytes each pass must
+    move (pairs: 10 B per pixel for the insert pass plus 16 B per table slot three times; match: 12 B per pair twice plus 28 B per
+    segment row twice) over the device-to-device copy rate of a 512 MB buffer measured beside it (the floor); the two labellings, for scale; and the
+    host path the entries replace -- both masks .cpu(), scipy.ndimage.label per thing class, np.unique of the combined ids with
+    counts -- by the host clock.  Written to profiles/pq_kbench.txt (or --out)."""
+    import time
+    import numpy as np
+    from scipy import ndimage
+    from image_segmentation_amd.components import ws_ints as cc_ws
+    from image_segmentation_amd.panoptic import ws_ints as pq_ws, MIN_SLOTS
+    st = ops._stream()
+    i32 = dict(dtype=torch.int32, device="cuda")
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    def blobs(H, W):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        m = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+        for c, (cy, cx, ry, rx) in ((1, (0.35, 0.3, 0.25, 0.2)), (2, (0.65, 0.7, 0.22, 0.25))):
+            d = ((yy - cy * H) / (ry * H)) ** 2 + ((xx - cx * W) / (rx * W)) ** 2
+            m[d <= 1.0] = c
+            m[(d > 1.0) & (d <= 1.25)] = 3
+        return m
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def noise(H, W):
+        fg = torch.rand((H, W), generator=g, device="cuda") < 0.5
+        return torch.where(fg, torch.randint(1, 4, (H, W), generator=g, device="cuda", dtype=torch.uint8), torch.zeros((), dtype=torch.uint8, device="cuda"))
+
+    up4096 = lambda n: max(4096, (n + 4095) // 4096 * 4096)
+    say(f"pq: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz")
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None       # one size, e.g. 3000x4000
+    for H, W in ((256, 256), (3000, 4000)):
+        if only is not None and only != f"{H}x{W}":
+            continue
+        hw = H * W
+        iters = 50 if hw <= 1 << 20 else 5
+        for kind in ("blobs", "noise"):
+            if kind == "blobs":
+                tgt = blobs(H, W)
+                pred = torch.roll(tgt, (1, 2), (0, 1)).contiguous()
+            else:
+                pred, tgt = noise(H, W), noise(H, W)
+            labels, num = torch.empty((2, H, W), **i32), torch.empty((2, 4), **i32)
+            ws = torch.empty(cc_ws(H, W), **i32)
+
+            def label(side, mask, r, box, cap):
+                _lib.call("segk_cc_label", mask.data_ptr(), labels[side].data_ptr(), num[side].data_ptr(), r[0].data_ptr(), r[1].data_ptr(),
+                          box.data_ptr(), r[2].data_ptr(), ws.data_ptr(), H, W, 4, 0b1110, cap, st)
+            r1, b1 = torch.empty((3, 1), **i32), torch.empty((1, 4), **i32)
+            label(0, pred, r1, b1, 1); label(1, tgt, r1, b1, 1)       # a first call with one row only counts the components
+            cap = up4096(int(num[:, 0].max().item()))
+            rp, rg = torch.empty((3, cap), **i32), torch.empty((3, cap), **i32)
+            bp, bg = torch.empty((cap, 4), **i32), torch.empty((cap, 4), **i32)
+            f_l = lambda: (label(0, pred, rp, bp, cap), label(1, tgt, rg, bg, cap))
+            f_l()
+            totals = torch.empty(4, **i32)
+            seg_rows = torch.empty((7, cap + 8), **i32)
+            stats = torch.zeros((8, 16), dtype=torch.int64, device="cuda")
+
+            def make(mp):
+                pairs, wsp = torch.empty((3, mp), **i32), torch.empty(pq_ws(H, W, mp, cap), **i32)
+                f_p = lambda: _lib.call("segk_pq_pairs", pred.data_ptr(), labels[0].data_ptr(), num[0].data_ptr(), tgt.data_ptr(),
+                                        labels[1].data_ptr(), num[1].data_ptr(), pairs[0].data_ptr(), pairs[1].data_ptr(), pairs[2].data_ptr(),
+                                        totals.data_ptr(), wsp.data_ptr(), H, W, 1, -1, cap, mp, st)
+                f_m = lambda: _lib.call("segk_pq_match", pairs[0].data_ptr(), pairs[1].data_ptr(), pairs[2].data_ptr(), totals.data_ptr(),
+                                        rp[0].data_ptr(), num[0].data_ptr(), rg[0].data_ptr(), num[1].data_ptr(),
+                                        *(seg_rows[k].data_ptr() for k in range(7)), stats.data_ptr(), cap, mp, st)
+                return pairs, wsp, f_p, f_m
+            pairs, wsp, f_p, f_m = make(hw)                             # P <= H*W always fits: this call only counts the pairs
+            f_p()
+            mp = up4096(int(totals[0].item()))
+            del pairs, wsp
+            pairs, wsp, f_p, f_m = make(mp)
+            f_p(); f_m()
+            tot = totals.tolist()
+            assert tot[0] > 0 and int(pairs[2][:tot[0]].sum().item()) == hw, "the pair table is not lossless"
+            tl, tp, tm = rounds(f_l, iters), rounds(f_p, iters), rounds(f_m, iters)
+            src, dst = torch.empty(1 << 29, dtype=torch.uint8, device="cuda"), torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+            tc = rounds(lambda: dst.copy_(src), 5)                      # 512 MB each way: larger than the last-level cache
+            rate = 2 * src.numel() / tc[0] / 1e6                        # TB/s of the copy (read + write)
+            slots = 2 * mp + MIN_SLOTS
+            bytes_p, bytes_m = 10 * hw + 3 * 16 * slots + 12 * tot[0], 2 * 12 * tot[0] + 2 * 28 * (cap + 8)
+            floor_p, floor_m = bytes_p / (rate * 1e6), bytes_m / (rate * 1e6)
+            del src, dst
+            host = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                a, b = pred.cpu().numpy(), tgt.cpu().numpy()
+                ids, base = [np.zeros((H, W), np.int64), np.zeros((H, W), np.int64)], [0, 0]
+                for side, m in enumerate((a, b)):
+                    for c in (1, 2, 3):
+                        lab, n = ndimage.label(m == c)
+                        ids[side] += np.where(lab > 0, lab + base[side], 0)
+                        base[side] += n
+                    ids[side][(ids[side] == 0) & (m == 0)] = base[side] + 1
+                np.unique(ids[1] * (base[0] + 2) + ids[0], return_counts=True)
+                host.append((time.perf_counter() - t0) * 1e6)
+            host.sort()
+            say(f"pq {H}x{W} {kind:5s} K_pred={int(num[0, 0].item()):8d} K_target={int(num[1, 0].item()):8d} pairs={tot[0]:9d} matches={tot[3]:8d} "
+                f"max_components={cap:8d} max_pairs={mp:9d}")
+            say(f"    segk_pq_pairs {tp[0]:10.1f} us [{tp[1]:.1f}..{tp[2]:.1f}]   floor ({bytes_p / 1e6:.2f} MB at copy {rate:.2f} TB/s) {floor_p:9.1f} us   "
+                f"entry / floor = {tp[0] / floor_p:7.2f}")
+            say(f"    segk_pq_match {tm[0]:10.1f} us [{tm[1]:.1f}..{tm[2]:.1f}]   floor ({bytes_m / 1e6:.2f} MB) {floor_m:9.1f} us   "
+                f"entry / floor = {tm[0] / floor_m:7.2f}")
+            say(f"    two segk_cc_label {tl[0]:10.1f} us [{tl[1]:.1f}..{tl[2]:.1f}]   host path (2 x mask.cpu(), ndimage.label, np.unique) "
+                f"{host[1]:12.1f} us [{host[0]:.1f}..{host[-1]:.1f}]   host / (labels + pairs + match) = {host[1] / (tl[0] + tp[0] + tm[0]):8.2f}")
+            del pairs, wsp, labels, ws, rp, rg, bp, bg, seg_rows
+    path = os.path.join(ROOT, "profiles", "pq_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def tta():
     """Multi-view prediction through the C ABI (csrc/predict.hip): segk_predict_merge -- mask, colour, class
     counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
@@ -1396,6 +1527,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "raster":
         raster()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "pq":
+        pq()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "perturb":
         perturb()
