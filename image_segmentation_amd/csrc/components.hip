@@ -13,22 +13,22 @@
 //                      chains are shortened, the remaining equal neighbours are united with LDS atomicMin, and every pixel's
 //                      tile root leaves as a global linear index (-1: unlabelled).  Also zeroes the accumulators.
 //   cc_border_kernel   one thread per pixel on a tile border: lock-free union with its backward neighbours in other tiles
-//   cc_flatten_kernel  parent[p] = root(p); area at the root (+ run length per run head, summed per workgroup in a small
-//                      LDS table before the atomic); roots per row
-//   cc_scan_kernel     one workgroup: exclusive scan of the H row counts, K
+//   cc_flatten_kernel  parent[p] = root(p); area at the root (+ run_length per run head, summed per workgroup in scan.hpp's
+//                      AddTable before the atomic); roots per row
+//   cc_scan_kernel     one workgroup: scan.hpp's wg_scan of the H row counts, K
 //   cc_rank_kernel     one wave per row: ids 1..K in raster order of the roots, the reported rows, the largest component
 //                      per class (key = area << 32 | ~id: a tie goes to the lowest id)
-//   cc_ids_kernel      labels[p] = id, boxes of the reported components (min / max of runs per workgroup in the LDS table,
-//                      then global atomics filtered by a coherent read)
+//   cc_ids_kernel      labels[p] = id, boxes of the reported components (min / max of runs per workgroup in LDS cells found
+//                      by the same tab_slot, then global atomics filtered by a coherent read)
 //  segk_cc_clean
 //   cc_clean_init_kernel, cc_vote_kernel, cc_apply_kernel
-#include "common.hpp"
+// The run heads, the LDS table, the scan and dev_load are the object kernels' shared ones: scan.hpp.
+#include "scan.hpp"
 #include "segk_internal.h"
 #include "../../include/segk.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int TS = SEGK_CC_TILE_W, TH = SEGK_CC_TILE_H, TP = TS * TH;     // tile width and height, pixels per tile
 constexpr int RW = 8;                                    // rows a wave walks down in the flatten / ids kernels
 constexpr int NC = SEGK_MAX_CLASSES;
@@ -53,7 +53,6 @@ __host__ __device__ inline Ws ws_split(int32_t* ws, int H, int W) {
 }
 
 __device__ __forceinline__ int wg_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ int dev_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- union-find on the tile (LDS) and on the image (global).  find: the chain strictly decreases.  unite: needs no
 // roots -- if a (the larger) was not a root, its former parent `old` still has to meet b, and max(a, b) fell.
@@ -213,35 +212,16 @@ __global__ __launch_bounds__(256) void cc_border_kernel(const uint8_t* __restric
   }
 }
 
-// run heads of a wave's 64 values: a lane starts a run where its value differs from the lane before; returns the run
-// length for a head lane (0 otherwise)
-__device__ __forceinline__ int run_length(int key, int lane) {
-  const int prev = __shfl_up(key, 1);
-  const bool head = lane == 0 || prev != key;
-  const u64 heads = __ballot(head);
-  if (!head) return 0;
-  const u64 upper = lane == 63 ? 0ull : heads >> (lane + 1);
-  return upper ? __ffsll((long long)upper) : 64 - lane;
-}
-
-// a small open table in LDS keyed by component: what a workgroup adds to one component leaves as ONE global atomic per
-// word (a large component would otherwise take an atomic per run on the same address from every workgroup).  A key that
-// finds its slot taken by another goes to global memory directly: the sums are integers, the route does not show.
-constexpr int TAB = 128;
-__device__ __forceinline__ int tab_slot(int* keys, int key) {         // the key's slot, or -1
-  const int h = (int)(((unsigned)key * 2654435761u) >> 25);
-  const int old = atomicCAS(keys + h, -1, key);
-  return (old == -1 || old == key) ? h : -1;
-}
+constexpr int TAB = 128;                 // slots of a workgroup's LDS table (scan.hpp): areas here, boxes in cc_ids_kernel
 
 // ------------------------------------------------------------------------------------------------ flatten + area
 // a workgroup owns 32 rows x 64 columns, a wave 8 rows of them; per row the run heads add their run's length
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int* __restrict__ parent, int* __restrict__ area, int* __restrict__ rowcnt, int H,
                                                          int W) {
-  __shared__ int t_key[TAB], t_cnt[TAB];
+  __shared__ AddTable<TAB> tab;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int x = blockIdx.x * 64 + lane, y0 = blockIdx.y * (4 * RW) + wv * RW;
-  if (threadIdx.x < TAB) { t_key[threadIdx.x] = -1; t_cnt[threadIdx.x] = 0; }
+  tab.clear();
   int r[RW], n[RW];
 #pragma unroll
   for (int k = 0; k < RW; ++k) r[k] = (x < W && y0 + k < H) ? parent[(size_t)(y0 + k) * W + x] : -1;
@@ -263,38 +243,18 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* __restrict__ paren
     const u64 roots = __ballot(r[k] >= 0 && r[k] == y * W + x);
     if (lane == 0 && roots) atomicAdd(rowcnt + y, __popcll(roots));
     const int len = run_length(r[k], lane);
-    if (len && r[k] >= 0) {
-      const int h = tab_slot(t_key, r[k]);
-      if (h >= 0) atomicAdd(t_cnt + h, len);
-      else atomicAdd(area + r[k], len);
-    }
+    if (len && r[k] >= 0) tab.add(r[k], len, area + r[k]);
   }
   __syncthreads();
-  if (threadIdx.x < TAB && t_key[threadIdx.x] >= 0) atomicAdd(area + t_key[threadIdx.x], t_cnt[threadIdx.x]);
+  tab.flush([&](int root) { return area + root; });
 }
 
 // ------------------------------------------------------------------------------------------------ ranking
+// ONE workgroup: rowbase = the exclusive scan of the H row counts, *num = K
 __global__ __launch_bounds__(256) void cc_scan_kernel(const int* __restrict__ rowcnt, int* __restrict__ rowbase, int32_t* __restrict__ num,
                                                       int H) {
-  __shared__ int s[256];
-  const int tid = threadIdx.x, chunk = (H + 255) / 256;
-  const int lo = tid * chunk < H ? tid * chunk : H, hi = lo + chunk < H ? lo + chunk : H;
-  int sum = 0;
-  for (int y = lo; y < hi; ++y) sum += rowcnt[y];
-  s[tid] = sum;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int add = tid >= o ? s[tid - o] : 0;
-    __syncthreads();
-    s[tid] += add;
-    __syncthreads();
-  }
-  int run = s[tid] - sum;
-  for (int y = lo; y < hi; ++y) {
-    rowbase[y] = run;
-    run += rowcnt[y];
-  }
-  if (tid == 255) *num = s[255];
+  const int total = wg_scan(rowcnt, rowbase, (long)H);
+  if (threadIdx.x == 0) *num = total;
 }
 
 __device__ __forceinline__ u64 cc_key(int area, int id) { return ((u64)(unsigned)area << 32) | (u64)(0xffffffffu - (unsigned)id); }
@@ -371,7 +331,7 @@ __global__ __launch_bounds__(256) void cc_ids_kernel(const int* __restrict__ par
     if (y >= H) break;                                             // wave-uniform
     const int len = run_length(id[k], lane);
     if (len && id[k] >= 1 && id[k] <= cap) {
-      const int h = tab_slot(t_key, id[k]);
+      const int h = tab_slot<TAB>(t_key, id[k]);
       if (h >= 0) {
         atomicMin(&t_box[h][0], y); atomicMin(&t_box[h][1], x); atomicMax(&t_box[h][2], y + 1); atomicMax(&t_box[h][3], x + len);
       } else to_global(id[k], y, x, y + 1, x + len);

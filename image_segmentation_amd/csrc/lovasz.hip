@@ -8,12 +8,14 @@
 //             is inverted).  Every pass: hist (digit counts of one tile of TILE slots), scan (per segment and digit, exclusive
 //             over the tiles; the digit totals), scatter (the tile's slots ranked in input order by wave ballots, then stored)
 //   count     fg slots and counted slots per tile of the sorted order; fgscan: exclusive over the tiles, the totals are G and n
+//             (the prefix over a workgroup, here and for the scatter's digit bases, is scan.hpp's block_scan: DESIGN.md 3.20)
 //   terms     F_i by ballots, g_i = J_i - J_{i-1} in float64 from integers, coef scattered back to pixel order, one float64
 //             partial per tile; the block that arrives last (ticket.hpp) adds the partials per segment in a fixed order and
 //             writes the state and the loss
 // No workgroup waits for another: every scan across tiles is a launch of its own, the finish is a last-arriver ticket.  No
 // atomics on global memory but that ticket, nothing to zero, no host sync, no allocation.
 #include "class_pixels.hpp"
+#include "scan.hpp"
 #include "segk_internal.h"
 
 namespace {
@@ -173,19 +175,8 @@ __global__ __launch_bounds__(ST) void lovasz_scatter_kernel(const unsigned* __re
 #pragma unroll
   for (int j = 0; j < NW; ++j) cnt[j][tid] = 0;
   // thread = digit: start of the digit in the segment (exclusive sum of the totals) + the tiles in front
-  const unsigned dt = dtot[q * RADIX + tid];
-  unsigned inc = dt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned x = __shfl_up(inc, o);
-    inc += lane >= o ? x : 0u;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  unsigned wb = 0;
-#pragma unroll
-  for (int j = 0; j < NW; ++j) wb += j < w ? wsum[j] : 0u;
-  base[tid] = wb + inc - dt + off[(size_t)blk * RADIX + tid];
+  unsigned all;
+  base[tid] = block_scan<NW>(dtot[q * RADIX + tid], wsum, all) + off[(size_t)blk * RADIX + tid];
 
   const long sb = (long)q * L;
   const long i0 = (long)t * TILE + w * (ROUNDS * 64) + lane;
@@ -277,24 +268,10 @@ __global__ __launch_bounds__(SCAN_T) void lovasz_fgscan_kernel(unsigned* __restr
     const unsigned i = base + tid;
     const unsigned v = i < TS ? f[i] : 0u;
     nacc += i < TS ? n[i] : 0u;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned x = __shfl_up(inc, o);
-      inc += lane >= o ? x : 0u;
-    }
-    if (lane == 63) ws[w] = inc;
-    __syncthreads();
-    unsigned wb = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_W; ++j) {
-      const unsigned x = ws[j];
-      wb += j < w ? x : 0u;
-      tot += x;
-    }
-    if (i < TS) f[i] = carry + wb + inc - v;
+    unsigned tot;
+    const unsigned ex = carry + block_scan<SCAN_W>(v, ws, tot);
+    if (i < TS) f[i] = ex;
     carry += tot;
-    __syncthreads();
   }
   nacc = wave_sum(nacc);
   if (lane == 0) wn[w] = nacc;

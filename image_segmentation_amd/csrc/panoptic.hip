@@ -11,28 +11,29 @@
 //  segk_pq_pairs
 //   pq_init_kernel     table keys empty, counts 0, first pixels +inf, the leader bitmap 0, the overflow flag 0
 //   pq_insert_kernel   one workgroup per 2048 pixels: segment pair of every pixel, equal keys of consecutive pixels collapsed
-//                      by a ballot of the run heads, the runs collapsed in an LDS table of 256 slots (a key that finds its
-//                      slot taken goes to the global table directly), then ONE global insert per LDS slot: atomicCAS on the
-//                      64-bit key, integer atomicAdd of the count, atomicMin of the first pixel
+//                      by scan.hpp's run_length, the runs collapsed in an LDS table of 256 slots of its own (64-bit keys, two
+//                      payloads; a key that finds its slot taken goes to the global table directly), then ONE global insert
+//                      per LDS slot: atomicCAS on the 64-bit key, integer atomicAdd of the count, atomicMin of the first pixel
 //   pq_mark_kernel     one thread per slot: bit `first pixel` of the leader bitmap
-//   pq_count_kernel    leaders per chunk of 1024 bitmap words
-//   pq_scan_kernel     ONE workgroup: exclusive scan of the chunk counts, P; decides overflow and writes totals
-//   pq_prefix_kernel   the same chunk again with its base: leaders before every bitmap word
+//   pq_words_kernel<false>  leaders per chunk of 1024 bitmap words (block_scan)
+//   pq_scan_kernel     ONE workgroup: wg_scan of the chunk counts, P; decides overflow and writes totals
+//   pq_words_kernel<true>   the same chunk again with its base: leaders before every bitmap word
 //   pq_emit_kernel     one thread per slot: row = leaders before its first pixel -> pair_g / pair_p / pair_n
 //  segk_pq_match
 //   pq_zero_kernel     the per-segment rows in use, totals[1..3]
-//   pq_area_kernel     one thread per pair: area_g, area_p, void_p, through LDS cells for the stuff rows and a small LDS table
-//                      for the others (a segment that meets thousands of others is one address)
+//   pq_area_kernel     one thread per pair: area_g, area_p, void_p, through LDS cells for the stuff rows and scan.hpp's
+//                      AddTable for the others (a segment that meets thousands of others is one address)
 //   pq_test_kernel     one thread per pair: 2 n > union -> the match records (a unique writer per row: DESIGN.md 3.19)
 //   pq_classify_kernel one thread per segment row: TP / FP / FN and the IoU sums into an LDS copy of the 8 x 16 cells, then one
 //                      64-bit integer atomic per non-zero cell
-#include "common.hpp"
+// block_scan, wg_scan, run_length, AddTable and the load / index helpers are the object kernels' shared ones: scan.hpp
+// (DESIGN.md 3.20).
+#include "scan.hpp"
 #include "segk_internal.h"
 #include "../../include/segk.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int BP = SEGK_PQ_BLOCK_PIXELS;    // pixels a workgroup inserts
 constexpr int LT = SEGK_PQ_LDS_SLOTS;       // slots of its LDS table, and of the area pass's: one per thread
 constexpr int CH = SEGK_PQ_CHUNK;           // bitmap words a workgroup counts and scans
@@ -42,8 +43,6 @@ constexpr u64 EMPTY = ~0ull;
 constexpr int NOPIX = 0x7fffffff;
 static_assert(BP == 8 * 256 && LT == 256 && CH == 4 * 256, "8 pixels, one LDS slot and 4 bitmap words per thread of a workgroup");
 static_assert(NC * NS == 128, "the statistics are 128 cells: one per thread of half a workgroup");
-
-__host__ __device__ inline long r4(long n) { return (n + 3) / 4 * 4; }
 
 // workspace layout in 32-bit words (SEGK_PQ_WS_INTS of the header).  head[0]: the overflow flag
 struct Ws {
@@ -68,11 +67,6 @@ __host__ __device__ inline Ws ws_split(int32_t* ws, long hw, long max_pairs) {
   w.part = w.wbase + r4(w.words);
   return w;
 }
-
-__device__ __forceinline__ int dev_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ u64 dev_load64(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ long stride_of(void) { return (long)gridDim.x * 256; }
-__device__ __forceinline__ long thread_of(void) { return (long)blockIdx.x * 256 + threadIdx.x; }
 
 __device__ __forceinline__ unsigned pq_hash(u64 k) {
   k ^= k >> 33; k *= 0xff51afd7ed558ccdULL;
@@ -141,14 +135,9 @@ __global__ __launch_bounds__(256) void pq_insert_kernel(const uint8_t* __restric
 #pragma unroll
   for (int k = 0; k < BP / 256; ++k) {
     // run heads of the wave's 64 consecutive pixels: a head adds its run's length once (its own pixel is the run's first)
-    const int lo = (int)(unsigned)key[k], hi = (int)(unsigned)(key[k] >> 32);
-    const int plo = __shfl_up(lo, 1), phi = __shfl_up(hi, 1);
-    const bool head = lane == 0 || plo != lo || phi != hi;
-    const u64 heads = __ballot(head);
-    if (head && key[k] != EMPTY) {
+    const int len = run_length(key[k], lane);
+    if (len && key[k] != EMPTY) {
       const int p = (int)(p0 + k * 256);
-      const u64 upper = lane == 63 ? 0ull : heads >> (lane + 1);
-      const int len = upper ? __ffsll((long long)upper) : 64 - lane;
       const int h = (int)(pq_hash(key[k]) & (unsigned)(LT - 1));
       const u64 old = atomicCAS(&t_key[h], EMPTY, key[k]);
       if (old == EMPTY || old == key[k]) {
@@ -172,29 +161,6 @@ __global__ __launch_bounds__(256) void pq_mark_kernel(int32_t* __restrict__ wsp,
     }
 }
 
-// exclusive prefix of v over the 256 threads of the workgroup, and the sum of all in `total`; s_w: 4 words of LDS
-__device__ __forceinline__ int block_scan(int v, int* s_w, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o);
-    if (lane >= o) inc += u;
-  }
-  __syncthreads();
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int t = s_w[k];
-    if (k < wv) base += t;
-    total += t;
-  }
-  return base + inc - v;
-}
-
 // chunk blockIdx.x of the bitmap: SCATTER false -> its leader count; true -> the leaders before each of its words
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void pq_words_kernel(int32_t* __restrict__ wsp, const int32_t* __restrict__ totals, long hw, long max_pairs) {
@@ -209,7 +175,7 @@ __global__ __launch_bounds__(256) void pq_words_kernel(int32_t* __restrict__ wsp
     sum += c[k];
   }
   int total;
-  int ex = block_scan(sum, s_w, total);
+  int ex = block_scan<4>(sum, s_w, total);
   if (!SCATTER) {
     if (threadIdx.x == 0) w.part[blockIdx.x] = total;
     return;
@@ -225,19 +191,8 @@ __global__ __launch_bounds__(256) void pq_words_kernel(int32_t* __restrict__ wsp
 // ONE workgroup: part[0..chunks) -> its exclusive prefix sums, in place; P; the overflow decision; totals
 __global__ __launch_bounds__(256) void pq_scan_kernel(int32_t* __restrict__ wsp, int32_t* __restrict__ totals, const int32_t* __restrict__ nump,
                                                       const int32_t* __restrict__ numg, long hw, long max_pairs, int cap) {
-  __shared__ int s_w[4];
   const Ws w = ws_split(wsp, hw, max_pairs);
-  const long per = (w.chunks + 255) / 256;
-  const long lo = threadIdx.x * per < w.chunks ? threadIdx.x * per : w.chunks, hi = lo + per < w.chunks ? lo + per : w.chunks;
-  int sum = 0;
-  for (long i = lo; i < hi; ++i) sum += w.part[i];
-  int total;
-  int run = block_scan(sum, s_w, total);
-  for (long i = lo; i < hi; ++i) {
-    const int v = w.part[i];
-    w.part[i] = run;
-    run += v;
-  }
+  const int total = wg_scan(w.part, w.part, w.chunks);
   if (threadIdx.x == 0) {
     const bool over = w.head[0] != 0 || (long)total > max_pairs || *nump > cap || *numg > cap || *nump < 0 || *numg < 0;
     totals[0] = over ? -1 : total;
@@ -286,18 +241,10 @@ __global__ __launch_bounds__(256) void pq_zero_kernel(Seg a, int32_t* __restrict
 
 // A segment that meets many others (a stuff class, a background component) is one address for thousands of pairs: what a
 // workgroup adds to one row leaves as ONE global atomic per word.  The eight stuff rows have cells of their own; the other rows
-// share a small open table keyed by row, and a key that finds its slot taken by another goes to global memory directly: the
-// sums are integers, the route does not show.  t: 0 area_g, 1 area_p, 2 void_p.
-__device__ __forceinline__ void area_add(int (*s_stuff)[NC], int* t_key, int* t_val, int32_t* __restrict__ dst, int t, int r, int n, int cap) {
-  if (r >= cap) {
-    atomicAdd(&s_stuff[t][r - cap], n);
-    return;
-  }
-  const int key = 3 * r + t;
-  const int h = (int)(((unsigned)key * 2654435761u) >> 24);
-  const int old = atomicCAS(t_key + h, -1, key);
-  if (old == -1 || old == key) atomicAdd(t_val + h, n);
-  else atomicAdd(dst + r, n);
+// share scan.hpp's AddTable under the key 3 * row + t.  t: 0 area_g, 1 area_p, 2 void_p.
+__device__ __forceinline__ void area_add(int (*s_stuff)[NC], AddTable<LT>& tab, int32_t* __restrict__ dst, int t, int r, int n, int cap) {
+  if (r >= cap) atomicAdd(&s_stuff[t][r - cap], n);
+  else tab.add(3 * r + t, n, dst + r);
 }
 
 __global__ __launch_bounds__(256) void pq_area_kernel(const int32_t* __restrict__ pair_g, const int32_t* __restrict__ pair_p,
@@ -305,21 +252,21 @@ __global__ __launch_bounds__(256) void pq_area_kernel(const int32_t* __restrict_
                                                       const int32_t* __restrict__ nump, const int32_t* __restrict__ numg, int cap,
                                                       int max_pairs) {
   __shared__ int s_stuff[3][NC];
-  __shared__ int t_key[LT], t_val[LT];
+  __shared__ AddTable<LT> tab;
   int P = totals[0];
   if (P < 0) return;
   P = P < max_pairs ? P : max_pairs;
-  t_key[threadIdx.x] = -1; t_val[threadIdx.x] = 0;
+  tab.clear();
   if (threadIdx.x < 3 * NC) s_stuff[threadIdx.x / NC][threadIdx.x % NC] = 0;
   __syncthreads();
   const int np = *nump, ng = *numg;
   int32_t* const dst[3] = {a.area_g, a.area_p, a.void_p};
   for (long i = thread_of(); i < P; i += stride_of()) {
     const int g = pair_g[i], p = pair_p[i], n = pair_n[i];
-    if (row_ok(g - 1, ng, cap)) area_add(s_stuff, t_key, t_val, dst[0], 0, g - 1, n, cap);
+    if (row_ok(g - 1, ng, cap)) area_add(s_stuff, tab, dst[0], 0, g - 1, n, cap);
     if (row_ok(p - 1, np, cap)) {
-      area_add(s_stuff, t_key, t_val, dst[1], 1, p - 1, n, cap);
-      if (g == -1) area_add(s_stuff, t_key, t_val, dst[2], 2, p - 1, n, cap);
+      area_add(s_stuff, tab, dst[1], 1, p - 1, n, cap);
+      if (g == -1) area_add(s_stuff, tab, dst[2], 2, p - 1, n, cap);
     }
   }
   __syncthreads();
@@ -327,8 +274,7 @@ __global__ __launch_bounds__(256) void pq_area_kernel(const int32_t* __restrict_
     const int v = s_stuff[threadIdx.x / NC][threadIdx.x % NC];
     if (v) atomicAdd(dst[threadIdx.x / NC] + cap + threadIdx.x % NC, v);
   }
-  const int key = t_key[threadIdx.x];
-  if (key >= 0) atomicAdd(dst[key % 3] + key / 3, t_val[threadIdx.x]);
+  tab.flush([&](int key) { return dst[key % 3] + key / 3; });
 }
 
 __global__ __launch_bounds__(256) void pq_test_kernel(const int32_t* __restrict__ pair_g, const int32_t* __restrict__ pair_p,

@@ -37,8 +37,6 @@ static_assert(sizeof(segk_rast_shape) == 32 && sizeof(segk_rast_tile) == 32, "ta
 
 struct Rec { int kind, value, begin, end, H; };             // a shape record with its range clamped; kind -1: skipped
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 // the toggles of one edge in the rows [y0, y1) and columns [x0, x1) of the image
 __device__ __forceinline__ void edge_toggles(const int4 e, int y0, int y1, int x0, int x1, uint32_t* __restrict__ s_bits) {
   int X0 = e.x, Y0 = e.y, X1 = e.z, Y1 = e.w;

@@ -6,12 +6,14 @@
 // The host knows neither the object count nor any of the totals: grids are sized from H, W and the capacities, a kernel reads
 // the counts it needs from device memory (totals[], written by an earlier launch of the same call) and grid-strides over them.
 // Every loop is bounded by an argument; no workgroup waits for another (every prefix sum is reduce, then scan of the block
-// partials by ONE workgroup, then scan again with the block's base); order between the launches is stream order.
+// partials by ONE workgroup, then scan again with the block's base); order between the launches is stream order.  The prefix
+// inside a workgroup (block_scan) and the scan of the partials (wg_scan) are the object kernels' shared ones: scan.hpp
+// (DESIGN.md 3.20).
 //
 //  segk_vec_runs
 //   vec_runs_kernel<false>  one workgroup per tile of 128 rows x 32 columns: rows read whole (coalesced) into LDS, 8 lanes walk one
 //                           column segment: run starts per (column, tile row) in t-order
-//   vec_scan_kernel         exclusive scan of those counts, totals[0]
+//   vec_scan_kernel         wg_scan of those counts, totals[0]
 //   vec_runs_kernel<true>   the same walk with the segment's base: run_start / run_obj
 //  segk_vec_rings           E edges, R rings, V vertices; J = ceil(log2(max_edges)) + 1 rounds
 //   vec_sides_kernel        side mask of every pixel (4 bits: the sides that carry an edge), edges per block of 2048 pixels
@@ -28,19 +30,16 @@
 //   vec_verts_kernel<false> corners and ring starts per block of 2048 slots
 //   vec_scan_kernel         totals[3] = V
 //   vec_verts_kernel<true>  xy of the corners, ring_offset, ring_area2
-#include "common.hpp"
+#include "scan.hpp"
 #include "segk_internal.h"
 #include "../../include/segk.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int CH = SEGK_VEC_CHUNK;          // items a workgroup scans
 constexpr int RY = SEGK_VEC_RUN_ROWS;       // rows and columns of a run-table tile
 constexpr int RX = 32;
 static_assert(CH == 8 * 256 && RY == 128, "a workgroup scans 8 items per thread; 8 lanes x 16 rows walk a column segment");
-
-__host__ __device__ inline long r4(long n) { return (n + 3) / 4 * 4; }
 
 // workspace layout in 32-bit words (SEGK_VEC_WS_INTS of the header): the 64-bit arrays come first
 struct Ws {
@@ -66,30 +65,6 @@ __host__ __device__ inline Ws ws_split(int32_t* ws, long hw, long me) {
   return w;
 }
 
-// exclusive prefix of v over the 256 threads of the workgroup, and the sum of all in `total`; s_w: 4 words of LDS
-template <typename T>
-__device__ __forceinline__ T block_scan(T v, T* s_w, T& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  T inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T u = __shfl_up(inc, o);
-    if (lane >= o) inc += u;
-  }
-  __syncthreads();                     // the words of the call before have been read
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  T base = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const T t = s_w[w];
-    if (w < wv) base += t;
-    total += t;
-  }
-  return base + inc - v;
-}
-
 template <typename T> __device__ __forceinline__ int scan_count(T v);
 template <> __device__ __forceinline__ int scan_count<int>(int v) { return v; }
 template <> __device__ __forceinline__ int scan_count<u64>(u64 v) { return (int)(v >> 32); }
@@ -97,29 +72,10 @@ template <> __device__ __forceinline__ int scan_count<u64>(u64 v) { return (int)
 // ONE workgroup: d[0..n) -> its exclusive prefix sums, in place; the count of the sum -> *out (the high word of a 64-bit pair).
 // guard: skipped when guard[1] (the edge count) exceeds cap.
 template <typename T>
-__global__ __launch_bounds__(256) void vec_scan_kernel(T* __restrict__ d, long n, int32_t* __restrict__ out, const int32_t* __restrict__ guard,
-                                                       int cap) {
-  __shared__ T s_w[4];
+__global__ __launch_bounds__(256) void vec_scan_kernel(T* d, long n, int32_t* __restrict__ out, const int32_t* __restrict__ guard, int cap) {
   if (guard && guard[1] > cap) return;
-  T carry = 0;
-  for (long i0 = 0; i0 < n; i0 += 1024) {
-    const long i = i0 + 4 * threadIdx.x;
-    T v[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[k] = i + k < n ? d[i + k] : (T)0;
-      sum += v[k];
-    }
-    T total;
-    T ex = carry + block_scan(sum, s_w, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (i + k < n) d[i + k] = ex;
-      ex += v[k];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) *out = scan_count(carry);
+  const T total = wg_scan(d, d, n);
+  if (threadIdx.x == 0) *out = scan_count(total);
 }
 
 // ------------------------------------------------------------------------------------------------ run table
@@ -189,7 +145,7 @@ __global__ __launch_bounds__(256) void vec_sides_kernel(const int32_t* __restric
   __shared__ int s_w[4];
   const long hw = (long)H * W;
   const Ws ws = ws_split(wsp, hw, me);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < me / 4 + 1; i += (long)gridDim.x * 256) ws.area[i] = 0;
+  for (long i = thread_of(); i < me / 4 + 1; i += stride_of()) ws.area[i] = 0;
   int sum = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -207,7 +163,7 @@ __global__ __launch_bounds__(256) void vec_sides_kernel(const int32_t* __restric
     }
   }
   int total;
-  block_scan(sum, s_w, total);
+  block_scan<4>(sum, s_w, total);
   if (threadIdx.x == 0) ws.ppart[blockIdx.x] = total;
 }
 
@@ -224,7 +180,7 @@ __global__ __launch_bounds__(256) void vec_edges_kernel(int32_t* __restrict__ ws
     const long p = (long)blockIdx.x * CH + k * 256 + threadIdx.x;
     const unsigned m = p < hw ? ws.sides[p] : 0u;
     int total;
-    int e = carry + block_scan((int)__popc(m), s_w, total);
+    int e = carry + block_scan<4>((int)__popc(m), s_w, total);
     carry += total;
     if (p < hw) ws.pixbase[p] = e;
 #pragma unroll
@@ -236,8 +192,8 @@ __global__ __launch_bounds__(256) void vec_edges_kernel(int32_t* __restrict__ ws
   }
 }
 
-__device__ __forceinline__ int stride_of(void) { return (int)(gridDim.x * 256); }
-
+// Edge loops count in int: E <= max_edges <= 2^30 and the grid stride (flat_grid: at most 8 workgroups per CU) is far below
+// 2^30, so an index plus one stride still fits; thread_of and stride_of themselves are long (scan.hpp).
 // successor of edge e = (pixel, side d): of the edges that leave its end vertex (vx, vy) with the object on their right --
 // E: top of the pixel SE of the vertex, S: right of SW, W: bottom of NW, N: left of NE -- the first that exists of right turn,
 // straight, left turn (connectivity 4) or left turn, straight, right turn (connectivity 8).
@@ -246,7 +202,7 @@ __global__ __launch_bounds__(256) void vec_succ_kernel(const int32_t* __restrict
   const Ws ws = ws_split(wsp, (long)H * W, max_edges);
   const int E = totals[1];
   if (E > max_edges) return;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < E; e += stride_of()) {
+  for (int e = (int)thread_of(); e < E; e += (int)stride_of()) {
     const int key = ws.key[e], p = key >> 2, d = key & 3;
     const int y = p / W, x = p - y * W, k = obj[p];
     const int vx = x + ((d == 0 || d == 1) ? 1 : 0), vy = y + ((d == 1 || d == 2) ? 1 : 0);
@@ -278,7 +234,7 @@ __global__ __launch_bounds__(256) void vec_jump_kernel(const int2* __restrict__ 
                                                        int max_edges) {
   const int E = totals[1];
   if (E > max_edges) return;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < E; e += stride_of()) {
+  for (int e = (int)thread_of(); e < E; e += (int)stride_of()) {
     const int2 a = src[e];
     const int2 b = src[a.x];
     dst[e] = make_int2(b.x, MIN ? (a.y < b.y ? a.y : b.y) : a.y + b.y);
@@ -290,7 +246,7 @@ __global__ __launch_bounds__(256) void vec_cut_kernel(const int2* __restrict__ s
                                                       int* __restrict__ head, const int32_t* __restrict__ totals, int max_edges) {
   const int E = totals[1];
   if (E > max_edges) return;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < E; e += stride_of()) {
+  for (int e = (int)thread_of(); e < E; e += (int)stride_of()) {
     const int h = src[e].y, s = succ[e];
     head[e] = h;
     dst[e] = s == h ? make_int2(e, 0) : make_int2(s, 1);
@@ -314,7 +270,7 @@ __global__ __launch_bounds__(256) void vec_heads_kernel(const int32_t* __restric
     const bool is_head = e < E && ws.head[e] == (int)e;
     const int len = is_head ? dist[e].y + 1 : 0;
     u64 total;
-    const u64 ex = carry + block_scan(is_head ? ((1ull << 32) | (u64)(unsigned)len) : 0ull, s_w, total);
+    const u64 ex = carry + block_scan<4>(is_head ? ((1ull << 32) | (u64)(unsigned)len) : 0ull, s_w, total);
     carry += total;
     if (SCATTER && is_head) {
       const int ring = (int)(ex >> 32), first = (int)(ex & 0xffffffffu);
@@ -344,9 +300,9 @@ __global__ __launch_bounds__(256) void vec_order_kernel(int32_t* __restrict__ ws
   const int E = totals[1];
   if (E > max_edges) return;
   const int lane = threadIdx.x & 63, nslot = max_edges / 4 + 1;
-  const int rounds = (E + stride_of() - 1) / stride_of();
+  const int stride = (int)stride_of(), rounds = (E + stride - 1) / stride;
   for (int it = 0; it < rounds; ++it) {                       // whole waves stay together for the ballots
-    const int e = it * stride_of() + blockIdx.x * 256 + threadIdx.x;
+    const int e = it * stride + (int)thread_of();
     bool valid = e < E;
     int ring = -1;
     long long a2 = 0;
@@ -389,7 +345,7 @@ __global__ __launch_bounds__(256) void vec_verts_kernel(int32_t* __restrict__ ws
     const long q = (long)blockIdx.x * CH + k * 256 + threadIdx.x;
     const unsigned o = q < E ? (unsigned)ws.succ[q] : 0u;
     u64 total;
-    const u64 ex = carry + block_scan(((u64)((o >> 30) & 1u) << 32) | (u64)(o >> 31), s_w, total);
+    const u64 ex = carry + block_scan<4>(((u64)((o >> 30) & 1u) << 32) | (u64)(o >> 31), s_w, total);
     carry += total;
     if (!SCATTER) continue;
     const int v = (int)(ex >> 32), ring = (int)(ex & 0xffffffffu);

@@ -122,6 +122,10 @@ def components(mask, connectivity=4, classes=None, min_area=0, keep_largest=Fals
 # ---------------------------------------------------------------------------------------------- synthetic masks
 SIZES = [(1, 1), (1, 9), (7, 1), (2, 3), (31, 33), (64, 64), (65, 129), (130, 259), (200, 37)]
 PATTERNS = ["one_class", "checkerboard", "spiral", "comb", "u_shape", "rings", "noise2", "noise4", "blobs", "high_values"]
+# more rows than the 1024 that the scan of the row counts takes per trip (csrc/scan.hpp): two trips and three, with a root on
+# most rows.  Kept beside SIZES: the narrow masks need neither every pattern nor the cleaning cases
+TALL_SIZES = [(1100, 3), (2049, 2)]
+TALL_PATTERNS = ["row_stripes", "noise2"]
 
 
 def _rng(H, W, salt):
@@ -162,6 +166,8 @@ def pattern(name, H, W):
     elif name == "rings":                                 # concentric rectangular rings of alternating classes 1, 2, 3
         d = np.minimum(np.minimum(yy, H - 1 - yy), np.minimum(xx, W - 1 - xx))
         m[:] = (1 + (d // 2) % 3).astype(np.uint8)
+    elif name == "row_stripes":                           # rows of the classes 1, 2, 1, ...: every row is a component
+        m[:] = (1 + (yy & 1)).astype(np.uint8)
     elif name == "noise2":
         m[:] = _rng(H, W, 2).integers(0, 2, size=(H, W), dtype=np.uint8)
     elif name == "noise4":

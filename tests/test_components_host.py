@@ -132,6 +132,19 @@ def test_patterns_are_what_they_claim():
 
 
 @pytest.mark.parametrize("connectivity", [4, 8])
+@pytest.mark.parametrize("size", R.TALL_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_tall_masks_have_a_root_on_most_rows(size, connectivity):
+    H, W = size
+    r = R.components(R.pattern("row_stripes", H, W), connectivity)
+    assert r["num"] == H and np.array_equal(r["labels"], np.repeat(np.arange(1, H + 1), W).reshape(H, W))
+    assert (r["area"] == W).all() and np.array_equal(r["first"], W * np.arange(H)) and r["cls"].tolist() == [1 + (y & 1) for y in range(H)]
+    r = R.components(R.pattern("noise2", H, W), connectivity)
+    roots_of_row = np.bincount(r["first"] // W, minlength=H)              # the noise: rows with no root, with one and with more
+    assert H > 1024 and (roots_of_row > 0).sum() > H // 4 and roots_of_row[1024:].any() and (roots_of_row == 0).any()
+    assert roots_of_row.max() > 1 or connectivity == 8
+
+
+@pytest.mark.parametrize("connectivity", [4, 8])
 def test_numbering_is_scipys(connectivity):
     ndi = pytest.importorskip("scipy.ndimage")
     structure = np.ones((3, 3), int) if connectivity == 8 else None

@@ -101,6 +101,16 @@ def test_cleaning_equals_the_restatement(C, size, connectivity):
         assert changed > 0                                          # the cases do remove something
 
 
+@pytest.mark.parametrize("connectivity", [4, 8])
+@pytest.mark.parametrize("size", R.TALL_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_row_scan_takes_more_than_one_trip(C, size, connectivity):
+    """one workgroup scans the H row counts 1024 per trip (csrc/scan.hpp): two trips and three, a root on most rows"""
+    H, W = size
+    for name in R.TALL_PATTERNS:
+        _, ref = run(C, name, H, W, connectivity, H * W)
+        assert name != "row_stripes" or ref["num"] == H
+
+
 def test_components_past_the_cap(C):
     H, W = 200, 37
     for name, lo in (("noise2", 1024), ("noise4", 1024)):

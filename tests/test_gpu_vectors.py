@@ -80,6 +80,19 @@ def test_c_abi_equals_the_restatement(name, connectivity):
         assert np.array_equal(again[n], got[n]) and np.array_equal(side[n], got[n]), (name, n)
 
 
+def test_partials_scan_takes_more_than_one_trip():
+    """The ONE workgroup that scans the block partials (csrc/scan.hpp, wg_scan) takes 1024 items per trip.  Its int instance
+    runs a second trip in the cases noise0.5_3c_2x1100 and stripes130x520 above (1100 and 1040 column segments) and, through
+    segk_cc_label, in tests/test_gpu_components.py; pq_scan_kernel is that same instance, and a second trip there would need
+    over 33 M pixels, so it has no large case of its own.  The 64-bit pair instance needs more than 1024 blocks of 2048 edges:
+    a 1026 x 1026 checkerboard of single-pixel objects, every one a ring of four edges, compared with the closed form that
+    tests/test_vectors_host.py pins to the restatement.  The capacities fit exactly."""
+    O, full = VC.checker_rings(1026)
+    caps = tuple(int(v) for v in full["totals"])
+    assert (caps[1] + 2047) // 2048 > 1024
+    compare(run_abi(O, 4, caps), expected(full, caps), f"checker_rings(1026) {caps}")
+
+
 @pytest.mark.parametrize("which", ["exact", "below", "above"])
 @BOTH
 def test_serpentine_round_count_follows_the_capacity(which, connectivity):

@@ -95,6 +95,26 @@ def test_hand_checked_records():
     assert VC.reference("nested3", 4)["totals"][2] == 6 and (VC.reference("nested3", 4)["ring_area2"] < 0).sum() == 3
 
 
+def test_checker_rings_closed_form_is_the_restatement():
+    """the large case of tests/test_gpu_vectors.py is compared with VC.checker_rings alone: here it meets the ring walk"""
+    O, full = VC.checker_rings(8)
+    want = VR.vectorize(O, 4)
+    assert full["size"] == want["size"] and full["totals"].tolist() == want["totals"].tolist() and full["totals"][1:].tolist() == [128, 32, 128]
+    for n in ("run_start", "run_obj") + VR.RING_ARRAYS:
+        assert full[n].dtype == want[n].dtype and np.array_equal(full[n], want[n]), n
+    O, full = VC.checker_rings(1026)                                       # what the GPU test relies on
+    E = int(full["totals"][1])
+    assert (E + 2047) // 2048 > 1024 and O.max() == E // 4 and np.array_equal(VR.rebuild_from_runs(full["run_start"], full["run_obj"], 1026, 1026), O)
+
+
+def test_scan_cases_cross_the_trip_size():
+    """column segments of the run table = W * ceil(H / 128): one case past 1024 in one tile row, one in two"""
+    for name, nj in (("noise0.5_3c_2x1100", 1), ("stripes130x520", 2)):
+        H, W = VC.MASKS[name][0].shape
+        assert (H + 127) // 128 == nj and 1024 < W * nj <= 2048
+        assert VC.reference(name, 4)["totals"][0] > W * nj                 # more runs than segments: the counts are not all 1
+
+
 def test_cross_check_with_scipy_where_installed():
     ndimage = pytest.importorskip("scipy.ndimage")
     for name in ("hole_island", "nested3", "stripes33x65", "noise0.5_1c_120x77"):

@@ -4,7 +4,9 @@ A case is a uint8 class mask with the classes that form objects; its object map 
 tests/components_reference.py (cached, as is the restatement's result).  RAW cases give the object map itself: maps no
 labelling produces (one id on two pixels that touch only diagonally, at connectivity 4) are still defined input of the
 C ABI.  The shapes are the smallest at which each mechanism can go wrong: the run-table tile is 128 rows x 32 columns, a
-scan block 2048 items, SEGK_CC_TILE 32 rows x 64 columns."""
+scan block 2048 items, SEGK_CC_TILE 32 rows x 64 columns, and the ONE workgroup that scans the block partials takes 1024 of
+them per trip (csrc/scan.hpp): 2 x 1100 and 130 x 520 give it 1100 and 2 * 520 column segments, checker_rings(1026) more than
+1024 blocks of 2048 edges."""
 import functools
 
 import numpy as np
@@ -15,10 +17,10 @@ import vector_reference as vref
 FG = (1, 2, 3, 4, 5, 6, 7)          # class 0 is background unless a case says otherwise
 
 
-def _stripes(H, W):
-    """diagonal bands of the classes 0, 1, 2, four pixels wide: rings cross every tile border"""
+def _stripes(H, W, band=4):
+    """diagonal bands of the classes 0, 1, 2, `band` pixels wide: rings cross every tile border"""
     y, x = np.mgrid[:H, :W]
-    return (((x + y) // 4) % 3).astype(np.uint8)
+    return (((x + y) // band) % 3).astype(np.uint8)
 
 
 def _nested(n):
@@ -77,6 +79,8 @@ def _mask_cases():
     c["checker16"] = ((1 + (x + y) % 2).astype(np.uint8), FG)
     for H, W in ((33, 65), (70, 130), (64, 32), (65, 33), (129, 31)):
         c[f"stripes{H}x{W}"] = (_stripes(H, W), FG)
+    c["stripes130x520"] = (_stripes(130, 520, band=13), FG)       # two tile rows: 1040 column segments
+    c["noise0.5_3c_2x1100"] = (_noise(2, 1100, 0.5, 3, 2000), FG)   # one tile row: 1100 column segments
     c["serpentine"] = (_serpentine(64), FG)
     sizes = ((37, 53), (120, 77), (200, 300))        # every density and every class count meets every size once
     for i, density in enumerate((0.1, 0.5, 0.9)):
@@ -133,3 +137,26 @@ def serpentine_capacities():
     """the three edge capacities of the serpentine: exact, one below, and a non-power-of-two above"""
     E = int(reference("serpentine", 4)["totals"][1])
     return {"exact": E, "below": E - 1, "above": E + 37 if (E + 37) & (E + 36) else E + 39}
+
+
+def checker_rings(S):
+    """(object map, complete result at connectivity 4) of the S x S checkerboard whose foreground pixels (x + y odd) each carry
+    an id of their own, 1.. in raster order -- in closed form: every foreground pixel is one ring of its four sides, walked
+    top, right, bottom, left from its smallest key, all four corners, twice the area of a unit square.  No labelling produces
+    this map and the restatement would walk millions of edges; tests/test_vectors_host.py pins the closed form to it at 8 x 8."""
+    y, x = np.mgrid[:S, :S]
+    fg = ((x + y) & 1) == 1
+    p = np.flatnonzero(fg)
+    N = len(p)
+    O = np.zeros(S * S, np.int32)
+    O[p] = np.arange(1, N + 1, dtype=np.int32)
+    O = O.reshape(S, S)
+    px, py = (p % S).astype(np.int32), (p // S).astype(np.int32)
+    corner = np.stack([np.stack([px + dx, py + dy], axis=1) for dx, dy in zip(vref.SX, vref.SY)], axis=1)      # [N, 4, 2]
+    start, robj = vref.run_table(O)
+    full = {"size": (S, S), "connectivity": 4, "totals": np.array([len(start), 4 * N, N, 4 * N], np.int32),
+            "run_start": start, "run_obj": robj,
+            "ring_obj": np.arange(1, N + 1, dtype=np.int32), "ring_head": (4 * p).astype(np.int32),
+            "ring_len": np.full(N, 4, np.int32), "ring_area2": np.full(N, 2, np.int64),
+            "ring_offset": (4 * np.arange(N + 1)).astype(np.int32), "xy": corner.reshape(-1, 2).astype(np.int32)}
+    return O, full

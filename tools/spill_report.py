@@ -34,7 +34,7 @@ def main():
             spill, scratch = int(r.get("VGPRs Spill", 0)), int(r.get("ScratchSize", 0))
             if show_all or spill or scratch:
                 name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()[:110]
-                print(f"{u:12s} vgpr {r.get('VGPRs','?'):>4s} agpr {r.get('AGPRs','?'):>4s} spill {spill:4d} scratch {scratch:5d} occ {r.get('Occupancy','?'):>2s}  {name}")
+                print(f"{u:12s} vgpr {r.get('VGPRs','?'):>4s} agpr {r.get('AGPRs','?'):>4s} spill {spill:4d} scratch {scratch:5d} occ {r.get('Occupancy','?'):>2s} lds {r.get('LDS Size','?'):>6s}  {name}")
             bad += 1 if (spill or scratch) else 0
     print(f"{bad} kernel(s) with spills or scratch")
 
