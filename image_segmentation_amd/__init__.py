@@ -21,6 +21,8 @@ from .components import components, Components, Clean, mask_finish              
 from .vectors import vectorize, Vectors, default_capacities                                                 # noqa: F401
 from .raster import (Shape, rasterize, rasterize_batch, shapes_from_coco, shapes_from_vectors, rle_to_string,   # noqa: F401
                      rle_from_string, raster_plan)
+from .morph import (erode, dilate, open_mask, close_mask, label_band, boundary_distance, fill_holes, Filled,       # noqa: F401
+                    MorphStep)
 from .panoptic import match_objects, ObjectMatch, PanopticQuality, object_quality, quality_from_stats              # noqa: F401
 from .calibration import (Reliability, reliability, TemperatureFit, fit_temperature, refine_temperature,            # noqa: F401
                           default_temperatures, inverse_temperatures, fit_from_counts)

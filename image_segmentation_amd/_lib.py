@@ -10,13 +10,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 327        # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 328        # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
 MSE_PART_FLOATS = 1024   # SEGK_MSE_PART_FLOATS
 OPTIM_CHUNK = 4096       # SEGK_OPTIM_CHUNK
 OPTIM_MAX_GROUPS = 1024  # SEGK_OPTIM_MAX_GROUPS
+MORPH_MAX_RADIUS = 32    # SEGK_MORPH_MAX_RADIUS
+MORPH_TILE_H, MORPH_TILE_W = 64, 128       # SEGK_MORPH_TILE_H, SEGK_MORPH_TILE_W
+MORPH_WILD, MORPH_FAR = 0xFFFF, 0xFFFF     # SEGK_MORPH_WILD, SEGK_MORPH_FAR
+MORPH_METRICS = {"square": 0, "diamond": 1, "disk": 2}     # SEGK_MORPH_SQUARE / _DIAMOND / _DISK
 # flags of segk_optim_grad_norm (CLIP, SKIP_NONFINITE) and of segk_optim_adamw (NORMED, SKIP_NONFINITE, EMA_WARMUP, SWAP)
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE, OPTIM_NORMED, OPTIM_EMA_WARMUP, OPTIM_SWAP = 1, 2, 1, 4, 8
 
@@ -97,6 +101,9 @@ SIGNATURES = {
     "segk_raster_labels": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _l, _i, _vp]),
     "segk_pq_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_pq_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "segk_morph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "segk_byte_lut": (_i, [_vp, _vp, _vp, _l, _vp]),
+    "segk_fill_holes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd_bn": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_bn": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),

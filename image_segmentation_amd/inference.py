@@ -31,6 +31,7 @@ from . import _lib, ops, prompts, tiles as _tiles, tta as _tta
 from .augment import _upload
 from .clipunet import ClipUNet
 from .components import Components, as_clean, components as _components
+from .morph import as_morph
 from .vectors import as_vectors, vectorize as _vectorize
 from . import utils as U
 
@@ -63,8 +64,8 @@ class Prediction:
     counts: torch.Tensor                    # int64 [C] pixels per predicted class
     confusion: Optional[torch.Tensor]       # int64 [C,C], [pred][label]; None without labels
     meta: dict                              # the resize / padding record of process_batch_forward
-    raw_mask: Optional[torch.Tensor] = None         # with clean=: the argmax before cleaning (mask is the cleaned one)
-    components: Optional[Components] = None    # with clean=: the components of raw_mask (components.py)
+    raw_mask: Optional[torch.Tensor] = None         # with morph= or clean=: the argmax (mask is the finished one)
+    components: Optional[Components] = None    # with clean=: the components of the mask it was given (components.py)
     # set on merged views, None otherwise; attributes, not dataclass fields: the constructor stays as it was
     confidence = None                          # uint8 [H,W], (uint8)(255 p_best + 0.5)
     scores = None                              # Segmenter(return_scores=True): float32 [C,H,W], the merged probabilities
@@ -280,6 +281,11 @@ class Segmenter:
               min_area, keep_largest, max_components): the mask is cleaned on the device; Prediction.mask,
               color, counts and confusion describe the cleaned mask, raw_mask is the argmax and components its components
 
+    morph=    None (every output as without it), or a sequence of morph.MorphStep records / dicts {"op": ..., keywords}
+              ("erode", "dilate", "open", "close", "fill_holes", "label_band"): the steps are applied in order to the argmax
+              mask on the device, before clean=; Prediction.mask, color, counts and confusion describe the
+              final mask, raw_mask is the argmax
+
     Merged views (without them every output and the code path are as above):
     model     a list of models is an ensemble: same class count, same input arity, all on one device
     tta=      a tta.TTA (or a dict of its keywords): the flips and target sizes each model sees and the merge ("prob" /
@@ -312,13 +318,14 @@ class Segmenter:
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
                  sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False, tiles=None,
-                 temperature=None, vectors=None):
+                 temperature=None, vectors=None, morph=None):
         models = list(model) if isinstance(model, (list, tuple)) else [model]
         if not models:
             raise ValueError("an ensemble needs at least one model")
         model = models[0]
         self.clean = as_clean(clean)
         self.vectors = as_vectors(vectors)
+        self.morph = as_morph(morph)
         if not float(sigma) > 0:
             raise ValueError(f"sigma must be positive, got {sigma}")
         self.sigma = float(sigma)
@@ -461,8 +468,8 @@ class Segmenter:
     def _finish(self, dev, C, pal, metas, labels, launch, confident):
         """The per-image end of every route: allocate the outputs, load the label map, run the route's one kernel and build
         the Prediction.  launch(k, mask, outs, conf, scores) is that kernel for image k, on pointers: outs = (color, palette,
-        counts, labels, confusion), all null with clean= -- the kernel then writes the argmax (and confidence / scores) alone,
-        and colour, counts and confusion counts come from the cleaned mask afterwards.  confident: the route writes a
+        counts, labels, confusion), all null with morph= or clean= -- the kernel then writes the argmax (and confidence / scores)
+        alone, and colour, counts and confusion counts come from the finished mask afterwards.  confident: the route writes a
         confidence map (and scores on request); metas[k]["original_size"] is the size of output k."""
         n = len(metas)
         counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
@@ -478,14 +485,19 @@ class Segmenter:
             lab = None if labels is None else _label_on(labels[k], (oh, ow), dev, k)
             outs = (ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab), ops._p(None if M is None else M[k]))
             Mk = None if M is None else M[k, :C, :C]
-            if cl is None:
+            if cl is None and not self.morph:
                 launch(k, mask.data_ptr(), outs, ops._p(conf), ops._p(scores))
                 pred = Prediction(mask, color, counts[k, :C], Mk, meta)
             else:
                 launch(k, mask.data_ptr(), (0,) * 5, ops._p(conf), ops._p(scores))
-                comps = _components(mask, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
-                _lib.call("segk_mask_finish", comps.mask.data_ptr(), *outs, C, oh, ow, s)
-                pred = Prediction(comps.mask, color, counts[k, :C], Mk, meta, mask, comps)
+                final, comps = mask, None
+                for step in self.morph or ():
+                    final = step(final)
+                if cl is not None:
+                    comps = _components(final, cl.connectivity, cl.classes, cl.min_area, cl.keep_largest, cl.max_components)
+                    final = comps.mask
+                _lib.call("segk_mask_finish", final.data_ptr(), *outs, C, oh, ow, s)
+                pred = Prediction(final, color, counts[k, :C], Mk, meta, mask, comps)
             if confident:
                 pred.confidence, pred.scores = conf, scores
             if self.vectors is not None:

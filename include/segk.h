@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 327
-#define SEGK_ENTRY_COUNT 113
+#define SEGK_ABI_VERSION 328
+#define SEGK_ENTRY_COUNT 116
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -532,6 +532,43 @@ int segk_pq_match(const int32_t* pair_g, const int32_t* pair_p, const int32_t* p
                   const int32_t* pred_num, const int32_t* target_cls, const int32_t* target_num, int32_t* area_g,
                   int32_t* match_g, int32_t* inter_g, int32_t* union_g, int32_t* area_p, int32_t* void_p, int32_t* match_p,
                   int64_t* stats, int max_components, int max_pairs, segk_stream_t s);
+
+/* ---- mask morphology: erode, dilate, open, close, void band, capped boundary distance, hole fill (the
+ * reference has no such code: this replaces a mask.cpu() + scipy.ndimage / cv2 post-process).  Integer arithmetic only: results
+ * are unique and bit-stable.  No workgroup waits for another, no atomics on global memory in segk_morph, the host reads nothing
+ * back, every device loop is bounded by an argument.  No entry needs a workspace; segk_morph uses SEGK_MORPH_LDS_BYTES(radius)
+ * bytes of dynamic LDS: 16-bit keys of the tile with its halo, a byte of column distance per cell of the tile's rows, the tile's
+ * own bytes (69632 at radius 32: the entry raises the kernel's limit, two workgroups still share a CU). */
+#define SEGK_MORPH_TILE_H 64
+#define SEGK_MORPH_TILE_W 128
+#define SEGK_MORPH_MAX_RADIUS 32
+#define SEGK_MORPH_SQUARE 0          /* dist(dx, dy) = max(|dx|, |dy|), fires at <= r */
+#define SEGK_MORPH_DIAMOND 1         /* |dx| + |dy|, fires at <= r */
+#define SEGK_MORPH_DISK 2            /* dx dx + dy dy, fires at <= r r */
+#define SEGK_MORPH_WILD 0xFFFFu      /* the key that differs from nothing (and that pixels outside the image have) */
+#define SEGK_MORPH_FAR 0xFFFF        /* dist of a pixel that does not fire */
+#define SEGK_MORPH_LDS_BYTES(r) \
+  ((SEGK_MORPH_TILE_H + 2 * (r)) * (SEGK_MORPH_TILE_W + 2 * (r)) * 2 + SEGK_MORPH_TILE_H * (SEGK_MORPH_TILE_W + 2 * (r)) + \
+   SEGK_MORPH_TILE_H * SEGK_MORPH_TILE_W)
+/* DESIGN.md 3.21 "the primitive", "write rule": mask [H,W] uint8; key uint16 [256] and fire uint8 [256] are DEVICE tables
+ * indexed by a pixel's byte.  D(p) = the minimum of dist(p, q) over the pixels q inside the image with key[mask[q]] !=
+ * key[mask[p]], neither key being SEGK_MORPH_WILD; p fires when D(p) <= radius (disk: radius squared).
+ *   out  [H,W] uint8 (may be NULL): without paint, `value` where p fires and fire[mask[p]] is set, else mask[p]; with paint
+ *        [H,W] uint8, paint[p] where p fires, fire[mask[p]] is set and key[paint[p]] != key[mask[p]], else mask[p]
+ *   dist [H,W] uint16 (may be NULL): D(p) (squared for the disk) where p fires, else SEGK_MORPH_FAR
+ * At least one of out and dist; out is neither mask nor paint; 1 <= radius <= SEGK_MORPH_MAX_RADIUS; H*W <=
+ * SEGK_CC_MAX_PIXELS; 0 <= value <= 255; key and dist 2-byte aligned.  The inputs are only read. */
+int segk_morph(const uint8_t* mask, const uint8_t* paint, uint8_t* out, uint16_t* dist, const uint16_t* key,
+               const uint8_t* fire, int value, int metric, int radius, int H, int W, segk_stream_t s);
+/* dst[i] = lut[src[i]] for n bytes; lut uint8 [256] on the device; 1 <= n <= SEGK_CC_MAX_PIXELS; dst is not src. */
+int segk_byte_lut(const uint8_t* src, uint8_t* dst, const uint8_t* lut, long n, segk_stream_t s);
+/* DESIGN.md 3.21 "holes": after segk_cc_label (same H, W, max_components; labels, num, area, box, first are its outputs) on the
+ * map in which the complement of the class set is one class.  out [H,W] uint8 (not the mask) = value where the pixel's
+ * component id is in 1..min(num, max_components), its box touches no image border (y0 > 0, x0 > 0, y1 < H, x1 < W) and its area
+ * is <= max_area; else mask[p].  filled[0] += the number of such components (the caller zeroes it).  box 16-byte aligned. */
+int segk_fill_holes(const uint8_t* mask, const int32_t* labels, const int32_t* num, const int32_t* area, const int32_t* box,
+                    const int32_t* first, uint8_t* out, int32_t* filled, int value, int max_area, int H, int W,
+                    int max_components, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

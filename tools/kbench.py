@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1187,6 +1187,156 @@ def pq():
     print(f"written to {path}")
 
 
+def morph():
+    """Mask morphology (csrc/morph.hip) through image_segmentation_amd.morph: erode, dilate, open_mask, close_mask,
+    boundary_distance (disk), label_band (square) and fill_holes on a blob mask with 1 % speckle (classes 0..3, the set = 1 and 2)
+    at 256 x 256 (r = 1, 3) and 3000 x 4000 (r = 3, 32).  Per operation: device-event time of its segk_morph launches through the C
+    ABI (tables and outputs made before), warmed, seven rounds: median and min..max, and the median of the public call beside
+    it (which checks the arguments and builds the tables' bytes on the host per call); the byte model -- per launch one read of the
+    map with the halo of every tile and one byte (distance: two) written per pixel, a paint launch two more bytes read per pixel
+    -- over the device-to-device copy rate of a 512 MB buffer measured beside it (the floor); and the host path of the same
+    job by the host clock, the copies both ways included: mask.cpu(), scipy.ndimage (binary_erosion / binary_dilation with the
+    disk up to r = 3, the exact Euclidean transform thresholded above it; maximum_filter != minimum_filter for the band;
+    distance_transform_edt on both sides; binary_fill_holes), .cuda().  Written to profiles/morph_kbench.txt (or --out)."""
+    import time
+    import numpy as np
+    import image_segmentation_amd as seg
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    from image_segmentation_amd import morph as M
+    TH, TW = _lib.MORPH_TILE_H, _lib.MORPH_TILE_W
+    st = ops._stream()
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def blobs(H, W):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        m = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+        for c, (cy, cx, ry, rx) in ((1, (0.35, 0.3, 0.25, 0.2)), (2, (0.65, 0.7, 0.22, 0.25))):
+            d = ((yy - cy * H) / (ry * H)) ** 2 + ((xx - cx * W) / (rx * W)) ** 2
+            m[d <= 1.0] = c
+            m[(d > 1.0) & (d <= 1.25)] = 3
+        hit = torch.rand((H, W), generator=g, device="cuda") < 0.01
+        return torch.where(hit, torch.randint(0, 4, (H, W), generator=g, device="cuda", dtype=torch.uint8), m)
+
+    def staged(H, W, r):
+        """bytes of the map one launch reads: every tile's rows and columns with the halo, clipped to the image"""
+        rows = sum(min(H, y + TH + r) - max(0, y - r) for y in range(0, H, TH))
+        cols = sum(min(W, x + TW + r) - max(0, x - r) for x in range(0, W, TW))
+        return rows * cols
+
+    def disk(r):
+        yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
+        return yy * yy + xx * xx <= r * r
+
+    def host_erode(S, r):
+        return ndimage.binary_erosion(S, disk(r), border_value=1) if r <= 3 else ndimage.distance_transform_edt(S) > r
+
+    def host_dilate(S, r):
+        return ndimage.binary_dilation(S, disk(r)) if r <= 3 else ndimage.distance_transform_edt(~S) <= r
+
+    S_of = lambda a: (a == 1) | (a == 2)
+    host_ops = {
+        "erode": lambda a, r: np.where(S_of(a) & ~host_erode(S_of(a), r), 0, a),
+        "dilate": lambda a, r: np.where(~S_of(a) & host_dilate(S_of(a), r), 1, a),
+        "open_mask": lambda a, r: np.where(S_of(a) & ~host_dilate(host_erode(S_of(a), r), r), 0, a),
+        "close_mask": lambda a, r: np.where(~S_of(a) & host_erode(host_dilate(S_of(a), r), r), 1, a),
+        "boundary_distance": lambda a, r: np.where(S_of(a), ndimage.distance_transform_edt(S_of(a)), ndimage.distance_transform_edt(~S_of(a))),
+        "label_band": lambda a, r: np.where(ndimage.maximum_filter(a, 2 * r + 1) != ndimage.minimum_filter(a, 2 * r + 1), 255, a),
+    }
+    say(f"morph: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz, tile {TH} x {TW}"
+        + ("" if ndimage is not None else ", scipy not installed: no host path"))
+    src, dst = torch.empty(1 << 29, dtype=torch.uint8, device="cuda"), torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    tc = rounds(lambda: dst.copy_(src), 5)                          # 512 MB each way: larger than the last-level cache
+    rate = 2 * src.numel() / tc[0] / 1e6                            # TB/s of the copy (read + write)
+    del src, dst
+    say(f"morph: device-to-device copy of 512 MB: {rate:.2f} TB/s")
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None       # one size, e.g. 3000x4000
+    for (H, W), radii in (((256, 256), (1, 3)), ((3000, 4000), (3, 32))):
+        if only is not None and only != f"{H}x{W}":
+            continue
+        hw = H * W
+        iters, host_rounds = (50, 3) if hw <= 1 << 20 else (5, 1)
+        x = blobs(H, W)
+        for r in radii:
+            calls = [("erode", dict(classes=(1, 2), radius=r, fill=0), 1, 1, 0),
+                     ("dilate", dict(classes=(1, 2), radius=r, value=1), 1, 1, 0),
+                     ("open_mask", dict(classes=(1, 2), radius=r, fill=0), 2, 1, 1),
+                     ("close_mask", dict(classes=(1, 2), radius=r, value=1), 2, 1, 1),
+                     ("boundary_distance", dict(max_radius=r, classes=(1, 2)), 1, 2, 0),
+                     ("label_band", dict(width=r, shape="square"), 1, 1, 0)]
+            for name, kw, launches, item, paints in calls:
+                fn = getattr(seg, name)
+                plan = {"erode": M._erode_plan, "dilate": M._dilate_plan, "open_mask": M._open_plan, "close_mask": M._close_plan,
+                        "boundary_distance": M._distance_plan, "label_band": M._band_plan}[name](**kw)
+                tabs = [M._tables_on(x.device, st, s.tables) for s in plan]
+                mid, out = torch.empty_like(x), torch.empty((H, W), dtype=torch.uint16 if item == 2 else torch.uint8, device="cuda")
+
+                def entry():                                        # the launches of the operation, nothing else
+                    for k, (s, tab) in enumerate(zip(plan, tabs)):
+                        dst = out if k == len(plan) - 1 else mid
+                        _lib.call("segk_morph", (mid if k else x).data_ptr(), x.data_ptr() if s.paint else 0, 0 if item == 2 else dst.data_ptr(),
+                                  dst.data_ptr() if item == 2 else 0, tab.data_ptr(), tab.data_ptr() + 512, s.value, s.metric, s.radius, H, W, st)
+                entry()
+                assert torch.equal(out, fn(x, **kw)), name
+                t = rounds(entry, iters)
+                tcall = rounds(lambda: fn(x, **kw), iters)[0]
+                nbytes = launches * (staged(H, W, r) + hw + item * hw) + paints * hw    # halo read, the pixel's own byte again, the output
+                floor = nbytes / (rate * 1e6)
+                line = (f"morph {H}x{W} r={r:2d} {name:17s} {t[0]:9.1f} us [{t[1]:.1f}..{t[2]:.1f}]   floor ({nbytes / 1e6:7.2f} MB) {floor:7.1f} us   "
+                        f"entry / floor = {t[0] / floor:7.2f}   public call {tcall:8.1f} us")
+                if ndimage is not None:
+                    host = []
+                    for _ in range(host_rounds):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        res = host_ops[name](x.cpu().numpy(), r)
+                        out = torch.from_numpy(res if name == "boundary_distance" else res.astype(np.uint8, copy=False)).cuda()
+                        torch.cuda.synchronize()
+                        host.append((time.perf_counter() - t0) * 1e6)
+                        del out
+                    host.sort()
+                    line += f"   host {host[len(host) // 2]:12.1f} us   host / entry = {host[len(host) // 2] / t[0]:9.1f}"
+                say(line)
+        cap = 1 << 20
+        f = lambda: seg.fill_holes(x, (1, 2), value=1, max_components=cap)
+        res = f()
+        t = rounds(f, iters)
+        line = (f"morph {H}x{W}      fill_holes        {t[0]:9.1f} us [{t[1]:.1f}..{t[2]:.1f}]   components {int(res.num)} filled {int(res.filled)} "
+                f"(byte table + segk_cc_label + fill pass)")
+        if ndimage is not None:
+            host = []
+            for _ in range(host_rounds):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                a = x.cpu().numpy()
+                out = torch.from_numpy(np.where(ndimage.binary_fill_holes(S_of(a)) & ~S_of(a), 1, a).astype(np.uint8)).cuda()
+                torch.cuda.synchronize()
+                host.append((time.perf_counter() - t0) * 1e6)
+            host.sort()
+            line += f"   host {host[len(host) // 2]:12.1f} us   host / entry = {host[len(host) // 2] / t[0]:9.1f}"
+        say(line)
+        del x
+    path = os.path.join(ROOT, "profiles", "morph_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def tta():
     """Multi-view prediction through the C ABI (csrc/predict.hip): segk_predict_merge -- mask, colour, class
     counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
@@ -1530,6 +1680,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "pq":
         pq()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "morph":
+        morph()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "perturb":
         perturb()

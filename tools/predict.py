@@ -22,7 +22,10 @@ it): the confidence maps become the calibrated ones.  Not for --model prompt, wh
 --coco FILE.json writes ONE COCO-style file for all inputs (images, annotations, categories): every connected component of a
 final (cleaned) mask whose class has a category becomes an annotation with bbox, area and a polygon list -- or, when it has a
 hole, its uncompressed RLE -- built on the device.  --coco-categories 1=cat,2=dog maps classes to category
-ids (the class number) and names; the default is every class but 0 under its class name."""
+ids (the class number) and names; the default is every class but 0 under its class name.
+--open R / --close R / --fill-holes shape every mask on the device before the clean-up, in that order (spurs and
+bridges thinner than the element go, cracks close, holes fill); --morph-classes 1,2 names the classes they act on (default:
+every class but 0, closing and filling one class at a time), --morph-shape {disk,square,diamond} the element."""
 import argparse
 import os
 import sys
@@ -62,6 +65,11 @@ def main():
     ap.add_argument("--boxes", metavar="FILE.json", help="write the kept components' class, area and box per image")
     ap.add_argument("--coco", metavar="FILE.json", help="write the components of all masks as COCO annotations (polygons / RLE)")
     ap.add_argument("--coco-categories", default=None, metavar="C=NAME,...", help="classes that become categories, with their names")
+    ap.add_argument("--open", type=int, default=None, metavar="R", help="open the classes with radius R (1..32)")
+    ap.add_argument("--close", type=int, default=None, metavar="R", help="close every class with radius R (1..32)")
+    ap.add_argument("--fill-holes", action="store_true", help="fill the holes of every class")
+    ap.add_argument("--morph-classes", default=None, metavar="CLASSES", help="comma-separated classes (default: all but 0)")
+    ap.add_argument("--morph-shape", choices=["disk", "square", "diamond"], default="disk")
     ap.add_argument("images", nargs="+", metavar="IMG")
     args = ap.parse_args()
     try:
@@ -102,6 +110,27 @@ def main():
     if args.min_area > 0 or keep is not False or args.boxes:
         clean = dict(connectivity=args.connectivity, min_area=args.min_area, keep_largest=keep, max_components=args.max_components)
 
+    morph = None
+    if args.open is not None or args.close is not None or args.fill_holes:
+        try:
+            mcls = tuple(int(c) for c in args.morph_classes.split(",")) if args.morph_classes else tuple(range(1, args.classes))
+        except ValueError:
+            ap.error("--morph-classes takes comma-separated class numbers")
+        if not mcls or any(not 0 <= c < args.classes for c in mcls):
+            ap.error(f"--morph-classes: classes in 0..{args.classes - 1}")
+        other = next((c for c in range(args.classes) if c not in mcls), None)
+        if args.open is not None and other is None:
+            ap.error("--open needs a class outside --morph-classes for the opened pixels")
+        morph = []
+        if args.open is not None:                           # the set as a whole: every pixel keeps its own class
+            morph.append(dict(op="open", classes=mcls, radius=args.open, fill=other, shape=args.morph_shape))
+        if args.close is not None:
+            morph += [dict(op="close", classes=(c,), radius=args.close, shape=args.morph_shape) for c in mcls]
+        if args.fill_holes:
+            morph += [dict(op="fill_holes", classes=(c,), connectivity=args.connectivity) for c in mcls]
+    elif args.morph_classes is not None or args.morph_shape != "disk":
+        ap.error("--morph-classes and --morph-shape need --open, --close or --fill-holes")
+
     categories = None
     if args.coco_categories is not None:
         if not args.coco:
@@ -132,7 +161,7 @@ def main():
     try:
         segmenter = seg.Segmenter(models if tta is not None else models[0], target_size=args.size, interpolation=args.interpolation,
                                   palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta, tiles=tiles,
-                                  temperature=args.temperature, vectors=vectors)
+                                  temperature=args.temperature, vectors=vectors, morph=morph)
     except ValueError as e:
         ap.error(str(e))
     if args.confidence:
