@@ -23,6 +23,7 @@ from .raster import (Shape, rasterize, rasterize_batch, shapes_from_coco, shapes
                      rle_from_string, raster_plan)
 from .morph import (erode, dilate, open_mask, close_mask, label_band, boundary_distance, fill_holes, Filled,       # noqa: F401
                     MorphStep)
+from .mix import Mixer, MixPlan, MixedBatches                                                                      # noqa: F401
 from .panoptic import match_objects, ObjectMatch, PanopticQuality, object_quality, quality_from_stats              # noqa: F401
 from .calibration import (Reliability, reliability, TemperatureFit, fit_temperature, refine_temperature,            # noqa: F401
                           default_temperatures, inverse_temperatures, fit_from_counts)

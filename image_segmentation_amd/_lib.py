@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 328        # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 329        # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
@@ -21,6 +21,10 @@ MORPH_MAX_RADIUS = 32    # SEGK_MORPH_MAX_RADIUS
 MORPH_TILE_H, MORPH_TILE_W = 64, 128       # SEGK_MORPH_TILE_H, SEGK_MORPH_TILE_W
 MORPH_WILD, MORPH_FAR = 0xFFFF, 0xFFFF     # SEGK_MORPH_WILD, SEGK_MORPH_FAR
 MORPH_METRICS = {"square": 0, "diamond": 1, "disk": 2}     # SEGK_MORPH_SQUARE / _DIAMOND / _DISK
+MIX_NONE, MIX_BOX, MIX_CLASS, MIX_OBJECT = 0, 1, 2, 3      # SEGK_MIX_NONE / _BOX / _CLASS / _OBJECT
+MIX_TILE_H, MIX_TILE_W = 16, 64            # SEGK_MIX_TILE_H, SEGK_MIX_TILE_W
+MIX_MAX_OBJECTS, MIX_MAX_COMPONENTS = 32, 65536            # SEGK_MIX_MAX_OBJECTS, SEGK_MIX_MAX_COMPONENTS
+MIX_STAGE_BYTES, MIX_STAGE_SELECT = 0, 1   # SEGK_MIX_STAGE_BYTES, SEGK_MIX_STAGE_SELECT
 # flags of segk_optim_grad_norm (CLIP, SKIP_NONFINITE) and of segk_optim_adamw (NORMED, SKIP_NONFINITE, EMA_WARMUP, SWAP)
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE, OPTIM_NORMED, OPTIM_EMA_WARMUP, OPTIM_SWAP = 1, 2, 1, 4, 8
 
@@ -104,6 +108,8 @@ SIGNATURES = {
     "segk_morph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_byte_lut": (_i, [_vp, _vp, _vp, _l, _vp]),
     "segk_fill_holes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "segk_mix_select": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "segk_mix_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _l, _vp]),
     "segk_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd_bn": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_bn": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),

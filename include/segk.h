@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 328
-#define SEGK_ENTRY_COUNT 116
+#define SEGK_ABI_VERSION 329
+#define SEGK_ENTRY_COUNT 118
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -569,6 +569,61 @@ int segk_byte_lut(const uint8_t* src, uint8_t* dst, const uint8_t* lut, long n, 
 int segk_fill_holes(const uint8_t* mask, const int32_t* labels, const int32_t* num, const int32_t* area, const int32_t* box,
                     const int32_t* first, uint8_t* out, int32_t* filled, int value, int max_area, int H, int W,
                     int max_components, segk_stream_t s);
+
+/* ---- mixed-sample augmentation: CutMix, ClassMix, object copy-paste (the reference only puts two images side
+ * by side).  Every output value is a copy of one input value and the paste bit m(y, x) is defined in integers, so results are
+ * unique and bit-stable.  The host reads nothing back.  One descriptor per sample lives in DEVICE memory where the entries cannot
+ * see it: the kernels clamp the partner to 0..n-1 and the slot to 0..n_slots-1 and treat an unknown mode as SEGK_MIX_NONE; every
+ * address is formed from an entry argument that was checked. */
+#define SEGK_MIX_NONE 0
+#define SEGK_MIX_BOX 1
+#define SEGK_MIX_CLASS 2
+#define SEGK_MIX_OBJECT 3
+#define SEGK_MIX_TILE_H 16           /* segk_mix_apply: one workgroup per tile, a thread takes four pixels of a row */
+#define SEGK_MIX_TILE_W 64
+#define SEGK_MIX_MAX_OBJECTS 32
+#define SEGK_MIX_MAX_COMPONENTS 65536    /* ids fit the low 24 bits of a key */
+#define SEGK_MIX_ROW_INTS(cap) (4 + 2 * (cap))   /* one slot of cc_rows: num, three unused words, cls [cap], area [cap] */
+#define SEGK_MIX_STAGE_BYTES 0
+#define SEGK_MIX_STAGE_SELECT 1
+typedef struct segk_mix_desc {   /* one sample; 64 bytes */
+  uint64_t seed;                 /* of the selection keys */
+  int32_t mode;                  /* SEGK_MIX_* */
+  int32_t partner;               /* sample that is pasted from; may be the sample itself */
+  int32_t flip;                  /* 0 | 1: the partner is mirrored horizontally */
+  int32_t dy, dx;                /* output (y, x) looks at partner (y - dy, flip ? W - 1 - (x - dx) : x - dx) */
+  int32_t y0, x0, y1, x1;        /* SEGK_MIX_BOX, output coordinates, y1 and x1 exclusive */
+  int32_t slot;                  /* SEGK_MIX_OBJECT: which id map and cc_rows slot hold the partner's components */
+  int32_t pad_[4];
+} segk_mix_desc;
+/* DESIGN.md 3.22 "selection".  y: labels [n][H][W] of label_bytes 1 (uint8) or 8 (int64); a value outside 0..255 is "outside".
+ * stage SEGK_MIX_STAGE_BYTES: descs is a table of n_desc slot owners (mode SEGK_MIX_OBJECT); bytes [n_slots][H][W] of slot
+ *   descs[i].slot = the partner's labels as bytes, outside -> 255 (what segk_cc_label then reads).  Slots are distinct.
+ * stage SEGK_MIX_STAGE_SELECT: one workgroup per sample i < n_desc = n writes select[i * select_stride ..]:
+ *   SEGK_MIX_CLASS   256 bytes: candidates = the byte values that occur in the partner's labels and have exclude[v] == 0 (exclude
+ *                    uint8 [256] on the device); k = n_classes > 0 ? min(count, n_classes) : ceil(count / 2); byte v = 1 for the
+ *                    k candidates with the smallest key(v) = (splitmix(seed, v) & ~0xFFFFFF) | v, else 0
+ *   SEGK_MIX_OBJECT  max_components bytes: cc_rows int32 [n_slots][SEGK_MIX_ROW_INTS(max_components)] holds num / cls / area of
+ *                    segk_cc_label per slot; candidates = the ids 1..min(num, max_components) with bit cls of things_mask set and
+ *                    min_area <= area <= max_area; k = min(count, max_objects); byte id - 1 = 1 for the k smallest key(id)
+ *   other modes      nothing is written
+ * No atomics on global memory, no workgroup waits for another, loops are bounded by H W and max_components.  n <= 65535, H W <=
+ * SEGK_CC_MAX_PIXELS, select_stride >= 256 (and >= max_components when n_slots > 0), 1 <= max_objects <= SEGK_MIX_MAX_OBJECTS,
+ * 1 <= max_components <= SEGK_MIX_MAX_COMPONENTS. */
+int segk_mix_select(const segk_mix_desc* descs, int n_desc, int n, const void* y, int label_bytes, int H, int W,
+                    const uint8_t* exclude, int n_classes, const int32_t* cc_rows, int n_slots, int things_mask, int min_area,
+                    int max_area, int max_objects, int max_components, uint8_t* bytes, uint8_t* select, int select_stride,
+                    int stage, segk_stream_t s);
+/* DESIGN.md 3.22 "geometry", "paste bit", "write rule".  X: images, elem_bytes 4 or 2: [n][C][H][W]; elem_bytes 1: [n][H][W][C]
+ * (uint8); 1 <= C <= 4.  y / y_out: labels [n][H][W] of label_bytes 1 or 8.  ids int32 [n_slots][H][W]: labels of segk_cc_label
+ * (may be NULL when n_slots == 0).  m(y, x) = 0 where the partner pixel lies outside the image, else BOX: the box test; CLASS:
+ * select[label byte]; OBJECT: select[id - 1] for 1 <= id <= max_components.  X_out / y_out at (y, x) = the partner's at the source
+ * pixel where m = 1, else the sample's own; with has_seam, y_out = seam_value where a 4-neighbour inside the image has another m.
+ * pasted int32 [n] += sum of m (the caller zeroes it; one add per workgroup).  Every output element is written once.  The outputs
+ * overlap no input and not each other; X, X_out aligned to elem_bytes, y, y_out to label_bytes, pasted and ids to 4. */
+int segk_mix_apply(const segk_mix_desc* descs, int n, const void* X, const void* y, void* X_out, void* y_out, int32_t* pasted,
+                   int C, int H, int W, int elem_bytes, int label_bytes, const uint8_t* select, int select_stride,
+                   const int32_t* ids, int n_slots, int max_components, int has_seam, long seam_value, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph, mix)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1337,6 +1337,125 @@ def morph():
     print(f"written to {path}")
 
 
+def mix():
+    """Mixed-sample augmentation (csrc/mix.hip) through image_segmentation_amd.mix at the bench batch, B = 32,
+    3 x 256 x 256, int64 labels: float32 NCHW and uint8 NHWC images, each mode (every sample mixed, flips drawn, shifts for
+    copy_paste), with and without a seam.  Per line: device-event time of the segk_mix_apply launch alone (tables, id maps and
+    outputs made before), warmed, seven rounds: median and min..max; the launches in front of it (segk_mix_select, and for
+    copy_paste the byte stage and one segk_cc_label per partner); the public call (plans checked and the descriptor table
+    uploaded per call); the byte model -- read one image and the deciding map (labels; for copy_paste the id map too), write
+    image and label -- over the device-to-device copy rate of a 512 MB buffer measured beside it (the floor); and the equivalent
+    torch expression (index, flip, roll, where) on the same tensors, checked to give the same result.  Written to
+    profiles/mix_kbench.txt (or --out)."""
+    import numpy as np
+    import image_segmentation_amd as seg
+    from image_segmentation_amd import mix as M
+    st = ops._stream()
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    B, C, H, W, cap = 32, 3, 256, 256, 1024
+    say(f"mix: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz, tile {_lib.MIX_TILE_H} x {_lib.MIX_TILE_W}, "
+        f"B = {B}, {C} x {H} x {W}, int64 labels")
+    src, dst = torch.empty(1 << 29, dtype=torch.uint8, device="cuda"), torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    tc = rounds(lambda: dst.copy_(src), 5)                          # 512 MB each way: larger than the last-level cache
+    rate = 2 * src.numel() / tc[0] / 1e6                            # TB/s of the copy (read + write)
+    del src, dst
+    say(f"mix: device-to-device copy of 512 MB: {rate:.2f} TB/s")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    # label maps: four classes in cells of 32 x 32 with 1 % speckle
+    cells = torch.randint(0, 4, (B, 1, H // 32, W // 32), generator=g, device="cuda")
+    y = cells.repeat_interleave(32, 2).repeat_interleave(32, 3)
+    hit = torch.rand((B, 1, H, W), generator=g, device="cuda") < 0.01
+    y = torch.where(hit, torch.randint(0, 4, (B, 1, H, W), generator=g, device="cuda"), y).contiguous()
+    yy = torch.arange(H, device="cuda").view(1, 1, H, 1)
+    xx = torch.arange(W, device="cuda").view(1, 1, 1, W)
+
+    def torch_mix(X, plans, sel, ids, seam, nhwc):
+        dev = X.device
+        col = lambda f: torch.tensor([f(p) for p in plans], device=dev).view(B, 1, 1, 1)
+        partner = torch.tensor([p.partner for p in plans], device=dev)
+        flip = col(lambda p: p.flip).bool()
+        Xp, yp = X[partner], y[partner]
+        Xp = torch.where(flip, Xp.flip(2 if nhwc else 3), Xp)
+        yp = torch.where(flip, yp.flip(3), yp)
+        idp = None
+        if ids is not None:
+            idp = ids[torch.tensor([int(d) for d in M_slots], device=dev)].view(B, 1, H, W)
+            idp = torch.where(flip, idp.flip(3), idp)
+        if any(p.dy or p.dx for p in plans):
+            Xp, yp = Xp.clone(), yp.clone()
+            for b, p in enumerate(plans):
+                Xp[b] = torch.roll(Xp[b], (p.dy, p.dx), dims=(0, 1) if nhwc else (1, 2))
+                yp[b] = torch.roll(yp[b], (p.dy, p.dx), dims=(1, 2))
+                if idp is not None:
+                    idp[b] = torch.roll(idp[b], (p.dy, p.dx), dims=(1, 2))
+        dy, dx = col(lambda p: p.dy), col(lambda p: p.dx)
+        m = (yy >= dy) & (yy < H + dy) & (xx >= dx) & (xx < W + dx)
+        mode = plans[0].mode
+        if mode == M.BOX:
+            m = m & (yy >= col(lambda p: p.box[0])) & (yy < col(lambda p: p.box[2])) & (xx >= col(lambda p: p.box[1])) & (xx < col(lambda p: p.box[3]))
+        elif mode == M.CLASS:
+            m = m & (yp >= 0) & (yp <= 255) & torch.gather(sel, 1, yp.clamp(0, 255).view(B, -1)).view(B, 1, H, W).bool()
+        else:
+            m = m & (idp >= 1) & (idp <= cap) & torch.gather(sel, 1, (idp.long() - 1).clamp(0, cap - 1).view(B, -1)).view(B, 1, H, W).bool()
+        Xo = torch.where(m.view(B, H, W, 1) if nhwc else m, Xp, X)
+        yo = torch.where(m, yp, y)
+        if seam is not None:
+            s = torch.zeros_like(m)
+            s[:, :, 1:] |= m[:, :, 1:] != m[:, :, :-1]
+            s[:, :, :-1] |= m[:, :, :-1] != m[:, :, 1:]
+            s[:, :, :, 1:] |= m[:, :, :, 1:] != m[:, :, :, :-1]
+            s[:, :, :, :-1] |= m[:, :, :, :-1] != m[:, :, :, 1:]
+            yo = torch.where(s, torch.full_like(yo, seam), yo)
+        return Xo, yo, m.sum((1, 2, 3)).int()
+
+    for name, X in (("float32", torch.rand((B, C, H, W), generator=g, device="cuda")),
+                    ("uint8  ", torch.randint(0, 256, (B, H, W, C), generator=g, device="cuda", dtype=torch.uint8))):
+        nhwc = X.dtype == torch.uint8
+        for mode in ("cutmix", "classmix", "copy_paste"):
+            for seam in (None, 255):
+                mixer = seg.Mixer(mode, p=1.0, seam_value=seam, flip=True, max_shift=0.25, min_area=64, max_components=cap, seed=0)
+                plans = mixer.plan(B, H, W)
+                Xo, yo = mixer.apply(X, y, plans)
+                last = mixer.last                                   # its launches point into last["tables"], kept alive here
+                pasted = last["pasted"].clone()
+                front = [l for l in last["launches"] if l[0] != "segk_mix_apply"]
+                apply_args = [l for l in last["launches"] if l[0] == "segk_mix_apply"][0][1]
+                scratch = torch.zeros((B,), dtype=torch.int32, device="cuda")
+                args = list(apply_args)
+                args[6] = scratch.data_ptr()                        # pasted is added to: the timed launches add elsewhere
+                t = rounds(lambda: _lib.call("segk_mix_apply", *args), 50)
+                tf = rounds(lambda: [_lib.call(n, *a) for n, a in front], 20)[0] if front else 0.0
+                tcall = rounds(lambda: mixer.apply(X, y, plans), 20)[0]
+                sel = last["tables"][1].long() if mode != "cutmix" else None
+                ids = last["tables"][2] if mode == "copy_paste" else None
+                M_slots = [int(d) for d in np.frombuffer(last["tables"][0][:64 * B].cpu().numpy().tobytes(), dtype=M.DESC)["slot"]]
+                expr = lambda: torch_mix(X, plans, sel, ids, seam, nhwc)
+                Xt, yt, pt = expr()
+                same = torch.equal(Xt.view(torch.uint8), Xo.view(torch.uint8)) and torch.equal(yt, yo) and torch.equal(pt, pasted)
+                tt = rounds(expr, 10)[0]
+                img = B * C * H * W * X.element_size()
+                nbytes = 2 * img + 2 * B * H * W * 8 + (B * H * W * 4 if mode == "copy_paste" else 0)
+                floor = nbytes / (rate * 1e6)
+                say(f"mix {name} {mode:10s} seam {str(seam):4s} apply {t[0]:8.1f} us [{t[1]:.1f}..{t[2]:.1f}]   floor ({nbytes / 1e6:6.2f} MB) {floor:6.1f} us   "
+                    f"apply / floor = {t[0] / floor:5.2f}   select stage {tf:8.1f} us   public call {tcall:8.1f} us   torch {tt:9.1f} us "
+                    f"({'same result' if same else 'RESULT DIFFERS'})   torch / apply = {tt / t[0]:6.1f}   pasted {int(pasted.sum()) / (B * H * W):.2f}")
+    path = os.path.join(ROOT, "profiles", "mix_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def tta():
     """Multi-view prediction through the C ABI (csrc/predict.hip): segk_predict_merge -- mask, colour, class
     counts and confidence in one pass -- at 1200 x 1600, C = 4, V = 1, 2 and 6 views (224 x 224 slots, flips cycling, equal
@@ -1683,6 +1802,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "morph":
         morph()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "mix":
+        mix()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "perturb":
         perturb()
