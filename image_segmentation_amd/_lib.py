@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 329        # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 330        # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
@@ -25,6 +25,11 @@ MIX_NONE, MIX_BOX, MIX_CLASS, MIX_OBJECT = 0, 1, 2, 3      # SEGK_MIX_NONE / _BO
 MIX_TILE_H, MIX_TILE_W = 16, 64            # SEGK_MIX_TILE_H, SEGK_MIX_TILE_W
 MIX_MAX_OBJECTS, MIX_MAX_COMPONENTS = 32, 65536            # SEGK_MIX_MAX_OBJECTS, SEGK_MIX_MAX_COMPONENTS
 MIX_STAGE_BYTES, MIX_STAGE_SELECT = 0, 1   # SEGK_MIX_STAGE_BYTES, SEGK_MIX_STAGE_SELECT
+BOUNDARY_TILE_H, BOUNDARY_TILE_W = 64, 128 # SEGK_BOUNDARY_TILE_H, SEGK_BOUNDARY_TILE_W
+BOUNDARY_MAX_WIDTH, BOUNDARY_BINS = 32, 34 # SEGK_BOUNDARY_MAX_WIDTH, SEGK_BOUNDARY_BINS
+BOUNDARY_HIST_WORDS, BOUNDARY_STAT_WORDS = 544, 656        # SEGK_BOUNDARY_HIST_WORDS, SEGK_BOUNDARY_STAT_WORDS
+# word offsets in the statistics: SEGK_BOUNDARY_BAND_G / _BAND_P / _BAND_I / _CONF / _HD_SUM / _HD_IMAGES / _HD_CAPPED / _HIST
+BOUNDARY_OFFSETS = {"band_g": 0, "band_p": 8, "band_i": 16, "conf": 24, "hd_sum": 88, "hd_images": 96, "hd_capped": 104, "hist": 112}
 # flags of segk_optim_grad_norm (CLIP, SKIP_NONFINITE) and of segk_optim_adamw (NORMED, SKIP_NONFINITE, EMA_WARMUP, SWAP)
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE, OPTIM_NORMED, OPTIM_EMA_WARMUP, OPTIM_SWAP = 1, 2, 1, 4, 8
 
@@ -110,6 +115,8 @@ SIGNATURES = {
     "segk_fill_holes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "segk_mix_select": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "segk_mix_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _l, _vp]),
+    "segk_boundary_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_boundary_finish": (_i, [_vp, _vp, _i, _i, _vp]),
     "segk_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd_bn": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_bn": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),

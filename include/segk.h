@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 329
-#define SEGK_ENTRY_COUNT 118
+#define SEGK_ABI_VERSION 330
+#define SEGK_ENTRY_COUNT 120
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -624,6 +624,44 @@ int segk_mix_select(const segk_mix_desc* descs, int n_desc, int n, const void* y
 int segk_mix_apply(const segk_mix_desc* descs, int n, const void* X, const void* y, void* X_out, void* y_out, int32_t* pasted,
                    int C, int H, int W, int elem_bytes, int label_bytes, const uint8_t* select, int select_stride,
                    const int32_t* ids, int n_slots, int max_components, int has_seam, long seam_value, segk_stream_t s);
+
+/* ---- boundary quality: Boundary IoU, band IoU, contour distances, HD95 (the reference has none of it).  Built
+ * on the primitive of 3.21 and nothing wider: every quantity is an integer count, the result is unique and bit-stable (integer
+ * atomics only, a few per workgroup).  No workgroup waits for another, the host reads nothing back, every device loop is bounded
+ * by an argument or the tile, no float on the device. */
+#define SEGK_BOUNDARY_TILE_H 64
+#define SEGK_BOUNDARY_TILE_W 128
+#define SEGK_BOUNDARY_MAX_WIDTH 32        /* of width and of max_distance */
+#define SEGK_BOUNDARY_BINS 34             /* distance bins 0..32 and room for the overflow bin max_distance + 1 */
+#define SEGK_BOUNDARY_HIST_WORDS (2 * SEGK_MAX_CLASSES * SEGK_BOUNDARY_BINS)   /* [2][8][34]: pred->label, label->pred */
+/* the statistics: int64 words, [8] per class unless said */
+#define SEGK_BOUNDARY_BAND_G 0            /* #{G = c, Dg <= width} */
+#define SEGK_BOUNDARY_BAND_P 8            /* #{P = c, Dp <= width} */
+#define SEGK_BOUNDARY_BAND_I 16           /* #{G = c = P, Dg <= width, Dp <= width} */
+#define SEGK_BOUNDARY_CONF 24             /* [8][8]: #{G = g, P = p, Dg <= width} */
+#define SEGK_BOUNDARY_HD_SUM 88           /* sum over images of the per-image HD95 (whole pixels) */
+#define SEGK_BOUNDARY_HD_IMAGES 96        /* images that sum is over */
+#define SEGK_BOUNDARY_HD_CAPPED 104       /* images whose HD95 fell in the overflow bin */
+#define SEGK_BOUNDARY_HIST 112            /* [2][8][34] */
+#define SEGK_BOUNDARY_STAT_WORDS (SEGK_BOUNDARY_HIST + SEGK_BOUNDARY_HIST_WORDS)
+#define SEGK_BOUNDARY_HALO(width, max_distance) (((width) > (max_distance) ? (width) : (max_distance)) + 1)
+/* dynamic LDS of segk_boundary_stats: 2 C class planes, 2 non-void planes and 2 contour planes of 64-bit words, four words per
+ * staged row */
+#define SEGK_BOUNDARY_LDS_BYTES(C, halo) ((2 * (C) + 4) * (SEGK_BOUNDARY_TILE_H + 2 * (halo)) * 32)
+/* DESIGN.md 3.23 "void", "band distance", "band counts", "band confusion", "contours", "contour distance histogram" for one
+ * image pair.  pred, label [H,W] uint8, only read.  A label >= num_classes or with its bit of ignore_mask (bits 0..7) set is
+ * void in both maps; a pred >= num_classes is void in pred.  The band counts and the confusion are ADDED to stats (int64
+ * [SEGK_BOUNDARY_STAT_WORDS]), the histogram to image_hist (int64 [SEGK_BOUNDARY_HIST_WORDS], zero before the image's first
+ * call; segk_boundary_finish clears it).  1 <= num_classes <= SEGK_MAX_CLASSES; metric SEGK_MORPH_SQUARE / _DIAMOND / _DISK;
+ * 1 <= width, max_distance <= SEGK_BOUNDARY_MAX_WIDTH; image_border 0 | 1; H*W <= SEGK_CC_MAX_PIXELS; stats and image_hist
+ * 8-byte aligned and distinct. */
+int segk_boundary_stats(const uint8_t* pred, const uint8_t* label, int64_t* stats, int64_t* image_hist, int num_classes,
+                        int ignore_mask, int metric, int width, int max_distance, int image_border, int H, int W,
+                        segk_stream_t s);
+/* DESIGN.md 3.23 "per-image HD95": from image_hist per class c < num_classes, n = both directions' total over bins
+ * 0..max_distance + 1; if n > 0, t = the smallest bin with 20 cum >= 19 n: t == max_distance + 1 adds 1 to HD_CAPPED[c], else t
+ * to HD_SUM[c] and 1 to HD_IMAGES[c].  Then stats' histogram += image_hist and image_hist = 0.  One workgroup. */
+int segk_boundary_finish(int64_t* stats, int64_t* image_hist, int num_classes, int max_distance, segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

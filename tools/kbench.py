@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph, mix)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph, boundary, mix)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1337,6 +1337,130 @@ def morph():
     print(f"written to {path}")
 
 
+def boundary():
+    """Boundary quality (csrc/boundary.hip): segk_boundary_stats + segk_boundary_finish through the C ABI on the
+    blob masks with 1 % speckle of the morph bench (the label) and the same blobs moved by (2, 3) with a speckle of their own (the
+    prediction), four classes, at 256 x 256 and 3000 x 4000, width 2 and 7, square band, max_distance 32.  Device events, warmed,
+    seven rounds: median and min..max.  Beside it (1) the yardstick: the route that exists without the fused kernel -- two
+    seg.boundary_distance launches plus the torch comparisons and bincounts that form the band counts ALONE (no confusion, no
+    contours, no histogram); the tool checks that its counts are the fused kernel's; (2) the byte floor, 2 bytes read per pixel
+    over the device-to-device copy rate of a 512 MB buffer; (3) the host path by the host clock: mask.cpu() and scipy.ndimage
+    (binary_erosion for the bands, distance_transform_edt of the complement of each contour set, histograms of the ceilings).
+    Written to profiles/boundary_kbench.txt (or --out)."""
+    import time
+    import numpy as np
+    import image_segmentation_amd as seg
+    from image_segmentation_amd import boundary as B
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    C, R = 4, 32
+    st = ops._stream()
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def speckled(m):
+        hit = torch.rand(m.shape, generator=g, device="cuda") < 0.01
+        return torch.where(hit, torch.randint(0, 4, m.shape, generator=g, device="cuda", dtype=torch.uint8), m)
+
+    def blobs(H, W):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        m = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+        for c, (cy, cx, ry, rx) in ((1, (0.35, 0.3, 0.25, 0.2)), (2, (0.65, 0.7, 0.22, 0.25))):
+            d = ((yy - cy * H) / (ry * H)) ** 2 + ((xx - cx * W) / (rx * W)) ** 2
+            m[d <= 1.0] = c
+            m[(d > 1.0) & (d <= 1.25)] = 3
+        return m
+
+    def host(pred, label, w):
+        """the scipy route: the same integers as the device's, every class, both maps"""
+        p, l = pred.cpu().numpy(), label.cpu().numpy()
+        sq = np.ones((3, 3), dtype=bool)
+        out = []
+        for c in range(C):
+            A, Q = l == c, p == c
+            bg, bp = A & ~ndimage.binary_erosion(A, sq, iterations=w, border_value=1), Q & ~ndimage.binary_erosion(Q, sq, iterations=w, border_value=1)
+            K = []
+            for M in (A, Q):
+                o = ~M
+                near = np.zeros_like(M)
+                near[1:] |= o[:-1]; near[:-1] |= o[1:]; near[:, 1:] |= o[:, :-1]; near[:, :-1] |= o[:, 1:]
+                K.append(M & near)
+            hist = []
+            for src, dst in ((K[1], K[0]), (K[0], K[1])):
+                d = np.ceil(ndimage.distance_transform_edt(~dst)[src] - 1e-9).astype(np.int64) if dst.any() else np.full(int(src.sum()), R + 1)
+                hist.append(np.bincount(np.minimum(d, R + 1), minlength=R + 2))
+            out.append((int(bg.sum()), int(bp.sum()), int((bg & bp).sum()), hist))
+        return out
+
+    say(f"boundary: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz, tile {_lib.BOUNDARY_TILE_H} x {_lib.BOUNDARY_TILE_W}, "
+        f"{C} classes, max_distance {R}" + ("" if ndimage is not None else ", scipy not installed: no host path"))
+    src, dst = torch.empty(1 << 29, dtype=torch.uint8, device="cuda"), torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    tc = rounds(lambda: dst.copy_(src), 5)
+    rate = 2 * src.numel() / tc[0] / 1e6                            # TB/s of the copy (read + write)
+    del src, dst
+    say(f"boundary: device-to-device copy of 512 MB: {rate:.2f} TB/s")
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None       # one size, e.g. 3000x4000
+    for H, W in ((256, 256), (3000, 4000)):
+        if only is not None and only != f"{H}x{W}":
+            continue
+        iters = 50 if H * W <= 1 << 20 else 5
+        base = blobs(H, W)
+        label, pred = speckled(base), speckled(torch.roll(base, (2, 3), (0, 1)))
+        for w in (2, 7):
+            acc = B.BoundaryStats.zeros(C, R, "cuda")
+
+            def fused():
+                _lib.call("segk_boundary_stats", pred.data_ptr(), label.data_ptr(), acc.words.data_ptr(), acc.image_hist.data_ptr(), C, 0, 0, w, R,
+                          0, H, W, st)
+                _lib.call("segk_boundary_finish", acc.words.data_ptr(), acc.image_hist.data_ptr(), C, R, st)
+
+            def route():                                            # what forms band_g / band_p / band_i without the fused kernel
+                dg = seg.boundary_distance(label, w, shape="square").view(torch.int16) != -1
+                dp = seg.boundary_distance(pred, w, shape="square").view(torch.int16) != -1
+                return (torch.bincount(label[dg].long(), minlength=C), torch.bincount(pred[dp].long(), minlength=C),
+                        torch.bincount(label[dg & dp & (label == pred)].long(), minlength=C))
+
+            one = seg.boundary_stats(pred, label, C, w, R, image_border=False)
+            for got, want in zip(route(), (one.band_g, one.band_p, one.band_i)):
+                assert torch.equal(got, want[:C]), "the yardstick and the fused kernel disagree"
+            t, ty = rounds(fused, iters), rounds(route, iters)
+            tcall = rounds(lambda: seg.boundary_stats(pred, label, C, w, R, image_border=False, out=acc), iters)[0]
+            floor = 2 * H * W / (rate * 1e6)
+            line = (f"boundary {H}x{W} width={w} stats+finish {t[0]:9.1f} us [{t[1]:.1f}..{t[2]:.1f}]   yardstick (2 distance launches + torch "
+                    f"band counts) {ty[0]:9.1f} us [{ty[1]:.1f}..{ty[2]:.1f}]   yardstick / fused = {ty[0] / t[0]:6.2f}   floor ({2 * H * W / 1e6:6.2f} MB) "
+                    f"{floor:6.2f} us   fused / floor = {t[0] / floor:7.1f}   public call {tcall:8.1f} us")
+            if ndimage is not None:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = host(pred, label, w)
+                th = (time.perf_counter() - t0) * 1e6
+                hist = one.hist.cpu().numpy()
+                for c, (bg, bp, bi, hh) in enumerate(res):
+                    assert (bg, bp, bi) == (int(one.band_g[c]), int(one.band_p[c]), int(one.band_i[c])), "scipy and the device disagree on the band"
+                    assert np.array_equal(hh[0], hist[0, c]) and np.array_equal(hh[1], hist[1, c]), "scipy and the device disagree on the contours"
+                line += f"   host {th:12.1f} us   host / fused = {th / t[0]:9.1f}"
+            say(line)
+        del base, label, pred
+    path = os.path.join(ROOT, "profiles", "boundary_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def mix():
     """Mixed-sample augmentation (csrc/mix.hip) through image_segmentation_amd.mix at the bench batch, B = 32,
     3 x 256 x 256, int64 labels: float32 NCHW and uint8 NHWC images, each mode (every sample mixed, flips drawn, shifts for
@@ -1802,6 +1926,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "morph":
         morph()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "boundary":
+        boundary()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mix":
         mix()
