@@ -26,6 +26,7 @@ from .morph import (erode, dilate, open_mask, close_mask, label_band, boundary_d
 from .mix import Mixer, MixPlan, MixedBatches                                                                      # noqa: F401
 from .panoptic import match_objects, ObjectMatch, PanopticQuality, object_quality, quality_from_stats              # noqa: F401
 from .boundary import boundary_stats, BoundaryStats, BoundaryQuality, boundary_quality, quality_from_boundary_stats  # noqa: F401
+from .superpixels import superpixels, snap_mask, Superpixels, Snapped, Snap                                         # noqa: F401
 from .calibration import (Reliability, reliability, TemperatureFit, fit_temperature, refine_temperature,            # noqa: F401
                           default_temperatures, inverse_temperatures, fit_from_counts)
 from .distill import Teacher, TeacherViews, DistillLoss, teacher_table, TEACHER_DESC                                 # noqa: F401

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsegk.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 330        # SEGK_ABI_VERSION of the include/segk.h this table was written against
+ABI_VERSION = 340        # SEGK_ABI_VERSION of the include/segk.h this table was written against
 MAX_CLASSES = 8
 MAX_VIEWS = 16           # SEGK_MAX_VIEWS
 MAX_TEMPS = 32           # SEGK_MAX_TEMPS
@@ -30,6 +30,12 @@ BOUNDARY_MAX_WIDTH, BOUNDARY_BINS = 32, 34 # SEGK_BOUNDARY_MAX_WIDTH, SEGK_BOUND
 BOUNDARY_HIST_WORDS, BOUNDARY_STAT_WORDS = 544, 656        # SEGK_BOUNDARY_HIST_WORDS, SEGK_BOUNDARY_STAT_WORDS
 # word offsets in the statistics: SEGK_BOUNDARY_BAND_G / _BAND_P / _BAND_I / _CONF / _HD_SUM / _HD_IMAGES / _HD_CAPPED / _HIST
 BOUNDARY_OFFSETS = {"band_g": 0, "band_p": 8, "band_i": 16, "conf": 24, "hd_sum": 88, "hd_images": 96, "hd_capped": 104, "hist": 112}
+SLIC_TILE, SLIC_MAX_CELLS = 64, 18          # SEGK_SLIC_TILE, SEGK_SLIC_MAX_CELLS
+SLIC_TILE_ROWS = (64, 16, 4)               # the tile_rows segk_slic_assign and segk_snap_vote take
+SLIC_MIN_STEP, SLIC_MAX_STEP = 4, 64       # SEGK_SLIC_MIN_STEP, SEGK_SLIC_MAX_STEP
+SLIC_MAX_COMPACTNESS, SLIC_MAX_ITERATIONS, SLIC_MAX_SIDE = 255, 20, 1 << 27    # SEGK_SLIC_MAX_COMPACTNESS / _ITERATIONS / _SIDE
+SLIC_SPACES = {"rgb": 0, "ycc": 1}         # SEGK_SLIC_RGB / _YCC
+SLIC_CENTRE_WORDS, SLIC_SUM_WORDS, SNAP_NONE = 5, 8, 255   # SEGK_SLIC_CENTRE_WORDS, SEGK_SLIC_SUM_WORDS, SEGK_SNAP_NONE
 # flags of segk_optim_grad_norm (CLIP, SKIP_NONFINITE) and of segk_optim_adamw (NORMED, SKIP_NONFINITE, EMA_WARMUP, SWAP)
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE, OPTIM_NORMED, OPTIM_EMA_WARMUP, OPTIM_SWAP = 1, 2, 1, 4, 8
 
@@ -117,6 +123,11 @@ SIGNATURES = {
     "segk_mix_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _l, _vp]),
     "segk_boundary_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_boundary_finish": (_i, [_vp, _vp, _i, _i, _vp]),
+    "segk_slic_start": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_slic_assign": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "segk_slic_update": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "segk_snap_vote": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "segk_snap_paint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _i, _i, _i, _i, _vp]),
     "segk_head_fwd": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_fwd_bn": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "segk_head_bwd_bn": (_i, [_fp, _vp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _vp]),

@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["api.hip", "conv_igemm.hip", "conv_pipe.hip", "conv_ws.hip", "conv_rs.hip", "convt_stream.hip", "stem.hip", "wgrad.hip", "bn_pool.hip", "pack.hip", "head.hip", "loss.hip", "distill.hip", "hard_loss.hip", "lovasz.hip", "recon.hip", "prompt.hip", "augment.hip", "perturb.hip", "components.hip", "vectors.hip", "raster.hip", "panoptic.hip", "morph.hip", "boundary.hip", "mix.hip", "resize.hip", "predict.hip", "calib.hip", "tiles.hip", "vit.hip", "gemm.hip", "optim.hip", "probe.hip"]
+SOURCES = ["api.hip", "conv_igemm.hip", "conv_pipe.hip", "conv_ws.hip", "conv_rs.hip", "convt_stream.hip", "stem.hip", "wgrad.hip", "bn_pool.hip", "pack.hip", "head.hip", "loss.hip", "distill.hip", "hard_loss.hip", "lovasz.hip", "recon.hip", "prompt.hip", "augment.hip", "perturb.hip", "components.hip", "vectors.hip", "raster.hip", "panoptic.hip", "morph.hip", "boundary.hip", "slic.hip", "mix.hip", "resize.hip", "predict.hip", "calib.hip", "tiles.hip", "vit.hip", "gemm.hip", "optim.hip", "probe.hip"]
 LIB = os.path.join(CSRC, "libsegk.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

@@ -32,6 +32,7 @@ from .augment import _upload
 from .clipunet import ClipUNet
 from .components import Components, as_clean, components as _components
 from .morph import as_morph
+from .superpixels import as_snap
 from .vectors import as_vectors, vectorize as _vectorize
 from . import utils as U
 
@@ -64,12 +65,13 @@ class Prediction:
     counts: torch.Tensor                    # int64 [C] pixels per predicted class
     confusion: Optional[torch.Tensor]       # int64 [C,C], [pred][label]; None without labels
     meta: dict                              # the resize / padding record of process_batch_forward
-    raw_mask: Optional[torch.Tensor] = None         # with morph= or clean=: the argmax (mask is the finished one)
+    raw_mask: Optional[torch.Tensor] = None         # with snap=, morph= or clean=: the argmax (mask is the finished one)
     components: Optional[Components] = None    # with clean=: the components of the mask it was given (components.py)
     # set on merged views, None otherwise; attributes, not dataclass fields: the constructor stays as it was
     confidence = None                          # uint8 [H,W], (uint8)(255 p_best + 0.5)
     scores = None                              # Segmenter(return_scores=True): float32 [C,H,W], the merged probabilities
     vectors = None                             # Segmenter(vectors=...): the vectors.Vectors of `mask`
+    superpixels = None                         # Segmenter(snap=...): the superpixels.Superpixels of the input image
 
 
 def _num_classes(model):
@@ -285,6 +287,11 @@ class Segmenter:
               ("erode", "dilate", "open", "close", "fill_holes", "label_band"): the steps are applied in order to the argmax
               mask on the device, before clean=; Prediction.mask, color, counts and confusion describe the
               final mask, raw_mask is the argmax
+    snap=     None (every output as without it), or a superpixels.Snap / a dict of its keywords (step, compactness, iterations,
+              space, classes, min_share, fill, weighted): the argmax is snapped to the SLIC superpixels of the input image on
+              the device, before morph= and clean=; the images are then uint8 [H,W,C] / [H,W], a float image is
+              refused before the forward.  weighted=True lets a vote weigh the confidence map and needs a route that writes one
+              (merged views or tiles).  Prediction.superpixels holds the Superpixels, raw_mask the argmax
 
     Merged views (without them every output and the code path are as above):
     model     a list of models is an ensemble: same class count, same input arity, all on one device
@@ -318,7 +325,7 @@ class Segmenter:
 
     def __init__(self, model, target_size=224, interpolation="bilinear", palette=COLOR_MAP, batch_size=32, antialias=None,
                  sigma=3.0, clean=None, tta=None, model_weights=None, outputs=None, return_scores=False, tiles=None,
-                 temperature=None, vectors=None, morph=None):
+                 temperature=None, vectors=None, morph=None, snap=None):
         models = list(model) if isinstance(model, (list, tuple)) else [model]
         if not models:
             raise ValueError("an ensemble needs at least one model")
@@ -326,6 +333,7 @@ class Segmenter:
         self.clean = as_clean(clean)
         self.vectors = as_vectors(vectors)
         self.morph = as_morph(morph)
+        self.snap = as_snap(snap)
         if not float(sigma) > 0:
             raise ValueError(f"sigma must be positive, got {sigma}")
         self.sigma = float(sigma)
@@ -350,6 +358,9 @@ class Segmenter:
             return
         self._merged = tta is not None or len(models) > 1 or self.return_scores
         if not self._merged:
+            if self.snap is not None and self.snap.weighted:
+                raise ValueError("snap: weighted=True weighs the votes by the confidence map, which this route does not write: "
+                                 "pass tta=, several models, return_scores=True or tiles=")
             if model_weights is not None or outputs is not None:
                 raise ValueError("model_weights= and outputs= belong to merged views: pass tta= or several models")
             self._init_temperature(temperature, ["probs" if _is_prompt_model(model) else "logits"])
@@ -431,6 +442,11 @@ class Segmenter:
             raise ValueError(f"{len(heatmaps)} heatmaps for {n} images")
         if labels is not None and len(labels) != n:
             raise ValueError(f"{len(labels)} label maps for {n} images")
+        if self.snap is not None:
+            for k, im in enumerate(images):
+                if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8:
+                    raise ValueError(f"image {k}: snap= takes the superpixels of a uint8 [H,W,C] image, got "
+                                     f"{getattr(im, 'dtype', type(im).__name__)} {tuple(getattr(im, 'shape', ()))}")
         params = [next(m.parameters(), None) for m in self.models]
         if any(p is None for p in params):
             raise ValueError("the model has no parameters")
@@ -465,12 +481,13 @@ class Segmenter:
         _check_classes(C, pal)
         return pal
 
-    def _finish(self, dev, C, pal, metas, labels, launch, confident):
+    def _finish(self, dev, C, pal, metas, labels, launch, confident, images):
         """The per-image end of every route: allocate the outputs, load the label map, run the route's one kernel and build
         the Prediction.  launch(k, mask, outs, conf, scores) is that kernel for image k, on pointers: outs = (color, palette,
-        counts, labels, confusion), all null with morph= or clean= -- the kernel then writes the argmax (and confidence / scores)
-        alone, and colour, counts and confusion counts come from the finished mask afterwards.  confident: the route writes a
-        confidence map (and scores on request); metas[k]["original_size"] is the size of output k."""
+        counts, labels, confusion), all null with snap=, morph= or clean= -- the kernel then writes the argmax (and confidence /
+        scores) alone, and colour, counts and confusion counts come from the finished mask afterwards.  confident: the route
+        writes a confidence map (and scores on request); metas[k]["original_size"] is the size of output k; images: the device
+        images, which snap= takes its superpixels from."""
         n = len(metas)
         counts = torch.zeros((n, _lib.MAX_CLASSES), dtype=torch.int64, device=dev)
         M = torch.zeros((n, _lib.MAX_CLASSES, _lib.MAX_CLASSES), dtype=torch.int64, device=dev) if labels is not None else None
@@ -485,12 +502,15 @@ class Segmenter:
             lab = None if labels is None else _label_on(labels[k], (oh, ow), dev, k)
             outs = (ops._p(color), ops._p(pal), counts[k].data_ptr(), ops._p(lab), ops._p(None if M is None else M[k]))
             Mk = None if M is None else M[k, :C, :C]
-            if cl is None and not self.morph:
+            if cl is None and not self.morph and self.snap is None:
                 launch(k, mask.data_ptr(), outs, ops._p(conf), ops._p(scores))
                 pred = Prediction(mask, color, counts[k, :C], Mk, meta)
             else:
                 launch(k, mask.data_ptr(), (0,) * 5, ops._p(conf), ops._p(scores))
-                final, comps = mask, None
+                final, comps, sp = mask, None, None
+                if self.snap is not None:
+                    sp, snapped = self.snap(images[k], mask, conf)
+                    final = snapped.mask
                 for step in self.morph or ():
                     final = step(final)
                 if cl is not None:
@@ -498,6 +518,7 @@ class Segmenter:
                     final = comps.mask
                 _lib.call("segk_mask_finish", final.data_ptr(), *outs, C, oh, ow, s)
                 pred = Prediction(final, color, counts[k, :C], Mk, meta, mask, comps)
+                pred.superpixels = sp
             if confident:
                 pred.confidence, pred.scores = conf, scores
             if self.vectors is not None:
@@ -519,7 +540,7 @@ class Segmenter:
             pl, pt, _, _ = metas[k]["pad"]
             _lib.call("segk_predict_mask", y[k].data_ptr(), mask, *outs, C, T, pt, pl, *metas[k]["new_size"],
                       *metas[k]["original_size"], mode, s)
-        return self._finish(dev, C, pal, metas, labels, launch, False)
+        return self._finish(dev, C, pal, metas, labels, launch, False, images)
 
     def _chunk_merged(self, dev, images, heatmaps, labels):
         """The merged-views form of _chunk: one forward per view over the whole chunk, one table upload for all its images,
@@ -563,7 +584,7 @@ class Segmenter:
                       *first[k]["original_size"], mask, *outs, conf, scores, s)
         # the slots and the table (table_dev) are read by launches still in flight: the caching allocator keeps them valid
         # in stream order, as it does for the batch of the single-view path
-        return self._finish(dev, C, pal, first, labels, launch, True)
+        return self._finish(dev, C, pal, first, labels, launch, True, images)
 
     def _tiled(self, dev, images, heatmaps, points, labels):
         """The tiled route: forwards of at most batch_size tiles, filled across consecutive images (at least one image); an
@@ -642,7 +663,7 @@ class Segmenter:
             _lib.call("segk_predict_tiles", Ys[k].data_ptr(), C, kind, merge, window, *plans[k][:2], T, overlap, mask, *outs,
                       conf, scores, s)
         # the tile outputs are read by launches still in flight: the caching allocator keeps them valid in stream order
-        return self._finish(dev, C, pal, metas, labels, launch, True)
+        return self._finish(dev, C, pal, metas, labels, launch, True, images)
 
 
 def predict(model, images, heatmaps=None, labels=None, points=None, **kw):

@@ -32,8 +32,8 @@ typedef void* segk_stream_t; /* hipStream_t */
 
 /* ABI version and the number of entry points this header declares: segk_version() / segk_entry_count() of a library
  * must equal them (image_segmentation_amd/_lib.py refuses a library whose values differ from the table it binds) */
-#define SEGK_ABI_VERSION 330
-#define SEGK_ENTRY_COUNT 120
+#define SEGK_ABI_VERSION 340
+#define SEGK_ENTRY_COUNT 125
 int segk_version(void);
 int segk_entry_count(void);
 /* first 16 hex digits of the sha256 over the sources this library was built from (image_segmentation_amd/build.py:
@@ -662,6 +662,56 @@ int segk_boundary_stats(const uint8_t* pred, const uint8_t* label, int64_t* stat
  * 0..max_distance + 1; if n > 0, t = the smallest bin with 20 cum >= 19 n: t == max_distance + 1 adds 1 to HD_CAPPED[c], else t
  * to HD_SUM[c] and 1 to HD_IMAGES[c].  Then stats' histogram += image_hist and image_hist = 0.  One workgroup. */
 int segk_boundary_finish(int64_t* stats, int64_t* image_hist, int num_classes, int max_distance, segk_stream_t s);
+
+/* ---- superpixels: SLIC in the pixel-centric integer form, and snapping a mask to a segmentation by a per-segment vote
+ * (the reference has none of it: this replaces an image.cpu() + skimage.segmentation.slic pass and a host
+ * loop over segments).  Integer arithmetic only, ties go to the lowest index, the sums are integer atomics (a few per
+ * workgroup): results are unique and bit-stable.  No workgroup waits for another, the host reads nothing back, no float on
+ * the device, every device loop is bounded by the step, the tile or 9. */
+#define SEGK_SLIC_TILE 64                 /* segk_slic_assign / segk_snap_vote: one workgroup of 256 per tile_rows x 64 pixels;
+                                             tile_rows is 4, 16 or SEGK_SLIC_TILE and never shows in a result: the host takes
+                                             fewer rows for a small image, so that it still fills the device */
+#define SEGK_SLIC_MAX_CELLS 18            /* cells per side a tile and its one-cell ring touch (at step 4) */
+#define SEGK_SLIC_MIN_STEP 4
+#define SEGK_SLIC_MAX_STEP 64
+#define SEGK_SLIC_MAX_COMPACTNESS 255
+#define SEGK_SLIC_MAX_ITERATIONS 20
+#define SEGK_SLIC_MAX_SIDE (1 << 27)      /* 16 H and 16 W fit an int32 centre */
+#define SEGK_SLIC_RGB 0
+#define SEGK_SLIC_YCC 1
+#define SEGK_SLIC_CENTRE_WORDS 5          /* Y, X, C0, C1, C2 in 1/16 units */
+#define SEGK_SLIC_SUM_WORDS 8             /* n, sum of y - (i - 1) S, of x - (j - 1) S, of c0, c1, c2, two unused words */
+#define SEGK_SNAP_NONE 255                /* paint[k] of a segment that is not painted */
+/* DESIGN.md 3.24 "features", "grid", "start centre".  image [H,W,C] uint8, C in {1, 3, 4} (a fourth channel is ignored), only
+ * read.  K = ceil(H / step) ceil(W / step).  centres int32 [K][5] = the start centres; sums int32 [K][8] = 0.  space
+ * SEGK_SLIC_RGB | _YCC; SEGK_SLIC_MIN_STEP <= step <= SEGK_SLIC_MAX_STEP; H*W <= SEGK_CC_MAX_PIXELS; H, W <=
+ * SEGK_SLIC_MAX_SIDE; centres 4-byte, sums 16-byte aligned. */
+int segk_slic_start(const uint8_t* image, int32_t* centres, int32_t* sums, int C, int space, int step, int H, int W, int K,
+                    segk_stream_t s);
+/* DESIGN.md 3.24 "assignment", "sums": round `round` (0 .. iterations - 1) of `iterations` (1 .. SEGK_SLIC_MAX_ITERATIONS).
+ * Every pixel takes the candidate of smallest D, the lowest index on a tie; n and the sums of its pixels are ADDED to
+ * sums[k] (positions as offsets from the origin of the cell before the home cell, so they fit 32 bits).  labels int32 [H,W]
+ * is written in the last round only.  1 <= compactness <= SEGK_SLIC_MAX_COMPACTNESS; tile_rows 4, 16 or SEGK_SLIC_TILE; the
+ * rest as segk_slic_start; labels 4-byte aligned.  Uses no dynamic LDS. */
+int segk_slic_assign(const uint8_t* image, const int32_t* centres, int32_t* sums, int32_t* labels, int C, int space, int step,
+                     int compactness, int round, int iterations, int tile_rows, int H, int W, int K, segk_stream_t s);
+/* DESIGN.md 3.24 "update": counts[k] = n; with n > 0 every component of centres[k] = floor((32 sum + n) / (2 n)) of the
+ * true sum, else it stays; sums[k] = 0.  K threads. */
+int segk_slic_update(int32_t* centres, int32_t* sums, int32_t* counts, int step, int H, int W, int K, segk_stream_t s);
+/* DESIGN.md 3.24 "vote": hist int64 [K][8] (the caller zeroes it): hist[labels[p]][mask[p]] += weights ? weights[p] : 1 for
+ * the pixels with 0 <= labels[p] < K and mask[p] < 8 with its bit of classes_mask (1..255) set.  labels int32 [H,W], mask
+ * and weights (may be NULL) uint8 [H,W], only read.  1 <= K <= SEGK_CC_MAX_PIXELS >= H*W; tile_rows 4, 16 or SEGK_SLIC_TILE;
+ * hist 8-byte, labels 4-byte aligned. */
+int segk_snap_vote(const int32_t* labels, const uint8_t* mask, const uint8_t* weights, int64_t* hist, int classes_mask,
+                   int tile_rows, int H, int W, int K, segk_stream_t s);
+/* DESIGN.md 3.24 "winner", "snap".  winner int32 [K] = the class of the largest entry of hist[k], the lowest on a tie, -1 for
+ * a row of zeros; paint uint8 [K] (scratch) = winner[k] when 256 hist[k][winner] >= min_share sum_c hist[k][c], else
+ * SEGK_SNAP_NONE.  out [H,W] uint8 = paint[labels[p]] where 0 <= labels[p] < K, that is not SEGK_SNAP_NONE and bit mask[p] of
+ * the 256-bit set allow0..allow3 (allow0 bit 0 = value 0) is set; else mask[p].  0 <= min_share <= 256; out is neither mask
+ * nor paint; hist 8-byte, labels and winner 4-byte aligned.  Two launches. */
+int segk_snap_paint(const int32_t* labels, const uint8_t* mask, const int64_t* hist, int32_t* winner, uint8_t* paint,
+                    uint8_t* out, long allow0, long allow1, long allow2, long allow3, int min_share, int H, int W, int K,
+                    segk_stream_t s);
 
 /* ---- output head: Conv2d(C, ncls, 1) (unet.py:91,105; clipunet.py:181,187) ----------------------- */
 /* y NHWC [B,H,W,Cp] -> logits NCHW fp32 [B,ncls,H,W];  w fp32 [ncls][C], bias [ncls] */

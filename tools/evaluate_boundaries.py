@@ -7,7 +7,10 @@ images whose HD95 lies past --max-distance, per class, and their means.
 Usage: python tools/evaluate_boundaries.py --checkpoint F --images DIR --labels DIR --classes 4 --ignore-index 3 --out FILE.json
 --open R / --close R / --min-area N shape every predicted mask on the device first (--morph-classes names
 the classes they act on, default every class but 0), so two runs with and without them tell what the post-process does to the
-contour.  --width W fixes the band's half-width (default: 2 % of each image's diagonal, the published rule, at most 32)."""
+contour.  --width W fixes the band's half-width (default: 2 % of each image's diagonal, the published rule, at most 32).
+--snap STEP / --snap-share F / --snap-compactness M / --snap-weighted snap every predicted mask to the SLIC superpixels of its
+image before that (the flags of tools/predict.py): two runs tell what snapping does to Boundary IoU and HD95.
+--snap-weighted runs the single view through the merged route, which writes the confidence map the votes weigh."""
 import argparse
 import os
 import sys
@@ -47,7 +50,16 @@ def main():
     ap.add_argument("--morph-classes", default=None, metavar="CLASSES", help="comma-separated classes (default: all but 0)")
     ap.add_argument("--morph-shape", choices=["disk", "square", "diamond"], default="disk")
     ap.add_argument("--connectivity", type=int, choices=[4, 8], default=4)
+    ap.add_argument("--snap", type=int, default=None, metavar="STEP", help="snap the mask to SLIC superpixels of this spacing (4..64)")
+    ap.add_argument("--snap-share", type=float, default=0.5, metavar="F", help="share of a superpixel's votes its winner needs")
+    ap.add_argument("--snap-compactness", type=int, default=20, metavar="M", help="1..255: larger keeps superpixels square")
+    ap.add_argument("--snap-weighted", action="store_true", help="a vote weighs the confidence map")
     args = ap.parse_args()
+    snap = None
+    if args.snap is not None:
+        snap = dict(step=args.snap, compactness=args.snap_compactness, min_share=args.snap_share, weighted=args.snap_weighted)
+    elif args.snap_weighted or args.snap_share != 0.5 or args.snap_compactness != 20:
+        ap.error("--snap-share, --snap-compactness and --snap-weighted need --snap STEP")
     morph = None
     if args.open or args.close:
         mcls = ints_of(ap, args.morph_classes, "--morph-classes") if args.morph_classes else tuple(range(1, args.classes))
@@ -72,6 +84,7 @@ def main():
         bq = seg.BoundaryQuality(args.classes, args.ignore_index, args.width, args.max_distance, ints_of(ap, args.tolerances, "--tolerances"),
                                  args.shape, not args.no_image_border)
         segmenter_morph = seg.morph.as_morph(morph) if morph is not None else None
+        snap = seg.Snap(**snap) if snap is not None else None
     except ValueError as e:
         ap.error(str(e))
     names = sorted(f for f in os.listdir(args.images) if f.lower().endswith(EXT))
@@ -82,7 +95,8 @@ def main():
     model = seg.unet(3, args.classes) if args.model == "unet" else seg.SegmentationAutoencoder(3, num_classes=args.classes)
     model = seg.load_checkpoint(model, args.checkpoint).cuda()
     segmenter = seg.Segmenter(model, target_size=args.size, interpolation=args.interpolation, palette=None, batch_size=args.batch_size,
-                              clean=clean, morph=segmenter_morph)
+                              clean=clean, morph=segmenter_morph, snap=snap,
+                              tta=dict(flips=("",)) if snap is not None and snap.weighted else None)
     for i in range(0, len(pairs), args.batch_size):
         batch = pairs[i:i + args.batch_size]
         preds = segmenter([np.asarray(Image.open(p).convert("RGB")) for p, _ in batch])
@@ -93,7 +107,9 @@ def main():
                 ap.error(f"{l}: {e}")
     out = bq.compute()
     out.update(ignore_index=args.ignore_index, width=args.width, shape=args.shape, image_border=not args.no_image_border,
-               open=args.open, close=args.close, min_area=args.min_area)
+               open=args.open, close=args.close, min_area=args.min_area, snap=args.snap,
+               snap_share=args.snap_share if args.snap is not None else None,
+               snap_compactness=args.snap_compactness if args.snap is not None else None, snap_weighted=args.snap_weighted)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
     show = lambda v: "-" if v is None else f"{v:.4f}"

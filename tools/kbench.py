@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels at U-Net layer shapes (B=32, 256x256 input): conv3x3 forward /
 weight-gradient through the C ABI.  Usage: python tools/kbench.py [conv|wgrad|all] [--iters N]
-(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph, boundary, mix)"""
+(other families: ends, convt, bn, loss, head, recon, vit, stem, pack, predict, prompt, augment, perturb, components, vectors, tta, tiles, calib, distill, hardloss, lovasz, optim, raster, pq, morph, boundary, slic, mix)"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1461,6 +1461,82 @@ def boundary():
     print(f"written to {path}")
 
 
+def slic():
+    """Superpixels (csrc/slic.hip) at 256 x 256 and 3000 x 4000 on an RGB image of smooth colour fields with
+    noise, step 16, compactness 20, "ycc", 10 iterations: segk_slic_assign alone (a middle round: no labels written, and the
+    last one), a whole seg.superpixels call (21 launches), and vote + snap (seg.snap_mask on a four-class blob mask moved by
+    two pixels, weighted).  Device events, warmed, seven rounds: median and min..max.  Beside it the byte floor of a whole call
+    -- the image read T times plus the labels written once, over the device-to-device copy rate of a 512 MB buffer -- and the
+    pixels x candidates per second of the assign kernel.  Written to profiles/slic_kbench.txt (or --out)."""
+    import image_segmentation_amd as seg
+    S, m, T, space = 16, 20, 10, "ycc"
+    st = ops._stream()
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def rounds(fn, iters):
+        t = sorted(timeit(fn, iters) for _ in range(7))
+        return t[3], t[0], t[-1]
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def picture(H, W):
+        yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32),
+                                indexing="ij")
+        chans = [128 + 100 * torch.sin(yy / (0.07 * H) + k) * torch.cos(xx / (0.05 * W) - k) for k in range(3)]
+        img = torch.stack(chans, dim=-1) + 12 * torch.randn((H, W, 3), generator=g, device="cuda")
+        mask = ((torch.sin((yy + 2) / (0.07 * H)) > 0).to(torch.uint8) + 2 * (torch.cos(xx / (0.05 * W)) > 0).to(torch.uint8))
+        return img.clamp(0, 255).to(torch.uint8).contiguous(), torch.roll(mask, 2, 1).contiguous()
+
+    say(f"slic: build {_lib.build_id()}, clock probe {ops.clock_probe()['median_ghz']} GHz, tile {_lib.SLIC_TILE} x {_lib.SLIC_TILE}, step {S}, "
+        f"compactness {m}, {space}, {T} iterations")
+    src, dst = torch.empty(1 << 29, dtype=torch.uint8, device="cuda"), torch.empty(1 << 29, dtype=torch.uint8, device="cuda")
+    tc = rounds(lambda: dst.copy_(src), 5)
+    rate = 2 * src.numel() / tc[0] / 1e6                            # TB/s of the copy (read + write)
+    del src, dst
+    say(f"slic: device-to-device copy of 512 MB: {rate:.2f} TB/s")
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None       # one size, e.g. 3000x4000
+    for H, W in ((256, 256), (3000, 4000)):
+        if only is not None and only != f"{H}x{W}":
+            continue
+        iters = 50 if H * W <= 1 << 20 else 5
+        img, mask = picture(H, W)
+        sp = seg.superpixels(img, S, m, T, space)
+        conf = torch.randint(0, 256, (H, W), generator=g, device="cuda", dtype=torch.uint8)
+        K = sp.k
+        sums = torch.zeros((K, _lib.SLIC_SUM_WORDS), dtype=torch.int32, device="cuda")
+        labels = torch.empty((H, W), dtype=torch.int32, device="cuda")
+
+        SP = sys.modules["image_segmentation_amd.superpixels"]
+        chosen = SP.tile_rows(H, W)
+
+        def assign(rnd, rows):
+            def f():                                                # on the converged centres; the sums grow, which costs the same
+                _lib.call("segk_slic_assign", img.data_ptr(), sp.centres.data_ptr(), sums.data_ptr(), labels.data_ptr(), 3,
+                          _lib.SLIC_SPACES[space], S, m, rnd, T, rows, H, W, K, st)
+            return f
+        ta, tl = rounds(assign(0, chosen), iters), rounds(assign(T - 1, chosen), iters)
+        per_rows = "  ".join(f"{rows} rows {rounds(assign(0, rows), iters)[0]:.1f} us" for rows in _lib.SLIC_TILE_ROWS)
+        say(f"slic {H}x{W} assign by tile height (the host layer takes {chosen}): {per_rows}")
+        tcall = rounds(lambda: seg.superpixels(img, S, m, T, space), max(iters // 5, 2))
+        tsnap = rounds(lambda: seg.snap_mask(mask, sp, min_share=0.5, weights=conf), iters)
+        floor = (T * 3 + 4) * H * W / (rate * 1e6)
+        say(f"slic {H}x{W} K={K}  assign {ta[0]:9.1f} us [{ta[1]:.1f}..{ta[2]:.1f}] = {9 * H * W / ta[0] / 1e3:7.2f} G candidates/s   assign + labels "
+            f"{tl[0]:9.1f} us [{tl[1]:.1f}..{tl[2]:.1f}]   superpixels() {tcall[0]:9.1f} us [{tcall[1]:.1f}..{tcall[2]:.1f}]   byte floor "
+            f"({(T * 3 + 4) * H * W / 1e6:7.2f} MB) {floor:7.2f} us   call / floor = {tcall[0] / floor:7.1f}   snap_mask (vote + winner + paint) "
+            f"{tsnap[0]:9.1f} us [{tsnap[1]:.1f}..{tsnap[2]:.1f}]")
+        del img, mask, sp, conf, sums, labels
+    path = os.path.join(ROOT, "profiles", "slic_kbench.txt")
+    if "--out" in sys.argv:
+        path = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"written to {path}")
+
+
 def mix():
     """Mixed-sample augmentation (csrc/mix.hip) through image_segmentation_amd.mix at the bench batch, B = 32,
     3 x 256 x 256, int64 labels: float32 NCHW and uint8 NHWC images, each mode (every sample mixed, flips drawn, shifts for
@@ -1929,6 +2005,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "boundary":
         boundary()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "slic":
+        slic()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mix":
         mix()

@@ -25,7 +25,11 @@ hole, its uncompressed RLE -- built on the device.  --coco-cate
 ids (the class number) and names; the default is every class but 0 under its class name.
 --open R / --close R / --fill-holes shape every mask on the device before the clean-up, in that order (spurs and
 bridges thinner than the element go, cracks close, holes fill); --morph-classes 1,2 names the classes they act on (default:
-every class but 0, closing and filling one class at a time), --morph-shape {disk,square,diamond} the element."""
+every class but 0, closing and filling one class at a time), --morph-shape {disk,square,diamond} the element.
+--snap STEP snaps every mask to the SLIC superpixels of its image (grid spacing STEP, 4..64) before all of that (DESIGN.md
+3.24): a superpixel whose winning class holds at least --snap-share F of its votes (default 0.5) takes that class;
+--snap-compactness M (1..255, default 20) trades colour against squareness, --snap-weighted lets a vote weigh the confidence
+map (merged views or --tile only)."""
 import argparse
 import os
 import sys
@@ -70,6 +74,10 @@ def main():
     ap.add_argument("--fill-holes", action="store_true", help="fill the holes of every class")
     ap.add_argument("--morph-classes", default=None, metavar="CLASSES", help="comma-separated classes (default: all but 0)")
     ap.add_argument("--morph-shape", choices=["disk", "square", "diamond"], default="disk")
+    ap.add_argument("--snap", type=int, default=None, metavar="STEP", help="snap the mask to SLIC superpixels of this spacing (4..64)")
+    ap.add_argument("--snap-share", type=float, default=0.5, metavar="F", help="share of a superpixel's votes its winner needs")
+    ap.add_argument("--snap-compactness", type=int, default=20, metavar="M", help="1..255: larger keeps superpixels square")
+    ap.add_argument("--snap-weighted", action="store_true", help="a vote weighs the confidence map (merged views or --tile)")
     ap.add_argument("images", nargs="+", metavar="IMG")
     args = ap.parse_args()
     try:
@@ -131,6 +139,12 @@ def main():
     elif args.morph_classes is not None or args.morph_shape != "disk":
         ap.error("--morph-classes and --morph-shape need --open, --close or --fill-holes")
 
+    snap = None
+    if args.snap is not None:
+        snap = dict(step=args.snap, compactness=args.snap_compactness, min_share=args.snap_share, weighted=args.snap_weighted)
+    elif args.snap_weighted or args.snap_share != 0.5 or args.snap_compactness != 20:
+        ap.error("--snap-share, --snap-compactness and --snap-weighted need --snap STEP")
+
     categories = None
     if args.coco_categories is not None:
         if not args.coco:
@@ -161,7 +175,7 @@ def main():
     try:
         segmenter = seg.Segmenter(models if tta is not None else models[0], target_size=args.size, interpolation=args.interpolation,
                                   palette=palette, batch_size=args.batch_size, sigma=args.sigma, clean=clean, tta=tta, tiles=tiles,
-                                  temperature=args.temperature, vectors=vectors, morph=morph)
+                                  temperature=args.temperature, vectors=vectors, morph=morph, snap=snap)
     except ValueError as e:
         ap.error(str(e))
     if args.confidence:
